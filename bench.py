@@ -27,6 +27,14 @@ mono, bit reservoir at 32 / 44.1 / 48 kHz (decode, frames/s) and re-encodes at 3
 `decode_only` is BASELINE config 2 (Huffman + decode transforms to float32 PCM, resident).  Multi-GPU: every rank owns
 its own batches (weak scaling, no collective on the data path) and runs regions (i) and (iii); torch is used only for the
 rendezvous / barrier / max-over-ranks (gloo).
+
+A plain run measures the headline alone: it builds the resident batch, warms up on untimed steps (--warmup steps, 3-10 more
+as --full's per-kernel pass, then max(--warmup, PLAIN_SETTLE_STEPS); no event pairs), times EXACTLY --steps steps of region (i)
+as one region and prints a short line (`value`, `ms_per_step` = wall clock of the region / --steps, max over ranks).  Everything else above -- the per-kernel table, the roofline and its rocprofv3 passes, the three
+regions behind `value_min` / `value_max`, the parity checks against the library and the oracle, the four-stream step,
+`decode_only`, the host-fed regions, config5 and the CPU baseline -- runs with --full, as it did before that option existed.
+--dump-outputs DIR (either mode) writes what the last timed step computed: its MP3 bytes, its message offset and a fixed
+sample of its int16 PCM (dump_outputs below).
 """
 import argparse
 import ctypes as C
@@ -68,6 +76,29 @@ def same_bytes(view, ref):
 
 def bits_of(s):
     return np.frombuffer("".join(format(b, "08b") for b in s.encode()).encode(), dtype=np.uint8) - ord("0")
+
+
+PLAIN_SETTLE_STEPS = 40         # a plain run: untimed steps directly in front of its one region, at least (main: the second warm-up)
+DUMP_MAX_MP3_BYTES = 8 << 20     # --dump-outputs: MP3 bytes kept whole up to this many (32 MiB as float32), a sample beyond
+DUMP_PCM_SAMPLES = 1 << 20       # ... and this many int16 PCM samples of the step's decode half, at fixed positions
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, mp3, hide_offset, pcm):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy (float32 / float64, at most 36 MiB in all): `mp3_bytes` = the MP3
+    stream out (the `data` a caller of Context.hide_message receives), `hide_offset` = where the message ended up (its `hide_offset`),
+    `pcm_int16_sample` = int16 PCM of the step's decode half (interleaved) at DUMP_PCM_SAMPLES positions drawn with DUMP_SEED, in
+    ascending order: the same positions in every run of the same arguments.  A stream longer than DUMP_MAX_MP3_BYTES is sampled the same way."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(a, k):
+        return a if a.size <= k else a[np.sort(rng.choice(a.size, size=k, replace=False))]
+    arrays = {"mp3_bytes": sample(mp3.reshape(-1), DUMP_MAX_MP3_BYTES).astype(np.float32),
+              "hide_offset": np.array([hide_offset], dtype=np.float64),
+              "pcm_int16_sample": sample(pcm.reshape(-1), DUMP_PCM_SAMPLES).astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def rank_host_record(rank, scan_threads, e2e_steady, host_share):
@@ -271,7 +302,7 @@ def live_pmc(frames, timeout_s=200):
                 return None, "time budget spent"
             out = os.path.join(td, name)
             cmd = [prof, "--kernel-trace", "--pmc"] + counters + ["--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
-                   "--resident-only", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-live-pmc", "--frames", str(frames)]
+                   "--full", "--resident-only", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-live-pmc", "--frames", str(frames)]
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=left)
             if r.returncode != 0:
                 if name == "sqt":                  # (an extra: the by-type counters are not what the roofline needs)
@@ -364,7 +395,12 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=10000, help="frames per GPU per step / per batch")
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps steps each; `value` is the median one (value_min / value_max beside it)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else this script measures and checks (see the top of the file); "
+                    "the options below from --e2e-batches to --no-live-pmc, except those that change the step itself (--no-overlap, --huffman-under, "
+                    "--lean-sync, --no-tail-stream, --decode-stream), only act with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (dump_outputs; rank 0's batch)")
+    ap.add_argument("--regions", type=int, default=None, help="timed regions of --steps steps each; `value` is the median one (value_min / value_max beside it); "
+                    "default 3 with --full, else 1")
     ap.add_argument("--e2e-batches", type=int, default=400, help="batches of the host-fed steady-state region (0 = skip)")
     ap.add_argument("--sustained-seconds", type=float, default=5.0, help="wall time of the `sustained` region: the host-fed steady state for that long, "
                     "frames/s of its first and last second, clocks and power from sysfs (0 = skip)")
@@ -398,6 +434,8 @@ def main():
     ap.add_argument("--decode-stream", choices=("on", "off"), default="off",
                     help="the decode transforms of batch k+1 on a context of their own, under the encode transforms and the rate loop of batch k")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 3 if args.full else 1
 
     # `python bench.py --gpus N` on its own (no torch.distributed.run in front): start the N ranks from here.  The parent
     # makes no GPU call and never exec()s; it relays rank 0's one json line and returns the worst exit code.
@@ -453,7 +491,7 @@ def main():
 
     # the counters behind roofline.traffic and roofline_alu, measured in THIS run (child processes, before the GPU is touched here)
     pmc_live, pmc_note = None, "committed profile (--no-live-pmc, --resident-only, or more than one rank)"
-    if world == 1 and rank == 0 and not args.no_live_pmc and not args.resident_only:
+    if args.full and world == 1 and rank == 0 and not args.no_live_pmc and not args.resident_only:
         pmc_live, pmc_note = live_pmc(args.frames)
     from mp3stego import _lib
     from synth_pcm import synth_pcm
@@ -528,11 +566,11 @@ def main():
     d_verdict = ctx.alloc(16)
     d_segout = ctx.alloc(80)
 
-    # the library's own answer for the same job (device pipeline of mp3s_encode_pcm: same kernels, same chain check)
-    pcm16 = ctx.decode_stream(mp3_in, _lib.MP3S_PCM_I16)["pcm"]
-    final = ctx.encode_pcm(pcm16, 44100, 128, hide)
-    gr = final["gr"]
-    active = (gr["flags"] & _lib.RF_ACTIVE) != 0
+    # the library's own answer for the same job (device pipeline of mp3s_encode_pcm: same kernels, same chain check); --full checks against it
+    if args.full:
+        pcm16 = ctx.decode_stream(mp3_in, _lib.MP3S_PCM_I16)["pcm"]
+        final = ctx.encode_pcm(pcm16, 44100, 128, hide)
+        gr = final["gr"]
     prep_s = time.time() - t_prep
     ctx.set_option("file_pipeline", 1)
 
@@ -676,63 +714,101 @@ def main():
                     pr[kname] = (pr[kname][0] + ms, pr[kname][1] + cnt)
         return pr, on_main
 
-    # ---- untimed pass with an event pair around every kernel: the per-kernel table and the choice of the dominant one.
+    # ---- untimed pass with an event pair around every kernel (--full): the per-kernel table and the choice of the dominant one.
     #      (An event pair costs stream time -- about 0.05 ms per step for all kernels -- so the timed region below
-    #      carries them only around the dominant kernel, whose duration the roofline is computed from.)
-    for c in (ctx, aux, aux2, dctx):
-        if c is not None:
-            c.profile_select(None)
-            c.profile_enable(True)
+    #      carries them only around the dominant kernel, whose duration the roofline is computed from.)  A plain run takes the same
+    #      steps without event pairs (behind the W = 5 warm-up steps alone, its region of the driver's 20 steps read 2-5 % low).
+    if args.full:
+        for c in (ctx, aux, aux2, dctx):
+            if c is not None:
+                c.profile_select(None)
+                c.profile_enable(True)
     n_prof = max(3, min(10, args.steps))
     run(n_prof)
     barrier()
-    prof_all, main_kernels = collect()
-    per_step = {k: ms / n_prof for k, (ms, cnt) in prof_all.items()}          # ms per step
-    # the dominant kernel is picked among those on the main stream: the front end on the second stream runs under
-    # them (its own duration is stretched by sharing the CUs and is not what bounds the step)
-    dom = max((kname for kname in per_step if kname in main_kernels), key=per_step.get)
-    # ---- timed region (i): K steps, HIP events around the dominant kernel only
-    for c in (ctx, aux, aux2, dctx):
-        if c is not None:
-            c.profile_select([dom])
-            c.profile_enable(True)
-    # The contract's region -- barrier, EXACTLY K steps, barrier -- is timed `--regions` times back to back (default 3); `value` is the median
-    # region, value_min / value_max the others: one region of the driver's 20 steps is 10 ms, of which 0.3-0.4 are the three streams filling
-    # and draining, and moved between 18.2 and 19.2 M frames/s from lease to lease (round-5 verdict, item 3).
+    if args.full:
+        prof_all, main_kernels = collect()
+        per_step = {k: ms / n_prof for k, (ms, cnt) in prof_all.items()}          # ms per step
+        # the dominant kernel is picked among those on the main stream: the front end on the second stream runs under
+        # them (its own duration is stretched by sharing the CUs and is not what bounds the step)
+        dom = max((kname for kname in per_step if kname in main_kernels), key=per_step.get)
+        # ---- timed region (i): K steps, HIP events around the dominant kernel only
+        for c in (ctx, aux, aux2, dctx):
+            if c is not None:
+                c.profile_select([dom])
+                c.profile_enable(True)
+    # The contract's region -- barrier, EXACTLY K steps, barrier -- is timed `--regions` times back to back (default 3 with --full, else 1); `value` is
+    # the median region, value_min / value_max the others: one region of the driver's 20 steps is 10 ms, of which 0.3-0.4 are the three streams
+    # filling and draining, and moved between 18.2 and 19.2 M frames/s from one machine to the next (round-5 verdict, item 3).
     walls, gpu_mss = [], []
     # The W warm-up steps once more, directly in front of the first region (no event pairs): between the warm-up at the top and this point lie
     # the per-kernel pass, its collection and a few ms of host work with the device idle, and the first of three regions read 0.4-2 % below the
-    # other two every time (value_regions, r06) -- the later regions start the moment the one before has ended.
-    for c in (ctx, aux, aux2, dctx):
-        if c is not None:
-            c.profile_select([])
-    run(args.warmup)
-    for c in (ctx, aux, aux2, dctx):
-        if c is not None:
-            c.profile_select([dom])
+    # other two every time (value_regions, r06) -- the later regions start the moment the one before has ended.  A plain run times ONE region,
+    # and the median of --full's three never is the first: behind W = 5 here (20 untimed steps in all) its region of the driver's 20 steps
+    # read 0.5-2 % below --full's median, as --full's first region does; it warms up on PLAIN_SETTLE_STEPS here instead, as many steps as stand
+    # in front of --full's second region at --steps 20 --warmup 5 (then 0.5183 ms per step against the median region's 0.5206, five runs each, alternating).
+    if args.full:
+        for c in (ctx, aux, aux2, dctx):
+            if c is not None:
+                c.profile_select([])
+    run(args.warmup if args.full else max(args.warmup, PLAIN_SETTLE_STEPS))
+    if args.full:
+        for c in (ctx, aux, aux2, dctx):
+            if c is not None:
+                c.profile_select([dom])
     for _ in range(max(1, args.regions)):
         barrier()
         t0 = time.perf_counter()
         ctx.timer_start()
-        run(args.steps, max(1, args.dom_events_every))
+        run(args.steps, max(1, args.dom_events_every) if args.full else 0)
         gpu_mss.append(ctx.timer_stop())
         barrier()
         walls.append(time.perf_counter() - t0)
     order = sorted(range(len(walls)), key=lambda i: walls[i])
     wall, gpu_ms = walls[order[len(order) // 2]], gpu_mss[order[len(order) // 2]]
-    prof, _ = collect()
-    for c in (ctx, aux, aux2, dctx):
-        if c is not None:
-            c.profile_enable(False)
-            c.profile_select(None)
+    if args.full:
+        prof, _ = collect()
+        for c in (ctx, aux, aux2, dctx):
+            if c is not None:
+                c.profile_enable(False)
+                c.profile_select(None)
     d_is, d_si, d_hst = d_is2[(state["k"] - 1) & 1], d_si2[(state["k"] - 1) & 1], d_hst2[(state["k"] - 1) & 1]
-
-    # ---------------------------------------------------------------- verify the timed work (untimed)
+    d_pcm_last = d_pcm if dctx is None else d_pcm2[(state["k"] - 1) & 1]
+    max_step = reduce_max(wall / args.steps)
+    value = n * world / max_step
     verdict = ctx.download(d_verdict, np.int32, (2,))
     segout = ctx.download(d_segout, _lib.CHAIN_SEG_OUT_DTYPE, (1,))
+    if args.dump_outputs and rank == 0:
+        # (a caller gets the stream without its last len % 4 bytes: the library writes whole words, as the reference does -- the check below)
+        dump_outputs(args.dump_outputs, ctx.download(d_mp3, np.uint8, ((int(frame_off[-1]) // 4) * 4,)), int(segout["cursor"][0]) - 32,
+                     ctx.download(d_pcm_last, np.int16, (n * 1152, 2)))
+    config = {"workload": f"{n}-frame full decode->stego-embed->re-encode pipeline per MI355X (BASELINE "
+                          "configs[2]); MP3 main data + side info resident in HBM, MP3 frames out; the message cursor chain is "
+                          "decided and the serial chains of the rate loop are checked on the device inside every step", "frames_per_gpu": n,
+              "sample_rate": 44100, "channels": 2, "bitrate_kbps": 128, "message_bits": int(len(hide)),
+              "chain_verdict_units_to_redo": int(verdict[0]), "message_variant_entries": n_ent}
+    if not args.full:
+        # ---------------------------------------------------------------- a plain run ends here: the headline and what it was measured on
+        if rank == 0:
+            config["parallelism"] = f"frames sharded over {world} GPU(s), no collective"
+            print(json.dumps({                      # (--full prints these fields and everything else it measures: the block at the end)
+                "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(max_step * 1e3, 4), "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f64 (decode) / int32 (encode)", "data": "synthetic", "config": config,
+                "full": False, "timed_regions": len(walls), "gpu_event_ms_per_step": round(gpu_ms / args.steps, 4), "timed_region_s": round(wall, 4),
+                "front_end_overlap": aux is not None, "tail_stream": aux2 is not None, "prep_s": round(prep_s, 2), "device": ctx.device_name()}))
+        for c in (aux, aux2, dctx):
+            if c is not None:
+                c.close()
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---------------------------------------------------------------- verify the timed work (untimed)
     got_gr = ctx.download(d_out, _lib.GR_OUT_DTYPE, (units,))
     got_ix = ctx.download(d_ix, np.int16, (n, 2, 2, 576))
-    got_pcm = ctx.download(d_pcm if dctx is None else d_pcm2[(state["k"] - 1) & 1], np.int16, (n * 1152, 2))
+    got_pcm = ctx.download(d_pcm_last, np.int16, (n * 1152, 2))
     got_mp3 = ctx.download(d_mp3, np.uint8, (int(frame_off[-1]),)).tobytes()
     same = note("bytes: resident step, chain verdict", int(verdict[0]) == 0 and int(verdict[1]) == 0)          # the chain check agrees: the step was the whole job
     same = note("bytes: resident step, message cursor", int(segout["cursor"][0]) - 32 == int(final["hide_offset"])) and same
@@ -753,8 +829,6 @@ def main():
         bool(np.array_equal(o_enc["ix"].astype(np.int16)[:k - 1], got_ix[:k - 1])) and \
         mp3_final[:len(o_enc["mp3"]) - 8] == o_enc["mp3"][:len(o_enc["mp3"]) - 8]
 
-    max_step = reduce_max(wall / args.steps)
-    value = n * world / max_step
     value_min = n * world / reduce_max(max(walls) / args.steps)
     value_max = n * world / reduce_max(min(walls) / args.steps)
     value_regions = [round(n * world / reduce_max(w / args.steps), 1) for w in walls]       # (in the order they were timed)
@@ -1337,13 +1411,8 @@ def main():
             "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(max_step * 1e3, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64 (decode) / int32 (encode)", "data": "synthetic",
-            "config": {"workload": f"{n}-frame full decode->stego-embed->re-encode pipeline per MI355X (BASELINE "
-                                   "configs[2]); MP3 main data + side info resident in HBM, MP3 frames out; the message cursor chain is "
-                                   "decided and the serial chains of the rate loop are checked on the device inside every step", "frames_per_gpu": n,
-                       "sample_rate": 44100, "channels": 2, "bitrate_kbps": 128, "message_bits": int(len(hide)),
-                       "chain_verdict_units_to_redo": int(verdict[0]), "message_variant_entries": n_ent, "pipeline_rate_passes": int(final["rate_passes"]),
-                       "parallelism": f"frames sharded over {world} GPU(s), no collective"},
-            "timed_regions": len(walls), "value_min": round(value_min, 1), "value_max": round(value_max, 1), "value_regions": value_regions,
+            "config": dict(config, pipeline_rate_passes=int(final["rate_passes"]), parallelism=f"frames sharded over {world} GPU(s), no collective"),
+            "full": True, "timed_regions": len(walls), "value_min": round(value_min, 1), "value_max": round(value_max, 1), "value_regions": value_regions,
             "value_spread": round((value_max - value_min) / value, 4),
             # the evidence the nested objects below hold, once more as scalars (a reader that keeps scalars only sees them)
             "sustained_frames_per_s": sustained["frames_per_s"] if sustained else None,

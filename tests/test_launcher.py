@@ -20,7 +20,9 @@ CHILD = textwrap.dedent("""
     assert os.environ["LOCAL_RANK"] == str(r) and os.environ["LOCAL_WORLD_SIZE"] == str(w)
     assert os.environ["MASTER_ADDR"] == "127.0.0.1" and int(os.environ["MASTER_PORT"]) > 0
     mode = sys.argv[1]
-    print("stderr of rank", r, file=sys.stderr)
+    # (one string, one write: with Python's stdio unbuffered -- PYTHONUNBUFFERED -- print() writes every argument on its own, and the
+    #  ranks' pieces interleave in the shared file)
+    sys.stderr.write("stderr of rank %d\\n" % r)
     if mode == "gloo":
         import torch, torch.distributed as dist
         dist.init_process_group(backend="gloo", rank=r, world_size=w)
@@ -29,7 +31,7 @@ CHILD = textwrap.dedent("""
         if r == 0:
             print(json.dumps({"n_gpus": w, "sum": float(t[0])}))
         else:
-            print("noise from rank", r)             # must not reach the job's stdout
+            sys.stdout.write("noise from rank %d\\n" % r)   # must not reach the job's stdout
     elif mode == "fail1":
         if r == 1:
             sys.exit(7)
@@ -96,7 +98,7 @@ def test_timeout(tmp_path):
     assert rc == launch_ranks.E_TIMEOUT
 
 
-def test_bench_py_refuses_more_ranks_than_devices():
+def test_bench_py_refuses_more_ranks_than_devices(built):
     """the parent's path in bench.py itself: no GPU here, so --gpus 2 without MP3STEGO_DEVICE must end with the usage code and no
     json line (the old bench.py ignored --gpus and printed n_gpus 1)"""
     env = {k: v for k, v in os.environ.items() if k not in ("MP3STEGO_DEVICE", "WORLD_SIZE", "RANK")}

@@ -237,7 +237,7 @@ def test_bench_gpus2_starts_its_own_ranks():
     processes (tools/launch_ranks.py), both pinned to the test box's one GPU, and relays rank 0's one json line"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MP3STEGO_DEVICE"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--no-config5", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "5", "--no-config5", "--no-cpu-baseline",
                         "--no-single-file-100k", "--e2e-batches", "40", "--frames", "2000"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -256,7 +256,7 @@ def test_five_ranks_side_by_side_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MP3STEGO_DEVICE"] = "0"
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--steps", "3", "--no-config5", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "5", "--steps", "3", "--no-config5", "--no-cpu-baseline",
                         "--no-single-file-100k", "--no-short-files", "--e2e-batches", "20", "--sustained-seconds", "0", "--frames", "2000"],
                        env=env, capture_output=True, text=True, timeout=900)
     wall = time.time() - t0

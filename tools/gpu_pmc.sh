@@ -3,7 +3,7 @@
 # usage: bash tools/gpu_pmc.sh <tag> [program and arguments instead of the bench's resident step, e.g. python3 tools/dec_only.py]
 TAG=${1:-r01}
 shift
-if [ $# -eq 0 ]; then set -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --resident-only; fi
+if [ $# -eq 0 ]; then set -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --resident-only; fi
 PROG=("$@")
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
