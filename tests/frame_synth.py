@@ -88,26 +88,43 @@ def put_quad(bw, table_b, v):
             bw.put(1 if q < 0 else 0, 1)
 
 
+def _at(v, f):
+    """a per-stream scalar, or frame f's entry of a per-frame sequence"""
+    return v if np.isscalar(v) or isinstance(v, bool) else v[f]
+
+
 def make_stream(seed, n_frames, sr_idx=0, bitrate_idx=9, mode=0, mode_ext=0, crc=False, block_types=(0,),
-                allow_mixed=False, use_reservoir=True, tables=None, max_lin=40, id3=False):
-    """Returns the bytes of an MP3 stream.  mode: 0 stereo, 1 joint, 3 mono."""
+                allow_mixed=False, use_reservoir=True, tables=None, max_lin=40, id3=False, max_mdb=500, fill=1.0):
+    """Returns the bytes of an MP3 stream.  mode: 0 stereo, 1 joint, 3 mono.
+
+    sr_idx, bitrate_idx, mode, mode_ext and crc are one value for the stream or a sequence of one per frame (VBR, rate
+    switches): the bit reservoir then spans frames of different sizes.  sr_idx 3 writes the reserved rate bits into a frame
+    that is laid out at the rate of the frame before it, as the reference reads it (FrameHeader.py:112-121 keeps the rate).
+    max_mdb bounds main_data_begin (<= 511); fill < 1 lets the granules use less than their frame's share, so that the
+    reservoir grows to max_mdb and small frames reach back across many frames."""
+    assert 0 <= max_mdb <= 511
     rng = np.random.default_rng(seed)
-    nch = 1 if mode == 3 else 2
-    side_len = 17 if nch == 1 else 32
     tables = list(tables or [1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 16, 17, 19, 21, 23, 24, 26, 29, 31, 0])
     frames = []      # (header bytes, side-info writer fn needing main_data_begin, main data bytes, capacity)
     area_pos = data_pos = 0
     out_frames = []
+    sr_eff = None
     for f in range(n_frames):
-        pad = int(rng.integers(0, 2)) if sr_idx == 0 else 0
-        fsize = 144 * BITRATES[bitrate_idx] * 1000 // RATES[sr_idx] + pad
-        cap = fsize - 4 - side_len - (2 if crc else 0)
+        sr_bits, bitrate_f, mode_f, crc_f = _at(sr_idx, f), _at(bitrate_idx, f), _at(mode, f), bool(_at(crc, f))
+        sr_f = sr_bits if sr_bits != 3 else sr_eff                # reserved bits: the rate of the frame before
+        assert sr_f is not None, "a stream cannot start with the reserved rate"
+        sr_eff = sr_f
+        nch = 1 if mode_f == 3 else 2
+        side_len = 17 if nch == 1 else 32
+        pad = int(rng.integers(0, 2)) if sr_f == 0 else 0
+        fsize = 144 * BITRATES[bitrate_f] * 1000 // RATES[sr_f] + pad
+        cap = fsize - 4 - side_len - (2 if crc_f else 0)
         md = Bits()
         gran = [[None, None], [None, None]]
         scfsi = [[0] * 4 for _ in range(2)]
         mdb = area_pos - data_pos                         # bytes of reservoir in front of this frame's own area
         remaining = ((mdb if use_reservoir else 0) + cap) * 8 - 8
-        want = int(cap * 8 * (0.55 + 0.8 * rng.random())) // (2 * nch)
+        want = int(cap * 8 * (0.55 + 0.8 * rng.random()) * fill) // (2 * nch)
         units_left = 2 * nch
         for gr in range(2):
             for ch in range(nch):
@@ -150,12 +167,12 @@ def make_stream(seed, n_frames, sr_idx=0, bitrate_idx=9, mode=0, mode_ext=0, crc
                     if bt == 2:
                         reg0, reg1 = 36, 576
                     else:
-                        reg0, reg1 = SFB_LONG[sr_idx][r0c + 1], SFB_LONG[sr_idx][r0c + 1 + r1c + 1]
+                        reg0, reg1 = SFB_LONG[sr_f][r0c + 1], SFB_LONG[sr_f][r0c + 1 + r1c + 1]
                     ts = [int(rng.choice(tables)), int(rng.choice(tables)), 0]
                 else:
                     r0c = int(rng.integers(0, 16))
                     r1c = int(rng.integers(0, min(8, 21 - r0c)))
-                    reg0, reg1 = SFB_LONG[sr_idx][r0c + 1], SFB_LONG[sr_idx][r0c + 1 + r1c + 1]
+                    reg0, reg1 = SFB_LONG[sr_f][r0c + 1], SFB_LONG[sr_f][r0c + 1 + r1c + 1]
                     ts = [int(rng.choice(tables)) for _ in range(3)]
                 # ---- big values until the bit budget is used
                 big_values = 0
@@ -200,10 +217,10 @@ def make_stream(seed, n_frames, sr_idx=0, bitrate_idx=9, mode=0, mode_ext=0, crc
         # ---- bit reservoir: this frame's data starts mdb bytes before its own area
         if not use_reservoir:
             md_bytes += bytes(cap - len(md_bytes))
-        elif mdb + cap - len(md_bytes) > 500:                 # keep main_data_begin <= 511: stuff this frame
-            md_bytes += bytes(mdb + cap - len(md_bytes) - 500)
+        elif mdb + cap - len(md_bytes) > max_mdb:             # keep main_data_begin <= max_mdb: stuff this frame
+            md_bytes += bytes(mdb + cap - len(md_bytes) - max_mdb)
         assert len(md_bytes) <= mdb + cap, (f, len(md_bytes), mdb, cap)
-        hdr = [0xFF, 0xFA | (0 if crc else 1), (bitrate_idx << 4) | (sr_idx << 2) | (pad << 1), (mode << 6) | (mode_ext << 4)]
+        hdr = [0xFF, 0xFA | (0 if crc_f else 1), (bitrate_f << 4) | (sr_bits << 2) | (pad << 1), (mode_f << 6) | (_at(mode_ext, f) << 4)]
         si = Bits()
         si.put(mdb, 9)
         si.put(0, 5 if nch == 1 else 3)
@@ -225,7 +242,7 @@ def make_stream(seed, n_frames, sr_idx=0, bitrate_idx=9, mode=0, mode_ext=0, crc
                     si.put(g["r0c"], 4); si.put(g["r1c"], 3)
                 si.put(g["pre"], 1); si.put(g["sfs"], 1); si.put(g["c1"], 1)
         assert len(si) == side_len * 8
-        out_frames.append((bytes(hdr) + (b"\xAB\xCD" if crc else b"") + si.bytes(), cap))
+        out_frames.append((bytes(hdr) + (b"\xAB\xCD" if crc_f else b"") + si.bytes(), cap))
         frames.append(md_bytes)
         data_pos += len(md_bytes)
         area_pos += cap
@@ -240,6 +257,14 @@ def make_stream(seed, n_frames, sr_idx=0, bitrate_idx=9, mode=0, mode_ext=0, crc
     if id3:
         out = bytearray(b"ID3\x03\x00\x00" + bytes([0, 0, 0, 23]) + b"TIT2" + bytes([0, 0, 0, 13, 0, 0]) + b"\x00synth title\x00") + out
     return bytes(out)
+
+
+def concat(*streams):
+    """one stream of several make_stream results (without ID3 tags): each starts with main_data_begin = 0, so segments
+    with other headers, or many copies of a few synthesised frames, join into a valid stream of any length"""
+    for s in streams:
+        assert s[:3] != b"ID3" and s[0] == 0xFF and (s[4 + (0 if s[1] & 1 else 2)] << 1 | s[5 + (0 if s[1] & 1 else 2)] >> 7) == 0
+    return b"".join(streams)
 
 
 CORPUS = {
