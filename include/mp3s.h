@@ -701,6 +701,23 @@ int mp3s_clear_file_fd(mp3s_ctx *ctx, const uint8_t *mp3, size_t len, int fd, mp
  * NULL the first such code fails the whole call. */
 int mp3s_hide_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, const uint8_t *const *msgs,
                        const size_t *msg_lens, mp3s_buf **owner, mp3s_file *out, int32_t *status);
+/* replaces: a loop of Encoder(...).encode() over a list of WAV files -- reference encoder/encoder.py:21-58 (WAV_Reader.py:30-111 for
+ * each header, MP3_Encoder.py:596-618 for the frame loop).  All files with the same sampling rate and bitrate go through the
+ * device as ONE batch: one upload of the WAV images as the caller holds them (no host copy of the samples; a data chunk at an odd
+ * offset is put right on the device, k_wav_gather), transforms, rate loop with the message variants, chain check, bit packing, one
+ * download -- many short files cost about what one long file of the same total length costs.  bitrate_kbps[i] = bitrate of file
+ * i; hide_bits[i] / n_hide[i] = its message as 0/1 bytes, as for mp3s_encode_file (hide_bits NULL = nothing hidden anywhere).
+ * out[i] is byte for byte and field for field what mp3s_encode_file gives for file i alone.  status[i] = MP3S_OK or the code file
+ * i alone would have failed with (MP3S_E_EXIT with the reference's text for a rate or bitrate it refuses, MP3S_E_UNSUPPORTED for
+ * mono and for a file that ends inside its last frame, MP3S_E_ARG), its out[i] zeroed; with status == NULL the first such code
+ * fails the whole call -- the same rule as mp3s_hide_messages. */
+int mp3s_encode_files(mp3s_ctx *ctx, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                      const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status);
+/* test aid: the first device step of mp3s_encode_files alone -- the images of these WAV files (stereo, any supported rate) go up and
+ * k_wav_gather lays their frames back to back; pcm = room for cap_frames frames of [1152][2] int16, *n_frames = the frames of all files
+ * (np.fromfile + the frame slicing of reference encoder/WAV_Reader.py:108, MP3_Encoder.py:596-618, the over-read frame of E3 included) */
+int mp3s_debug_wav_gather(mp3s_ctx *ctx, const uint8_t *const *wavs, const size_t *lens, int n_files, int16_t *pcm, int64_t cap_frames,
+                          int64_t *n_frames);
 /* The share of one rank in hiding a message in (utf8 != NULL) or clearing (NULL) ONE stream that is spread over `world`
  * ranks: the stream's PCM frames (repeated last frame included) are cut into `world` contiguous blocks, sizes
  * differing by at most one; this call decodes block `rank` -- one frame of decoder state and one frame of PCM in front of
@@ -773,6 +790,17 @@ int mp3s_pipe_submit(mp3s_pipe *pipe, const uint8_t *const *mp3s, const size_t *
 /* a decode job: the files of one mp3s_decode_file loop, MP3 bytes -> WAV bytes (int16) + stego bits per file; results
  * through mp3s_pipe_collect like those of the other jobs (out[i].data = the WAV image, bits / n_bits set) */
 int mp3s_pipe_submit_decode(mp3s_pipe *pipe, const uint8_t *const *mp3s, const size_t *lens, int n_files, int64_t *ticket);
+/* an encode job: the files of one mp3s_encode_files call (same arguments, same results byte for byte), WAV bytes -> MP3 bytes --
+ * replaces a loop of Encoder(...).encode(), reference encoder/encoder.py:21-58, as the hide job replaces a loop of hide_message.
+ * Stages: a worker reads the headers and lays out the encoder's inputs || the WAV images go up as they are (4 608 bytes per frame:
+ * the largest transfer the library has) || k_wav_gather on the front-end stream, under the rate loop of the job in front || encode
+ * side || download.  A job of more than one (sampling rate, bitrate) group, with a file that fails its checks, or larger than the
+ * slot (frames: max_job_bytes / 96, the frames an MP3 job of that size can have -- the slot's WAV image is made from that count when
+ * its first encode job comes --, and MP3 bytes OUT: max_job_bytes.  That image costs 48 x max_job_bytes of device memory per slot (402 MB for 8 MB jobs), + page-locked staging
+ * as large as the short files -- below 256 KB each -- of the slot's jobs have needed so far) goes through mp3s_encode_files and counts as `slow`.  Results through mp3s_pipe_collect; the WAV and
+ * hide_bits buffers are borrowed until then (bitrate_kbps and n_hide are copied). */
+int mp3s_pipe_submit_encode(mp3s_pipe *pipe, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                            const uint8_t *const *hide_bits, const int32_t *n_hide, int64_t *ticket);
 /* waits for the OLDEST job in flight and hands out its results: out[i] / status[i] as mp3s_hide_messages fills them
  * (max_files = room in both arrays), *n_files = files of that job.  MP3S_E_BUSY: nothing in flight. */
 int mp3s_pipe_collect(mp3s_pipe *pipe, int64_t *ticket, mp3s_buf **owner, mp3s_file *out, int32_t *status, int max_files,

@@ -109,6 +109,12 @@ constexpr int kParseInherits = 1, kParseMismatch = 2;
 int launch_parse(hipStream_t stream, const uint8_t *d_image, uint32_t image_base, const FrameRef *d_refs, const StreamRef *d_streams, int n_frames,
                  uint32_t md_base, mp3s_frame_side *d_side, mp3s_frame_hdr *d_hdr, uint8_t *d_blob, uint64_t *d_tsel, int32_t *d_status);
 
+// WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
+// alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
+struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes
+constexpr size_t kWavSlack = 32;
+int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
+
 constexpr size_t kPlaceEntry = 4912;   // [int32 frame, pad to 16 | int16 is[2304] | mp3s_granule_si si[4]]
 int launch_place_frames(hipStream_t stream, const uint8_t *d_entries, int n_entries, int16_t *d_is, mp3s_granule_si *d_si);
 int launch_copy(hipStream_t stream, const void *d_src, void *d_dst, size_t bytes);

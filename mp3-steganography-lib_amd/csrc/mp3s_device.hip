@@ -24,6 +24,7 @@ __constant__ DevTables c_tab;
 #include "k_parse.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
+#include "k_wav.hpp"
 
 namespace mp3s {
 
@@ -428,6 +429,19 @@ __global__ __launch_bounds__(256) void k_copy16(const uint4 *__restrict__ src, u
 int launch_copy(hipStream_t stream, const void *d_src, void *d_dst, size_t bytes)
 {
     hipLaunchKernelGGL(k_copy16, dim3(256 * 16), dim3(256), 0, stream, (const uint4 *)d_src, (uint4 *)d_dst, bytes / 16);
+    return (int)hipGetLastError();
+}
+
+// one grid row per stream; a row's workgroups walk the stream's PCM in strides (the longest stream sizes the row: the groups
+// of a short stream behind its end return at once).  Measured for batches of like streams (one long file; 250 files of 40 frames);
+// a batch of one long and very many short files launches up to 2 048 groups per short stream that find nothing to do -- correct, and
+// not measured: a flat grid over 1 KB runs with a prefix table is the form for it)
+int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *d_runs, int n_runs, int max_frames, int16_t *d_pcm)
+{
+    if (n_runs <= 0 || max_frames <= 0) return 0;
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)max_frames * 288 + 255) / 256, 2048);
+    for (int r0 = 0; r0 < n_runs; r0 += 32768)
+        hipLaunchKernelGGL(k_wav_gather, dim3(gx, (unsigned)std::min(n_runs - r0, 32768)), dim3(256), 0, stream, d_image, d_runs, r0, d_pcm);
     return (int)hipGetLastError();
 }
 

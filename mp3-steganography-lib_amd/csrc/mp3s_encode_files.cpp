@@ -1,0 +1,188 @@
+// C-ABI of the library (include/mp3s.h), part 3b: a list of WAV files in, MP3 files out -- the files of one (sampling rate,
+// bitrate) as ONE device batch.  The WAV bytes go to the device as the caller holds them; k_wav_gather (k_wav.hpp) makes
+// the PCM buffer of the batch out of them there, and encode_batch takes it from HBM as it takes the PCM a decode left.
+#include "pipe_internal.h"
+
+// what mp3s_encode_file checks of a file before the device sees it, in its order: the header (wav_parse: MP3S_E_EXIT with the
+// reference's text, MP3S_E_MALFORMED), the frame count (wav_frame_count: MP3S_E_UNSUPPORTED), the message arguments
+int wav_encode_check(const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, mp3s_wav_info *w, int64_t *count)
+{
+    if (!wav) return fail(MP3S_E_ARG, "null pointer");
+    const char *msg = "";
+    int rc = wav_parse(wav, len, bitrate_kbps, w, &msg);
+    if (!rc) rc = wav_frame_count(*w, count, &msg);
+    if (rc) return fail(rc, "%s", msg);
+    if (n_hide < 0 || (n_hide > 0 && !hide_bits)) return fail(MP3S_E_ARG, "bad hide arguments");
+    if (*count > 0x7fffffff / 8) return fail(MP3S_E_ARG, "too many frames");
+    return MP3S_OK;
+}
+
+namespace {
+
+struct WavIn {
+    const uint8_t *wav; size_t len;
+    const uint8_t *hide; int n_hide;
+    mp3s_wav_info w; int64_t count;
+};
+
+// the files `idx` to the device: their images up, the gather queued on the context's stream -> *d_pcm_out = [n_all][1152][2] int16 in
+// the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is waited for; `runs` and the
+// callers' bytes are read by copies in flight until the stream is synchronised.
+int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, std::vector<WavRun> &runs,
+                  void **d_pcm_out, int64_t *n_all_out)
+{
+    segs.assign(idx.size(), EncSeg());
+    runs.assign(idx.size(), WavRun());
+    std::vector<size_t> at(idx.size());
+    int64_t n_all = 0, max_frames = 0;
+    size_t img = 0, staged = 0;
+    for (size_t k = 0; k < idx.size(); k++) {
+        const WavIn &f = in[(size_t)idx[k]];
+        segs[k].n_frames = (int)f.count; segs[k].hide = f.hide; segs[k].n_hide = f.n_hide;
+        img = (img + 15) & ~(size_t)15;
+        at[k] = img;
+        runs[k].src = (uint64_t)img + (uint64_t)f.w.data_offset; runs[k].first_frame = (uint32_t)n_all; runs[k].n_frames = (uint32_t)f.count;
+        const size_t need = (size_t)f.w.data_offset + (size_t)f.count * 4608;   // (inside the file: wav_frame_count)
+        if (need < kDirectUpload) staged = img + need;
+        img += need;
+        n_all += f.count; max_frames = std::max(max_frames, f.count);
+        if (n_all > 0x7fffffff / 8) return fail(MP3S_E_ARG, "encode batch too large");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t runs_at = (img + kWavSlack + 15) & ~(size_t)15;
+    uint8_t *d_image = (uint8_t *)c->grab(27, runs_at + runs.size() * sizeof(WavRun));
+    void *d_pcm = c->grab(7, (size_t)n_all * 4608);
+    if (!d_image || !d_pcm) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of WAV input", (long long)n_all);
+    // long files go up from where they lie; short ones are laid end to end first, bytes as they are, and travel in runs
+    // (one copy per run instead of one per file: a copy from ordinary memory costs its thread 10 us and more whatever its size)
+    std::vector<uint8_t> &stage = c->h_blob;
+    if (stage.size() < staged) stage.resize(staged);
+    size_t run_lo = 0, run_hi = 0;
+    auto flush = [&]() {
+        if (run_hi > run_lo) HIPCHK(hipMemcpyAsync(d_image + run_lo, stage.data() + run_lo, run_hi - run_lo, hipMemcpyHostToDevice, c->stream));
+        run_lo = run_hi = 0;
+        return (int)MP3S_OK;
+    };
+    for (size_t k = 0; k < idx.size(); k++) {
+        const WavIn &f = in[(size_t)idx[k]];
+        const size_t need = (size_t)f.w.data_offset + (size_t)f.count * 4608;
+        if (need >= kDirectUpload) {
+            const int rc = flush();
+            if (rc) return rc;
+            const double t0 = trace_on() ? now_ms() : 0;
+            HIPCHK(hipMemcpyAsync(d_image + at[k], f.wav, need, hipMemcpyHostToDevice, c->stream));
+            if (trace_on()) fprintf(stderr, "mp3s:   encode_files: queueing the copy of %zu bytes from the caller's memory took %.3f ms\n", need, now_ms() - t0);
+        } else {
+            if (run_hi == run_lo) run_lo = at[k];
+            std::memcpy(stage.data() + at[k], f.wav, need);
+            run_hi = at[k] + need;
+        }
+    }
+    int rc = flush();
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(d_image + runs_at, runs.data(), runs.size() * sizeof(WavRun), hipMemcpyHostToDevice, c->stream));
+    if (launch_wav_gather(c->stream, d_image, (const WavRun *)(d_image + runs_at), (int)runs.size(), (int)max_frames, (int16_t *)d_pcm))
+        return fail(MP3S_E_HIP, "gathering the WAV samples failed");
+    *d_pcm_out = d_pcm; *n_all_out = n_all;
+    return MP3S_OK;
+}
+
+// the files `idx` (one sampling rate and bitrate) as one batch: images up, gather, encode_batch on the PCM in HBM.  The batch's
+// bytes are kept in a new part of `top`; out[i] points into it.
+int encode_group(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, int samplerate, int kbps, mp3s_buf *top, mp3s_file *out)
+{
+    std::vector<EncSeg> segs;
+    std::vector<WavRun> runs;
+    void *d_pcm = nullptr;
+    int64_t n_all = 0;
+    int rc = wav_to_device(c, in, idx, segs, runs, &d_pcm, &n_all);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    std::unique_ptr<mp3s_buf> part(new mp3s_buf());
+    int passes = 0;
+    rc = encode_batch(c, nullptr, (const int16_t *)d_pcm, segs, samplerate, kbps, part.get(), &passes, false);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }     // (`runs` is the source of a copy that may still be in flight)
+    for (size_t k = 0; k < idx.size(); k++) {
+        mp3s_file &o = out[idx[k]];
+        std::memset(&o, 0, sizeof o);
+        o.data = part->mp3 + segs[k].mp3_off; o.len = segs[k].mp3_len;
+        o.kbps = kbps; o.sampling_rate = samplerate; o.channels = 2; o.n_frames = segs[k].n_frames;
+        o.hide_offset = segs[k].hide_offset;
+        o.too_long = segs[k].hide_offset < (int64_t)segs[k].n_hide - 1 ? 1 : 0;
+    }
+    top->parts.push_back(std::move(part));
+    return MP3S_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mp3s_encode_files(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                      const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status)
+{
+    if (!c || !wavs || !lens || !bitrate_kbps || !owner || !out || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");
+    std::unique_ptr<mp3s_buf> top(new mp3s_buf());
+    std::vector<WavIn> in((size_t)n_files);
+    std::vector<int32_t> st((size_t)n_files, MP3S_OK);
+    std::vector<std::string> why((size_t)n_files);
+    struct Group { int rate, kbps; std::vector<int> idx; };
+    std::vector<Group> groups;
+    for (int i = 0; i < n_files; i++) {
+        WavIn &f = in[(size_t)i];
+        std::memset(&out[i], 0, sizeof out[i]);
+        f.wav = wavs[i]; f.len = lens[i];
+        f.hide = hide_bits ? hide_bits[i] : nullptr; f.n_hide = hide_bits ? n_hide[i] : 0;
+        st[(size_t)i] = wav_encode_check(f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.w, &f.count);
+        if (st[(size_t)i]) { why[(size_t)i] = mp3s_last_error(); continue; }
+        size_t g = 0;
+        while (g < groups.size() && (groups[g].rate != f.w.samplerate || groups[g].kbps != bitrate_kbps[i])) g++;
+        if (g == groups.size()) groups.push_back({f.w.samplerate, bitrate_kbps[i], {}});
+        groups[g].idx.push_back(i);
+    }
+    for (const Group &g : groups) {
+        const int rc = encode_group(c, in, g.idx, g.rate, g.kbps, top.get(), out);
+        if (!rc) continue;
+        (void)hipStreamSynchronize(c->stream);   // (copies of the failed batch may still read the callers' bytes and the staging)
+        // one file spoils its batch (a quantizer step that leaves the table ...): each file on its own, to name it
+        std::string first = mp3s_last_error();
+        for (int i : g.idx) {
+            st[(size_t)i] = g.idx.size() == 1 ? rc : encode_group(c, in, std::vector<int>{i}, g.rate, g.kbps, top.get(), out);
+            if (st[(size_t)i]) { why[(size_t)i] = g.idx.size() == 1 ? first : std::string(mp3s_last_error()); std::memset(&out[i], 0, sizeof out[i]); }
+        }
+    }
+    int first_bad = MP3S_OK;
+    for (int i = 0; i < n_files; i++) {
+        if (status) status[i] = st[(size_t)i];
+        if (st[(size_t)i] && !first_bad) { first_bad = st[(size_t)i]; fail(first_bad, "%s", why[(size_t)i].c_str()); }   // the text of the first file that failed
+    }
+    if (!status && first_bad) return first_bad;
+    *owner = top.release();
+    return MP3S_OK;
+}
+
+int mp3s_debug_wav_gather(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, int16_t *pcm, int64_t cap_frames, int64_t *n_frames)
+{
+    if (!c || !wavs || !lens || !pcm || !n_frames || n_files <= 0) return fail(MP3S_E_ARG, "bad argument");
+    std::vector<WavIn> in((size_t)n_files);
+    std::vector<int> idx((size_t)n_files);
+    int64_t total = 0;
+    for (int i = 0; i < n_files; i++) {
+        WavIn &f = in[(size_t)i];
+        f.wav = wavs[i]; f.len = lens[i]; f.hide = nullptr; f.n_hide = 0;
+        const int rc = wav_encode_check(f.wav, f.len, 128, nullptr, 0, &f.w, &f.count);
+        if (rc) return rc;
+        idx[(size_t)i] = i; total += f.count;
+    }
+    *n_frames = total;
+    if (total > cap_frames) return fail(MP3S_E_ARG, "%lld frames, room for %lld", (long long)total, (long long)cap_frames);
+    std::vector<EncSeg> segs;
+    std::vector<WavRun> runs;
+    void *d_pcm = nullptr;
+    int64_t n_all = 0;
+    int rc = wav_to_device(c, in, idx, segs, runs, &d_pcm, &n_all);
+    if (!rc) rc = mp3s_dev_download(c, pcm, d_pcm, (size_t)n_all * 4608);
+    else (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+}  // extern "C"

@@ -659,17 +659,10 @@ int mp3s_encode_file(mp3s_ctx *c, const uint8_t *wav, size_t len, int bitrate_kb
     mp3s_wav_info w;
     int rc = mp3s_wav_parse(wav, len, bitrate_kbps, &w);
     if (rc) return rc;
-    // MP3_Encoder.py:596-618 walks num_of_samples * channels values in steps of 1152 * channels and indexes the buffer
-    // as if it were stereo: mono input and a partial last frame both end in IndexError there
-    if (w.channels != 2) return fail(MP3S_E_UNSUPPORTED, "mono input: the reference encoder indexes the sample buffer out of bounds");
-    // count whole frames, plus one more when samples are left over (:611-614): that frame is read from whatever follows in
-    // the buffer -- np.fromfile was asked for twice the declared count (WAV_Reader.py:108), so a chunk behind the data
-    // chunk, or the second half of samples that are not 16 bits wide, is taken for audio; only a buffer that ends inside
-    // the frame raises (IndexError)
-    const int64_t total = w.num_of_samples * 2;
-    const int64_t count = total / 2304 + (total % 2304 ? 1 : 0);
-    if (count <= 0 || w.n_values < count * 2304)
-        return fail(MP3S_E_UNSUPPORTED, "sample count is not a multiple of 1152 per channel and the file ends inside the last frame: the reference encoder reads past the end of the sample buffer");
+    int64_t count = 0;
+    const char *msg = "";
+    rc = wav_frame_count(w, &count, &msg);   // (mono, and a file that ends inside its last frame, are refused)
+    if (rc) return fail(rc, "%s", msg);
     std::vector<int16_t> pcm((size_t)count * 2304);   // the data chunk may sit at an odd offset
     std::memcpy(pcm.data(), wav + w.data_offset, pcm.size() * 2);
     mp3s_encoded e;

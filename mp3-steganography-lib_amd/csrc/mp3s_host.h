@@ -155,6 +155,10 @@ int format_stream(int samplerate, int bitrate_kbps, int n_frames, const int16_t 
 // ---- container formats and message framing (mp3s_host_files.cpp)
 // reference encoder/WAV_Reader.py:30-111; *msg = the reference's sys.exit text when MP3S_E_EXIT is returned
 int wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_info *out, const char **msg);
+// the frames the reference's encoder makes of a parsed WAV file (encoder/MP3_Encoder.py:596-618): MP3S_OK and *count, or
+// MP3S_E_UNSUPPORTED with *msg where the reference ends in IndexError (mono; a file that ends inside its last frame).  The ONE
+// statement of the rule: mp3s_encode_file, mp3s_encode_files and the pipe's encode jobs all ask here.
+int wav_frame_count(const mp3s_wav_info &w, int64_t *count, const char **msg);
 // the 44-byte header scipy.io.wavfile.write emits for int16 data
 void wav_header(int64_t n_rows, int nch, int rate, uint8_t *out44);
 // reference steganography.py:10-24, 42-50

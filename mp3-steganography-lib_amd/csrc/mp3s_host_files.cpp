@@ -120,6 +120,26 @@ int wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_info *
     return MP3S_OK;
 }
 
+int wav_frame_count(const mp3s_wav_info &w, int64_t *count_out, const char **msg)
+{
+    // MP3_Encoder.py:596-618 walks num_of_samples * channels values in steps of 1152 * channels and indexes the buffer
+    // as if it were stereo: mono input and a partial last frame both end in IndexError there
+    *count_out = 0;
+    *msg = "mono input: the reference encoder indexes the sample buffer out of bounds";
+    if (w.channels != 2) return MP3S_E_UNSUPPORTED;
+    // count whole frames, plus one more when samples are left over (:611-614): that frame is read from whatever follows in
+    // the buffer -- np.fromfile was asked for twice the declared count (WAV_Reader.py:108), so a chunk behind the data
+    // chunk, or the second half of samples that are not 16 bits wide, is taken for audio; only a buffer that ends inside
+    // the frame raises (IndexError)
+    const int64_t total = w.num_of_samples * 2;
+    const int64_t count = total / 2304 + (total % 2304 ? 1 : 0);
+    *msg = "sample count is not a multiple of 1152 per channel and the file ends inside the last frame: the reference encoder reads past the end of the sample buffer";
+    if (count <= 0 || w.n_values < count * 2304) return MP3S_E_UNSUPPORTED;
+    *count_out = count;
+    *msg = "";
+    return MP3S_OK;
+}
+
 // the 44 bytes scipy.io.wavfile.write puts in front of int16 data (reference MP3_Parser.py:86-93 -> scipy)
 void wav_header(int64_t n_rows, int nch, int rate, uint8_t *h)
 {

@@ -351,6 +351,11 @@ int select_plan(const mp3s_chain_seg *segs, int n_segs, mp3s_select_span *spans,
                 const int32_t *min_reach);
 void tables_guess_of(const mp3s_frame_side *side, long n_frames, int extra, std::vector<uint8_t> &out);
 
+// ---------------------------------------------------------------- WAV files as device batches (mp3s_encode_files.cpp)
+// what mp3s_encode_file checks of a file before the device sees it, in its order (header, frame count, message arguments);
+// MP3S_OK with *w and *count (frames), or the code and text the one-file call fails with
+int wav_encode_check(const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, mp3s_wav_info *w, int64_t *count);
+
 // ---------------------------------------------------------------- one file as chunks through the overlapped stages (run_file.cpp)
 constexpr int kRunFallback = 1;          // run_file: not for this path -- the caller takes the synchronous one (same bytes)
 constexpr int kRunHide = 0, kRunClear = 1, kRunDecode = 2;

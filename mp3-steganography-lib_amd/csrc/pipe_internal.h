@@ -21,6 +21,10 @@ struct Slot {
            stage_bytes = 0;
     uint8_t *d_image = nullptr; size_t image_cap = 0;   // the file bytes of a walked job
     uint8_t *h_image = nullptr;                          // page-locked, made on first need: short files are laid end to end here first
+    // the WAV bytes of an encode job (4 608 per frame where an MP3 job has 96 and more): made when the slot's first encode job
+    // comes, from the slot's FRAME capacity -- a pipe that never sees one pays nothing for them
+    uint8_t *d_wav = nullptr; size_t wav_cap = 0;
+    uint8_t *h_wav = nullptr; size_t h_wav_cap = 0;      // page-locked, made and grown on need: short WAV files are laid end to end here first
     uint8_t *d_mp3 = nullptr; size_t mp3_cap = 0;
     int32_t *d_small = nullptr;
     // the encoder's intermediates of the slot's job (mdct, quantised lines, GrInfo, energies, scfsi): the slot's own, so
@@ -60,6 +64,10 @@ struct Job {
     std::vector<std::pair<const uint8_t *, size_t>> files, msgs;   // borrowed until the job is collected
     bool clear_all = false;
     bool decode = false;                 // MP3 -> WAV (int16) instead of hide / clear
+    // WAV -> MP3 (mp3s_pipe_submit_encode): files = the WAV images, msgs = per file {hide bits, their count}, enc_kbps per file
+    bool encode = false, enc_hide = false;
+    std::vector<int32_t> enc_kbps;
+    size_t o_runs = 0; int run_frames = 0;   // the gather's records inside the packed inputs, the longest stream's frames
     enum State { QUEUED, ISSUED, SLOW_DONE } state = QUEUED;
     // fast path
     bool walked = false;                 // side info and main data are taken apart on the device (k_dec_parse)
@@ -147,6 +155,7 @@ struct mp3s_pipe {
     hipStream_t s_up = nullptr, s_down = nullptr;
     hipStream_t s_dec = nullptr;         // the decode transforms of job k+1 under the encode transforms and the rate loop of job k (null: on the compute stream)
     hipEvent_t e_enc[2] = {nullptr, nullptr}; bool enc_used[2] = {false, false};   // the encode transforms that read PCM buffer x last are done
+    bool pcm_plain[2] = {false, false};  // ... or they went out without that event (a hide job on a pipe without s_dec: the compute stream's order was enough for it)
     hipStream_t s_comp = nullptr, s_ctx = nullptr;   // a compute stream of the pipe's own (pick_lanes), and the context's while the pipe has put its own in its place
     // The Huffman kernel is a latency chain that leaves the vector units mostly idle; the rate loop is bound by them.  The
     // front end of job k+1 therefore runs on a stream of its own, under the encode half of job k, with two sets of
@@ -187,6 +196,8 @@ bool prepare_chunk_encode(mp3s_pipe *P, Job &j, Slot &s);
 int issue_front(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23, bool inputs_later);
 int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down = false);
 int issue_down(mp3s_pipe *P, Job &j, Slot &s);
+bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s);
+int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down);
 void sync_all(mp3s_pipe *P);
 void bind_to(const std::vector<int> &cpus);
 bool finish_fast(mp3s_pipe *P, Job *j, Slot &s, bool *resolved);

@@ -552,6 +552,7 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
     if (rc) return rc;
     if (trace_on()) fprintf(stderr, "mp3s:   encode side queued %.3f ms after the job's start\n", now_ms() - t_issue0);
     if (P->s_dec) P->enc_used[set] = true;
+    P->pcm_plain[set] = !P->s_dec;           // (an encode job that writes this buffer next has no event of these transforms to wait for)
     HIPCHK(hipEventRecord(s.e_comp, P->s_tail ? P->s_tail : c->stream));
     P->last_tail = (int)(&s - P->slots.data());
     j.down_pending = true;
@@ -602,6 +603,152 @@ int issue_down(mp3s_pipe *P, Job &j, Slot &s)
     return MP3S_OK;
 }
 
+// ---- an encode job (mp3s_pipe_submit_encode): the headers of the WAV files, the image of their bytes, the gather's records and
+//      the encoder's inputs, packed [small results, zeroed | encoder inputs | gather records] behind o_in; false = not for this
+//      path (a file that fails its checks, a second (rate, bitrate) group, a job larger than the slot): mp3s_encode_files takes it
+bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
+{
+    const int nf = (int)j.files.size();
+    if (nf > kMaxFastFiles) return false;
+    j.walked = true; j.ck.on = false;      // (walked: the job brings its small results block, status words zeroed, with its inputs)
+    j.segs.assign((size_t)nf, EncSeg());
+    j.bits.clear(); j.guess.clear(); j.dec.clear(); j.res_bits.clear(); j.ups.clear(); j.stream_first.assign((size_t)nf, 0);
+    j.n_fix = 0; j.image_base = 0; j.md_base = 0;
+    // The slot's WAV image: as many frames as the slot's other buffers are made for (side_cap), 4 608 bytes each, + a header
+    // and the alignment of every file: 48 x max_job_bytes on the device (4 608 bytes per frame where the slot counts 96), e.g.
+    // 402 MB per slot of a pipe made for 8 MB jobs.  The page-locked staging for short files is sized by what they need (below).
+    if (!s.d_wav) {
+        const size_t cap = s.side_cap * 4608 + (size_t)kMaxFastFiles * 160 + 4096;
+        if (hipMalloc((void **)&s.d_wav, cap) != hipSuccess) { (void)hipGetLastError(); s.d_wav = nullptr; return false; }
+        s.wav_cap = cap;
+    }
+    WavRun *runs = reinterpret_cast<WavRun *>(s.h_stage + s.o_in + s.in_cap);    // (moved down behind the encoder's inputs below)
+    if ((size_t)nf * sizeof(WavRun) > s.pack_cap - s.in_cap) return false;
+    long n = 0;
+    int64_t longest = 0;
+    size_t img = 0, run_lo = 0, run_hi = 0;
+    std::vector<Upload> lay;             // every file's place in the image
+    lay.reserve((size_t)nf);
+    for (int i = 0; i < nf; i++) {
+        const uint8_t *file = j.files[i].first;
+        const uint8_t *hide = j.enc_hide ? j.msgs[i].first : nullptr;
+        const int n_hide = j.enc_hide ? (int)j.msgs[i].second : 0;
+        mp3s_wav_info w;
+        int64_t count = 0;
+        if (wav_encode_check(file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w, &count)) return false;
+        if (i == 0) { j.rate = w.samplerate; j.kbps = j.enc_kbps[0]; }
+        else if (w.samplerate != j.rate || j.enc_kbps[(size_t)i] != j.kbps) return false;   // more than one device batch
+        if ((size_t)(n + count) > s.side_cap) return false;
+        const size_t need = (size_t)w.data_offset + (size_t)count * 4608;        // (inside the file: wav_frame_count)
+        img = (img + 15) & ~(size_t)15;
+        if (img + need + kWavSlack > s.wav_cap) return false;
+        runs[i].src = (uint64_t)img + (uint64_t)w.data_offset; runs[i].first_frame = (uint32_t)n; runs[i].n_frames = (uint32_t)count;
+        j.stream_first[(size_t)i] = (uint32_t)n;
+        j.segs[(size_t)i].n_frames = (int)count; j.segs[(size_t)i].hide = hide; j.segs[(size_t)i].n_hide = n_hide;
+        lay.push_back({img, file, need});
+        img += need;
+        n += (long)count; longest = std::max(longest, count);
+    }
+    // the files' bytes, as they are: long files go up from where they lie, short ones (below kDirectUpload) are laid end to end in
+    // page-locked staging first and travel in runs.  The staging is as large as the short files of the jobs seen so far asked for
+    // (+ a quarter), not as large as the image: the slot has no job in flight when it grows.
+    size_t staged = 0;
+    for (const Upload &u : lay) if (u.bytes < kDirectUpload) staged = u.dst + u.bytes;
+    if (staged > s.h_wav_cap) {
+        if (s.h_wav) (void)hipHostFree(s.h_wav);
+        s.h_wav = nullptr; s.h_wav_cap = 0;
+        const size_t cap = std::min(s.wav_cap, std::max<size_t>(staged + staged / 4, (size_t)1 << 20));
+        if (hipHostMalloc((void **)&s.h_wav, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s.h_wav = nullptr; return false; }
+        s.h_wav_cap = cap;
+    }
+    for (const Upload &u : lay) {
+        if (u.bytes >= kDirectUpload) {
+            if (run_hi > run_lo) { j.ups.push_back({run_lo, s.h_wav + run_lo, run_hi - run_lo}); run_lo = run_hi = 0; }
+            j.ups.push_back(u);
+        } else {
+            if (run_hi == run_lo) run_lo = u.dst;
+            std::memcpy(s.h_wav + u.dst, u.src, u.bytes);
+            run_hi = u.dst + u.bytes;
+        }
+    }
+    if (run_hi > run_lo) j.ups.push_back({run_lo, s.h_wav + run_lo, run_hi - run_lo});
+    j.n_total = (int)n; j.run_frames = (int)longest;
+    j.L = EncLayout();
+    j.o_small = s.o_in;
+    const size_t small_room = (small_bytes(nf) + 15) & ~(size_t)15;
+    std::memset(s.h_stage + j.o_small, 0, kSmallHead);
+    j.o_encblk = j.o_small + small_room;
+    // (no stream to ask for table counts: the cursors are guessed at three per unit as mp3s_encode_pcm does, the selection on the
+    //  device covers what the message can reach)
+    if (small_room >= s.in_cap || !encode_inputs(j, s, s.h_stage + j.o_encblk, s.in_cap - small_room, P->c->opt[MP3S_OPT_SELECT] != 0)) return false;
+    j.res.reset(new mp3s_buf());
+    if (!j.res->big[0].reserve(j.L.mp3_bytes) || !j.res->big[2].reserve(small_bytes(j.L.n_segs))) return false;
+    j.res->mp3 = j.res->big[0].data();
+    j.o_runs = (j.o_encblk + j.L.bytes + 15) & ~(size_t)15;
+    std::memmove(s.h_stage + j.o_runs, runs, (size_t)nf * sizeof(WavRun));
+    j.pack_end = j.o_runs + (size_t)nf * sizeof(WavRun);
+    return j.pack_end <= s.o_in + s.pack_cap;
+}
+
+// ... and everything it does on the device, queued on the streams: images and inputs on the copy-up stream, the gather on the
+// front-end stream (where the parse and Huffman kernels of a hide job run: under the rate loop of the job in front), the encode
+// side on the compute stream with the tail where the pipe has put it, the copy down
+int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
+{
+    mp3s_ctx *c = P->c;
+    const EncLayout &L = j.L;
+    const int n = j.n_total;
+    const int set = j.set = (int)(P->issued++ & 1u);
+    void *d_keep = c->grab(set ? 26 : 7, (size_t)n * 2304 * 2);
+    if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+    HIPCHK(hipEventRecord(s.e_start, P->s_up));
+    for (const Upload &u : j.ups) HIPCHK(hipMemcpyAsync(s.d_wav + u.dst, u.src, u.bytes, hipMemcpyHostToDevice, P->s_up));
+    HIPCHK(hipMemcpyAsync(s.d_stage + j.o_small, s.h_stage + j.o_small, j.pack_end - j.o_small, hipMemcpyHostToDevice, P->s_up));
+    HIPCHK(hipEventRecord(s.e_up, P->s_up));
+    HIPCHK(hipStreamWaitEvent(P->s_huff, s.e_up, 0));
+    // PCM buffer `set` is written here.  It may still be read by the download of the decode job that used it last ...
+    if (P->keep_slot[set] >= 0) HIPCHK(hipStreamWaitEvent(P->s_huff, P->slots[(size_t)P->keep_slot[set]].e_down, 0));
+    P->keep_slot[set] = -1;
+    // ... or by the encode transforms of the job before last: behind e_enc[set] where they recorded it; a hide job on a pipe
+    // without a decode stream did not (the compute stream's own order was all it needed) -- then behind everything the compute
+    // stream has been given so far
+    if (P->pcm_plain[set]) {
+        HIPCHK(hipEventRecord(s.e_in, c->stream));
+        HIPCHK(hipStreamWaitEvent(P->s_huff, s.e_in, 0));
+    } else if (P->enc_used[set]) HIPCHK(hipStreamWaitEvent(P->s_huff, P->e_enc[set], 0));
+    if (launch_wav_gather(P->s_huff, s.d_wav, (const WavRun *)(s.d_stage + j.o_runs), (int)j.files.size(), j.run_frames, (int16_t *)d_keep))
+        return fail(MP3S_E_HIP, "gathering the WAV samples failed");
+    HIPCHK(hipEventRecord(s.e_huff, P->s_huff));
+    HIPCHK(hipStreamWaitEvent(c->stream, s.e_huff, 0));
+    const int units = L.units;
+    const size_t b_mdct = (size_t)L.n_all * 2304 * 4, b_ix = (size_t)L.n * 2304 * 2, b_out = (size_t)units * sizeof(mp3s_gr_out),
+                 b_en = ((size_t)units * 22 * 4 + 255) & ~(size_t)255, b_sc = (size_t)L.n * 8 * 4;
+    const size_t need = b_mdct + b_ix + b_out + b_en + b_sc;
+    if (need > s.enc_cap) {   // (hipFree waits for the device; only while the slot is growing to its job size)
+        if (s.d_enc) (void)hipFree(s.d_enc);
+        s.d_enc = nullptr; s.enc_cap = 0;
+        if (hipMalloc((void **)&s.d_enc, need + need / 8) != hipSuccess) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+        s.enc_cap = need + need / 8;
+    }
+    void *d_agg = c->grab(15, chain_agg_bytes(L.n));
+    if (!d_agg) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+    EncDev &dev = j.dev;
+    dev = EncDev();
+    dev.d_pcm = (const int16_t *)d_keep; dev.d_in = s.d_stage + j.o_encblk; dev.d_mdct_all = (int32_t *)s.d_enc; dev.d_ix = (int16_t *)(s.d_enc + b_mdct);
+    dev.d_out = (mp3s_gr_out *)(s.d_enc + b_mdct + b_ix); dev.d_en = (int32_t *)(s.d_enc + b_mdct + b_ix + b_out); dev.d_agg = d_agg;
+    dev.d_mp3 = s.d_mp3; dev.d_sc = (int32_t *)(s.d_enc + b_mdct + b_ix + b_out + b_en);
+    dev.d_small = (int32_t *)(s.d_stage + j.o_small); dev.direct_status = true;
+    j.down_split = 0;
+    if (!enc_variant_buffers(c, L, dev)) return fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
+    const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, nullptr, P->e_enc[set]);
+    if (rc) return rc;
+    P->enc_used[set] = true; P->pcm_plain[set] = false;
+    HIPCHK(hipEventRecord(s.e_comp, P->s_tail ? P->s_tail : c->stream));
+    P->last_tail = (int)(&s - P->slots.data());
+    j.down_pending = true;
+    return defer_down ? MP3S_OK : issue_down(P, j, s);
+}
+
 namespace {
 
 // A pipe of depth 1 or 2 has no job queued far enough ahead to hide this: the copy of a job's results waits for the job's last
@@ -612,8 +759,8 @@ namespace {
 int issue_fast(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23)
 {
     const bool defer = P->depth <= 2 && !P->internal;
-    int rc = issue_front(P, j, s, blob_len, max_p23, false);
-    if (!rc) rc = issue_back(P, j, s, false, defer);
+    int rc = j.encode ? issue_encode(P, j, s, defer) : issue_front(P, j, s, blob_len, max_p23, false);
+    if (!rc && !j.encode) rc = issue_back(P, j, s, false, defer);
     if (P->pending_down && P->pending_down != &j) {           // the job in front: its results may come down now
         Job *q = P->pending_down;
         P->pending_down = nullptr;
@@ -672,7 +819,13 @@ void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held
     // (the context's own pipe is not entered from here: this pipe owns the context)
     const int64_t keep = P->c->opt[MP3S_OPT_FILE_PIPELINE];
     P->c->opt[MP3S_OPT_FILE_PIPELINE] = 0;
-    if (j.block) {
+    if (j.encode) {
+        std::vector<int32_t> nh(nf);
+        for (int i = 0; i < nf; i++) { mp[i] = j.msgs[i].first; nh[i] = (int32_t)j.msgs[i].second; }
+        j.slow_rc = mp3s_encode_files(P->c, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
+                                      &j.slow_owner, j.slow_out.data(), j.slow_st.data());
+        j.slow_err = mp3s_last_error();
+    } else if (j.block) {
         j.slow_rc = mp3s_reencode_block(P->c, fp[0], fl[0], mp[0], ml[0], j.rank, j.world, j.has_carry ? &j.carry : nullptr, &j.blk_owner, &j.blk);
         j.slow_err = mp3s_last_error();
     } else if (j.decode) {
@@ -726,7 +879,8 @@ void worker(mp3s_pipe *P, int me)
         size_t blob_len = 0;
         int max_p23 = 0;
         bool fast;
-        if (j->block) {
+        if (j->encode) fast = prepare_encode(P, *j, s);
+        else if (j->block) {
             fast = P->c->opt[MP3S_OPT_DEVICE_PARSE] && prepare_block(P, *j, s);
             max_p23 = j->max_p23;
         } else {
@@ -735,7 +889,7 @@ void worker(mp3s_pipe *P, int me)
             else fast = prepare_fast(P, *j, s, scratch, &blob_len, &max_p23);
         }
         const double t1 = now_ms(), c1 = thread_cpu_ms();
-        if (trace_on()) fprintf(stderr, "mp3s: pipe job %lld slot %d on cpu %d: %s + layout %.3f ms (cpu %.3f)%s\n", (long long)j->ticket, j->slot, sched_getcpu(), j->walked ? "walk" : "scan", t1 - t0, c1 - c0, fast ? "" : " -> synchronous path");
+        if (trace_on()) fprintf(stderr, "mp3s: pipe job %lld slot %d on cpu %d: %s + layout %.3f ms (cpu %.3f)%s\n", (long long)j->ticket, j->slot, sched_getcpu(), j->encode ? "headers" : j->walked ? "walk" : "scan", t1 - t0, c1 - c0, fast ? "" : " -> synchronous path");
         Job::State st;
         bool cancelled = false;
         {
@@ -778,6 +932,8 @@ void free_slot(Slot &s)
     if (s.h_image) (void)hipHostFree(s.h_image);
     if (s.d_stage) (void)hipFree(s.d_stage);
     if (s.d_image) (void)hipFree(s.d_image);
+    if (s.d_wav) (void)hipFree(s.d_wav);
+    if (s.h_wav) (void)hipHostFree(s.h_wav);
     if (s.d_mp3) (void)hipFree(s.d_mp3);
     if (s.d_small) (void)hipFree(s.d_small);
     if (s.d_enc) (void)hipFree(s.d_enc);
@@ -996,6 +1152,22 @@ int mp3s_pipe_submit_decode(mp3s_pipe *P, const uint8_t *const *mp3s, const size
     j->decode = true; j->clear_all = true;
     j->files.resize((size_t)n_files); j->msgs.assign((size_t)n_files, {nullptr, 0});
     for (int i = 0; i < n_files; i++) j->files[i] = {mp3s[i], lens[i]};
+    return submit_job(P, std::move(j), ticket);
+}
+
+int mp3s_pipe_submit_encode(mp3s_pipe *P, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                            const uint8_t *const *hide_bits, const int32_t *n_hide, int64_t *ticket)
+{
+    if (!P || P->internal || !wavs || !lens || !bitrate_kbps || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");
+    std::unique_ptr<Job> j(new Job());
+    j->encode = true; j->clear_all = true; j->enc_hide = hide_bits != nullptr;
+    j->files.resize((size_t)n_files); j->msgs.assign((size_t)n_files, {nullptr, 0});
+    j->enc_kbps.assign(bitrate_kbps, bitrate_kbps + n_files);
+    for (int i = 0; i < n_files; i++) {
+        j->files[i] = {wavs[i], lens[i]};
+        // (a negative count is the file's own MP3S_E_ARG at collect time, as mp3s_encode_files gives it)
+        if (hide_bits) j->msgs[i] = {hide_bits[i], (size_t)(int64_t)n_hide[i]};
+    }
     return submit_job(P, std::move(j), ticket);
 }
 

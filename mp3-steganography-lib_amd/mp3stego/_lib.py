@@ -178,7 +178,7 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_hide_message", "mp3s_clear_file", "mp3s_hide_message_fd", "mp3s_clear_file_fd", "mp3s_decode_file_fd", "mp3s_hide_messages", "mp3s_reencode_block", "mp3s_reveal_message",
            "mp3s_pipe_create", "mp3s_pipe_destroy", "mp3s_pipe_submit", "mp3s_pipe_submit_decode", "mp3s_pipe_collect", "mp3s_pipe_get_stats",
            "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
-           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci"]
+           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci"]
 
 _lib = None
 _lock = threading.Lock()
@@ -285,6 +285,9 @@ def lib():
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
         L.mp3s_pipe_submit.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(C.c_int64)]
+        L.mp3s_encode_files.argtypes = [vp, vp, vp, i32, vp, vp, vp, pvp, vp, vp]
+        L.mp3s_debug_wav_gather.argtypes = [vp, vp, vp, i32, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.mp3s_pipe_submit_encode.argtypes = [vp, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_int64)]
         L.mp3s_pipe_submit_decode.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_int64)]
         L.mp3s_pipe_collect.argtypes = [vp, C.POINTER(C.c_int64), pvp, vp, vp, i32, C.POINTER(C.c_int32)]
         L.mp3s_pipe_get_stats.argtypes = [vp, C.POINTER(PipeStats)]
@@ -786,6 +789,62 @@ class Context:
         finally:
             lib().mp3s_buf_free(owner)
 
+    def encode_files(self, wavs, bitrate=320, hide_bits=None, messages=None):
+        """encode_file over a list of WAV files as one device batch per (sampling rate, bitrate).  bitrate: one int, or one per
+        file; hide_bits: one 0/1 array (or None) per file; messages: one str (or None) per file, framed with message_frame -- a
+        convenience over hide_bits.  Returns one entry per file: the dict encode_file returns, or the Mp3sError that file alone
+        would raise."""
+        if len(wavs) == 0:
+            return []
+        n, files, lens, kbps, hptr, hlen, keep = _encode_args(wavs, bitrate, hide_bits, messages)
+        out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
+        check(lib().mp3s_encode_files(self.handle, files, lens, n, kbps, hptr, hlen, C.byref(owner), out, status))
+        own = _Owner(owner)
+        res = []
+        for i in range(n):
+            f = out[i]
+            if status[i]:
+                res.append(Mp3sError(status[i], f"file {i}"))
+            else:
+                res.append({"data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+                            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
+                            "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)})
+        del keep
+        return res
+
+    def debug_wav_gather(self, wavs):
+        """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
+        n, files, lens, _, _, _, keep = _encode_args(wavs, 128, None, None)
+        cap = sum(len(w) for w in wavs) // 4608 + n
+        pcm, got = np.zeros((cap, 1152, 2), dtype=np.int16), C.c_int64()
+        check(lib().mp3s_debug_wav_gather(self.handle, files, lens, n, pcm.ctypes.data, cap, C.byref(got)))
+        del keep
+        return pcm[:got.value]
+
+
+def _encode_args(wavs, bitrate, hide_bits, messages):
+    """the argument arrays of mp3s_encode_files / mp3s_pipe_submit_encode (+ everything that has to stay alive beside them)"""
+    n = len(wavs)
+    rates = [int(bitrate)] * n if np.isscalar(bitrate) else [int(b) for b in bitrate]
+    if len(rates) != n:
+        raise ValueError("one bitrate per file")
+    if hide_bits is not None and messages is not None:
+        raise ValueError("hide_bits or messages, not both")
+    if messages is not None:
+        hide_bits = [None if m is None else np.array(message_frame(m), dtype=np.uint8) for m in messages]
+    if hide_bits is not None and len(hide_bits) != n:
+        raise ValueError("one bit string (or None) per file")
+    bufs = [np.frombuffer(w, dtype=np.uint8) for w in wavs]
+    files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    kbps = (C.c_int32 * n)(*rates)
+    hbs = hptr = hlen = None
+    if hide_bits is not None:
+        hbs = [None if h is None or not len(h) else np.ascontiguousarray(h, dtype=np.uint8) for h in hide_bits]
+        hptr = (C.c_void_p * n)(*[None if h is None else h.ctypes.data for h in hbs])
+        hlen = (C.c_int32 * n)(*[0 if h is None else len(h) for h in hbs])
+    return n, files, lens, kbps, hptr, hlen, (wavs, bufs, hbs)
+
 
 class Pipe:
     """Asynchronous host-fed pipeline (include/mp3s.h section vii): `depth` jobs in flight, host scan || upload || kernels ||
@@ -841,6 +900,19 @@ class Pipe:
             return None
         check(rc)
         self._keep[t.value] = (mp3s, bufs, files, lens)
+        return t.value
+
+    def submit_encode(self, wavs, bitrate=320, hide_bits=None, messages=None):
+        """an encode job (WAV -> MP3 per file; the arguments of Context.encode_files) -> ticket, or None when every slot is taken"""
+        if len(wavs) > self._cap:
+            raise ValueError(f"{len(wavs)} files in one job, the pipe was made for {self._cap} (max_files)")
+        n, files, lens, kbps, hptr, hlen, keep = _encode_args(wavs, bitrate, hide_bits, messages)
+        t = C.c_int64()
+        rc = lib().mp3s_pipe_submit_encode(self.handle, files, lens, n, kbps, hptr, hlen, C.byref(t))
+        if rc == E_BUSY:
+            return None
+        check(rc)
+        self._keep[t.value] = (keep, files, lens, hptr)
         return t.value
 
     def submit_block(self, mp3, message, rank, world, carry_in=None):
