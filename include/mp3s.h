@@ -170,7 +170,12 @@ int mp3s_ctx_wait_last(mp3s_ctx *ctx, mp3s_ctx *other);
                                     * completion signal, bit 1: the rate loop the event the tail stream waits for; 0 (default): event records behind them.
                                     * Measured (round 5, docs/LOG.md): 3 gives the pipe +1.5 % (18.0 -> 18.3 M frames/s) and now and then puts a context's
                                     * one-file calls into a slower order of its streams (1.1 -> 1.4 ms per 10 000 frames): off [MP3S_PIPE_SIGNALS=0..3] */
-#define MP3S_OPT_COUNT 20
+#define MP3S_OPT_WAV_IMPORT 20     /* 1: mp3s_encode_file, mp3s_encode_files and mp3s_pipe_submit_encode (a pipe keeps the value its context had when the pipe
+                                    * was created) read their WAV files by the import rules of mp3s_wav_import_info -- RIFF chunk walk over the whole file,
+                                    * mono and stereo, 8/16/24/32-bit PCM, float32, WAVE_FORMAT_EXTENSIBLE, any length; the samples become the encoder's
+                                    * int16 stereo frames on the device (k_wav_import); 0 (default): the reference's reader, refusals and over-reads
+                                    * (mp3s_wav_parse) [MP3S_WAV_IMPORT=1 -> 1] */
+#define MP3S_OPT_COUNT 21
 /* what became of the one-file calls of this context (mp3s_hide_message, mp3s_clear_file, mp3s_decode_file, mp3s_decode_stream,
  * mp3s_hide_message_chunked): files that went through the overlapped stages as chunks, their chunks, chunks that were run
  * again because they depended on a carry the guess got wrong, chunks whose chains the host resolved, and files that took
@@ -650,6 +655,43 @@ typedef struct {
     int64_t n_values;       /* int16 values the reference's np.fromfile call yields (up to 2x the declared count) */
 } mp3s_wav_info;
 int mp3s_wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_info *out);
+/* The opt-in reader (MP3S_OPT_WAV_IMPORT): what a WAV file is to the encode calls when the option is on.  No device, no context.
+ *  - RIFF chunk walk from byte 12 over the whole file: id, little-endian size, payload, pad byte after an odd size (a zero byte; where
+ *    a writer left it out -- the byte there is not zero -- the next chunk starts at once: the files the strict reader takes with an odd
+ *    chunk and no pad byte stay readable, and the samples may lie at an ODD offset).  The first "fmt "
+ *    and the first "data" count and "fmt " must come first; a chunk header cut by the end of the file ends the walk.  No RIFF/WAVE,
+ *    no "fmt ", no "data": MP3S_E_EXIT "Bad WAVE file.".
+ *  - "fmt " of 16, 18 or 40 bytes.  Tag 1 (PCM) with 8, 16, 24 or 32 bits, tag 3 (IEEE float) with 32 bits; tag 0xFFFE (extensible,
+ *    40 bytes) takes the tag from the first two bytes of the sub-format GUID and the sample width from the container (wBitsPerSample)
+ *    whatever wValidBitsPerSample says: valid bits are left-justified in the container.  block_align is computed (channels x bytes), the
+ *    field in the file is not trusted.  Anything else: MP3S_E_EXIT with the reference's "compression used instead of PCM" / "samples
+ *    not int8, int16 or int32 type" text (64-bit float: the latter).
+ *  - 1 or 2 channels; 0 is MP3S_E_MALFORMED, more than 2 MP3S_E_UNSUPPORTED.  32 000 / 44 100 / 48 000 Hz and the bitrate table as
+ *    for mp3s_wav_parse, same texts (no resampling).
+ *  - data bytes = min(declared size, bytes left in the file); a declared size of 0 or 0xFFFFFFFF means "to the end of the file".
+ *    n_samples = data bytes / block_align (a cut last sample is dropped); none: MP3S_E_UNSUPPORTED "no samples".  Bytes behind the
+ *    samples are never audio.
+ *  - samples to int16 (little-endian input, no dither, no rounding for the integer formats): 8-bit unsigned (u - 128) << 8; 16-bit as
+ *    is; 24-bit s >> 8 and 32-bit s >> 16 (arithmetic: the upper two bytes); float32 clamp(rint(x * 32768.0f), -32768, 32767),
+ *    round-half-even, all in float32, NaN gives 0.
+ *  - mono: the sample goes to BOTH channels.  The encoder is stereo-only, so a mono file becomes a stereo MP3 at the requested
+ *    bitrate and mp3s_file.channels is 2.
+ *  - the last frame is filled with zeros from sample n_samples on.
+ * A 16-bit stereo file of whole frames that mp3s_wav_parse accepts gives the same bytes and fields with the option on as with it off. */
+#define MP3S_WAV_U8 1
+#define MP3S_WAV_S16 2
+#define MP3S_WAV_S24 3
+#define MP3S_WAV_S32 4
+#define MP3S_WAV_F32 5
+typedef struct {
+    int32_t format;          /* MP3S_WAV_U8, _S16, _S24, _S32, _F32 */
+    int32_t channels;        /* 1 or 2 */
+    int32_t samplerate, bits_per_sample, block_align, bitrate;
+    int64_t data_offset;     /* first sample byte, any alignment */
+    int64_t n_samples;       /* per channel: data bytes present in the file / block_align */
+    int64_t n_frames;        /* ceil(n_samples / 1152) */
+} mp3s_wav_import;
+int mp3s_wav_import_info(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out);
 /* replaces: scipy.io.wavfile.write header as used by MP3_Parser.write_to_wav -- reference decoder/MP3_Parser.py:86-93 */
 int mp3s_wav_header(int64_t n_rows, int nch, int rate, uint8_t out44[44]);
 /* replaces: str_to_binary_str(str(len(m)) + "#" + m) -- reference steganography.py:10-24, 42-50.  bits are 0/1 bytes. */
@@ -710,10 +752,15 @@ int mp3s_hide_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *
  * out[i] is byte for byte and field for field what mp3s_encode_file gives for file i alone.  status[i] = MP3S_OK or the code file
  * i alone would have failed with (MP3S_E_EXIT with the reference's text for a rate or bitrate it refuses, MP3S_E_UNSUPPORTED for
  * mono and for a file that ends inside its last frame, MP3S_E_ARG), its out[i] zeroed; with status == NULL the first such code
- * fails the whole call -- the same rule as mp3s_hide_messages. */
+ * fails the whole call -- the same rule as mp3s_hide_messages.
+ * With MP3S_OPT_WAV_IMPORT the files are read by the rules of mp3s_wav_import_info instead (its codes and texts per file): mono or
+ * stereo, 8/16/24/32-bit PCM or float32, any chunk layout, any length.  16-bit stereo files of whole frames still go through
+ * k_wav_gather; everything else of a batch is converted to the int16 stereo frames of the same PCM buffer by ONE k_wav_import launch
+ * (mono to both channels, the last frame zero-filled; the result is a stereo MP3, channels = 2).  Behind the PCM buffer nothing differs. */
 int mp3s_encode_files(mp3s_ctx *ctx, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
                       const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status);
-/* test aid: the first device step of mp3s_encode_files alone -- the images of these WAV files (stereo, any supported rate) go up and
+/* test aid: the first device step of mp3s_encode_files alone -- the images of these WAV files (stereo, any supported rate; with
+ * MP3S_OPT_WAV_IMPORT whatever mp3s_wav_import_info accepts, through k_wav_import) go up and
  * k_wav_gather lays their frames back to back; pcm = room for cap_frames frames of [1152][2] int16, *n_frames = the frames of all files
  * (np.fromfile + the frame slicing of reference encoder/WAV_Reader.py:108, MP3_Encoder.py:596-618, the over-read frame of E3 included) */
 int mp3s_debug_wav_gather(mp3s_ctx *ctx, const uint8_t *const *wavs, const size_t *lens, int n_files, int16_t *pcm, int64_t cap_frames,

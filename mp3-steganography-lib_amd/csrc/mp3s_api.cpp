@@ -133,6 +133,7 @@ int mp3s_ctx_create(int device, mp3s_ctx **out)
         c->opt[MP3S_OPT_PIPE_DEC] = env("MP3S_PIPE_DEC", 0) != 0;
         c->opt[MP3S_OPT_RATE_SIGNALS] = env("MP3S_RATE_SIGNALS", 0) != 0;
         c->opt[MP3S_OPT_PIPE_SIGNALS] = env("MP3S_PIPE_SIGNALS", 0) & 3;
+        c->opt[MP3S_OPT_WAV_IMPORT] = env("MP3S_WAV_IMPORT", 0) != 0;
     }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
@@ -755,6 +756,14 @@ int mp3s_wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_i
     if ((!file && len) || !out) return fail(MP3S_E_ARG, "null pointer");
     const char *msg = "";
     const int rc = wav_parse(file, len, bitrate_kbps, out, &msg);
+    return rc ? fail(rc, "%s", msg) : MP3S_OK;
+}
+
+int mp3s_wav_import_info(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out)
+{
+    if (!file || !len || !out) return fail(MP3S_E_ARG, "null pointer");
+    const char *msg = "";
+    const int rc = wav_import_parse(file, len, bitrate_kbps, out, &msg);
     return rc ? fail(rc, "%s", msg) : MP3S_OK;
 }
 

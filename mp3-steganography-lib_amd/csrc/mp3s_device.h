@@ -112,7 +112,11 @@ int launch_parse(hipStream_t stream, const uint8_t *d_image, uint32_t image_base
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes
-constexpr size_t kWavSlack = 32;
+// ... and of k_wav_import: a stream of any sample format (MP3S_WAV_*) and one or two channels; n_samples per channel are taken, the rest
+// of its n_frames frames is zero
+struct WavImportRun { uint64_t src, n_samples; uint32_t first_frame, n_frames, format, channels; };   // 32 bytes
+constexpr size_t kWavSlack = 64;   // k_wav_gather reads up to 31 bytes behind the last sample taken, k_wav_import up to 40 (k_wav.hpp)
+int launch_wav_import(hipStream_t stream, const uint8_t *d_image, const WavImportRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 
 constexpr size_t kPlaceEntry = 4912;   // [int32 frame, pad to 16 | int16 is[2304] | mp3s_granule_si si[4]]

@@ -445,6 +445,16 @@ int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *
     return (int)hipGetLastError();
 }
 
+// the same grid for the streams k_wav_import converts (ONE launch for a batch of up to 32 768 of them)
+int launch_wav_import(hipStream_t stream, const uint8_t *d_image, const WavImportRun *d_runs, int n_runs, int max_frames, int16_t *d_pcm)
+{
+    if (n_runs <= 0 || max_frames <= 0) return 0;
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)max_frames * 288 + 255) / 256, 2048);
+    for (int r0 = 0; r0 < n_runs; r0 += 32768)
+        hipLaunchKernelGGL(k_wav_import, dim3(gx, (unsigned)std::min(n_runs - r0, 32768)), dim3(256), 0, stream, d_image, d_runs, r0, d_pcm);
+    return (int)hipGetLastError();
+}
+
 int launch_pack(hipStream_t stream, const int16_t *d_ix, const mp3s_gr_out *d_gr, const int32_t *d_en, int n_frames, int sri,
                 int bri, int whole_slots, const uint32_t *d_frame_off, const uint8_t *d_padding, uint8_t *d_mp3,
                 int32_t *d_scfsi, int32_t *d_status, int32_t *d_sync, Profiler *prof, int f_begin, int f_end)

@@ -1,6 +1,6 @@
 // C-ABI of the library (include/mp3s.h), part 3b: a list of WAV files in, MP3 files out -- the files of one (sampling rate,
-// bitrate) as ONE device batch.  The WAV bytes go to the device as the caller holds them; k_wav_gather (k_wav.hpp) makes
-// the PCM buffer of the batch out of them there, and encode_batch takes it from HBM as it takes the PCM a decode left.
+// bitrate) as ONE device batch.  The WAV bytes go to the device as the caller holds them; k_wav_gather (k_wav.hpp) -- and k_wav_import
+// for the files only MP3S_OPT_WAV_IMPORT lets in -- make the PCM buffer of the batch out of them there, and encode_batch takes it from HBM as it takes the PCM a decode left.
 #include "pipe_internal.h"
 
 // what mp3s_encode_file checks of a file before the device sees it, in its order: the header (wav_parse: MP3S_E_EXIT with the
@@ -17,40 +17,71 @@ int wav_encode_check(const uint8_t *wav, size_t len, int bitrate_kbps, const uin
     return MP3S_OK;
 }
 
+// the same for either reader.  With `import` (MP3S_OPT_WAV_IMPORT) the header is wav_import_parse's, with its codes and texts; a
+// 16-bit stereo file of whole frames is what the strict reader makes of it (the compatibility rule), so it keeps k_wav_gather
+int wav_encode_plan(bool import, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p)
+{
+    *p = WavPlan();
+    if (!import) {
+        mp3s_wav_info w;
+        const int rc = wav_encode_check(wav, len, bitrate_kbps, hide_bits, n_hide, &w, &p->count);
+        if (rc) return rc;
+        p->samplerate = w.samplerate; p->format = MP3S_WAV_S16; p->channels = 2; p->data_offset = w.data_offset; p->n_samples = p->count * 1152;
+        p->need = (size_t)w.data_offset + (size_t)p->count * 4608;   // (inside the file: wav_frame_count)
+        return MP3S_OK;
+    }
+    if (!wav) return fail(MP3S_E_ARG, "null pointer");
+    const char *msg = "";
+    mp3s_wav_import w;
+    const int rc = wav_import_parse(wav, len, bitrate_kbps, &w, &msg);
+    if (rc) return fail(rc, "%s", msg);
+    if (n_hide < 0 || (n_hide > 0 && !hide_bits)) return fail(MP3S_E_ARG, "bad hide arguments");
+    if (w.n_frames > 0x7fffffff / 8) return fail(MP3S_E_ARG, "too many frames");
+    p->samplerate = w.samplerate; p->format = w.format; p->channels = w.channels; p->data_offset = w.data_offset;
+    p->count = w.n_frames; p->n_samples = w.n_samples;
+    p->need = (size_t)w.data_offset + (size_t)w.n_samples * (size_t)w.block_align;   // (inside the file: the samples present)
+    p->gather = w.format == MP3S_WAV_S16 && w.channels == 2 && w.n_samples % 1152 == 0;
+    return MP3S_OK;
+}
+
 namespace {
 
 struct WavIn {
     const uint8_t *wav; size_t len;
     const uint8_t *hide; int n_hide;
-    mp3s_wav_info w; int64_t count;
+    WavPlan p;
 };
 
-// the files `idx` to the device: their images up, the gather queued on the context's stream -> *d_pcm_out = [n_all][1152][2] int16 in
+// the files `idx` to the device: their images up, the gather (and, for what it does not take, the import kernel) queued on the context's stream -> *d_pcm_out = [n_all][1152][2] int16 in
 // the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is waited for; `runs` and the
 // callers' bytes are read by copies in flight until the stream is synchronised.
 int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, std::vector<WavRun> &runs,
-                  void **d_pcm_out, int64_t *n_all_out)
+                  std::vector<WavImportRun> &iruns, void **d_pcm_out, int64_t *n_all_out)
 {
     segs.assign(idx.size(), EncSeg());
-    runs.assign(idx.size(), WavRun());
+    runs.clear(); iruns.clear();
+    runs.reserve(idx.size());
     std::vector<size_t> at(idx.size());
-    int64_t n_all = 0, max_frames = 0;
+    int64_t n_all = 0, max_frames = 0, max_iframes = 0;
     size_t img = 0, staged = 0;
     for (size_t k = 0; k < idx.size(); k++) {
         const WavIn &f = in[(size_t)idx[k]];
-        segs[k].n_frames = (int)f.count; segs[k].hide = f.hide; segs[k].n_hide = f.n_hide;
+        segs[k].n_frames = (int)f.p.count; segs[k].hide = f.hide; segs[k].n_hide = f.n_hide;
         img = (img + 15) & ~(size_t)15;
         at[k] = img;
-        runs[k].src = (uint64_t)img + (uint64_t)f.w.data_offset; runs[k].first_frame = (uint32_t)n_all; runs[k].n_frames = (uint32_t)f.count;
-        const size_t need = (size_t)f.w.data_offset + (size_t)f.count * 4608;   // (inside the file: wav_frame_count)
+        wav_plan_record(f.p, img, (uint32_t)n_all, runs, iruns);
+        const size_t need = f.p.need;
         if (need < kDirectUpload) staged = img + need;
         img += need;
-        n_all += f.count; max_frames = std::max(max_frames, f.count);
+        n_all += f.p.count;
+        if (f.p.gather) max_frames = std::max(max_frames, f.p.count);
+        else max_iframes = std::max(max_iframes, f.p.count);
         if (n_all > 0x7fffffff / 8) return fail(MP3S_E_ARG, "encode batch too large");
     }
     HIPCHK(hipSetDevice(c->device));
     const size_t runs_at = (img + kWavSlack + 15) & ~(size_t)15;
-    uint8_t *d_image = (uint8_t *)c->grab(27, runs_at + runs.size() * sizeof(WavRun));
+    const size_t iruns_at = runs_at + ((runs.size() * sizeof(WavRun) + 15) & ~(size_t)15);
+    uint8_t *d_image = (uint8_t *)c->grab(27, iruns_at + iruns.size() * sizeof(WavImportRun));
     void *d_pcm = c->grab(7, (size_t)n_all * 4608);
     if (!d_image || !d_pcm) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of WAV input", (long long)n_all);
     // long files go up from where they lie; short ones are laid end to end first, bytes as they are, and travel in runs
@@ -65,7 +96,7 @@ int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<i
     };
     for (size_t k = 0; k < idx.size(); k++) {
         const WavIn &f = in[(size_t)idx[k]];
-        const size_t need = (size_t)f.w.data_offset + (size_t)f.count * 4608;
+        const size_t need = f.p.need;
         if (need >= kDirectUpload) {
             const int rc = flush();
             if (rc) return rc;
@@ -80,8 +111,11 @@ int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<i
     }
     int rc = flush();
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(d_image + runs_at, runs.data(), runs.size() * sizeof(WavRun), hipMemcpyHostToDevice, c->stream));
-    if (launch_wav_gather(c->stream, d_image, (const WavRun *)(d_image + runs_at), (int)runs.size(), (int)max_frames, (int16_t *)d_pcm))
+    if (!runs.empty()) HIPCHK(hipMemcpyAsync(d_image + runs_at, runs.data(), runs.size() * sizeof(WavRun), hipMemcpyHostToDevice, c->stream));
+    if (!iruns.empty()) HIPCHK(hipMemcpyAsync(d_image + iruns_at, iruns.data(), iruns.size() * sizeof(WavImportRun), hipMemcpyHostToDevice, c->stream));
+    if (trace_on()) fprintf(stderr, "mp3s:   encode_files: %zu streams through k_wav_gather, %zu through k_wav_import\n", runs.size(), iruns.size());
+    if (launch_wav_gather(c->stream, d_image, (const WavRun *)(d_image + runs_at), (int)runs.size(), (int)max_frames, (int16_t *)d_pcm) ||
+        launch_wav_import(c->stream, d_image, (const WavImportRun *)(d_image + iruns_at), (int)iruns.size(), (int)max_iframes, (int16_t *)d_pcm))
         return fail(MP3S_E_HIP, "gathering the WAV samples failed");
     *d_pcm_out = d_pcm; *n_all_out = n_all;
     return MP3S_OK;
@@ -93,14 +127,15 @@ int encode_group(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<in
 {
     std::vector<EncSeg> segs;
     std::vector<WavRun> runs;
+    std::vector<WavImportRun> iruns;
     void *d_pcm = nullptr;
     int64_t n_all = 0;
-    int rc = wav_to_device(c, in, idx, segs, runs, &d_pcm, &n_all);
+    int rc = wav_to_device(c, in, idx, segs, runs, iruns, &d_pcm, &n_all);
     if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
     std::unique_ptr<mp3s_buf> part(new mp3s_buf());
     int passes = 0;
     rc = encode_batch(c, nullptr, (const int16_t *)d_pcm, segs, samplerate, kbps, part.get(), &passes, false);
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }     // (`runs` is the source of a copy that may still be in flight)
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }     // (the records are the source of copies that may still be in flight)
     for (size_t k = 0; k < idx.size(); k++) {
         mp3s_file &o = out[idx[k]];
         std::memset(&o, 0, sizeof o);
@@ -115,10 +150,8 @@ int encode_group(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<in
 
 }  // namespace
 
-extern "C" {
-
-int mp3s_encode_files(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
-                      const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status)
+int encode_files_as(mp3s_ctx *c, bool import, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                    const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status)
 {
     if (!c || !wavs || !lens || !bitrate_kbps || !owner || !out || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");
     std::unique_ptr<mp3s_buf> top(new mp3s_buf());
@@ -132,11 +165,11 @@ int mp3s_encode_files(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *len
         std::memset(&out[i], 0, sizeof out[i]);
         f.wav = wavs[i]; f.len = lens[i];
         f.hide = hide_bits ? hide_bits[i] : nullptr; f.n_hide = hide_bits ? n_hide[i] : 0;
-        st[(size_t)i] = wav_encode_check(f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.w, &f.count);
+        st[(size_t)i] = wav_encode_plan(import, f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.p);
         if (st[(size_t)i]) { why[(size_t)i] = mp3s_last_error(); continue; }
         size_t g = 0;
-        while (g < groups.size() && (groups[g].rate != f.w.samplerate || groups[g].kbps != bitrate_kbps[i])) g++;
-        if (g == groups.size()) groups.push_back({f.w.samplerate, bitrate_kbps[i], {}});
+        while (g < groups.size() && (groups[g].rate != f.p.samplerate || groups[g].kbps != bitrate_kbps[i])) g++;
+        if (g == groups.size()) groups.push_back({f.p.samplerate, bitrate_kbps[i], {}});
         groups[g].idx.push_back(i);
     }
     for (const Group &g : groups) {
@@ -160,6 +193,15 @@ int mp3s_encode_files(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *len
     return MP3S_OK;
 }
 
+extern "C" {
+
+int mp3s_encode_files(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                      const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status)
+{
+    if (!c || !wavs || !lens || !bitrate_kbps || !owner || !out || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");   // (before the context is looked at)
+    return encode_files_as(c, c->opt[MP3S_OPT_WAV_IMPORT] != 0, wavs, lens, n_files, bitrate_kbps, hide_bits, n_hide, owner, out, status);
+}
+
 int mp3s_debug_wav_gather(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, int16_t *pcm, int64_t cap_frames, int64_t *n_frames)
 {
     if (!c || !wavs || !lens || !pcm || !n_frames || n_files <= 0) return fail(MP3S_E_ARG, "bad argument");
@@ -169,17 +211,18 @@ int mp3s_debug_wav_gather(mp3s_ctx *c, const uint8_t *const *wavs, const size_t 
     for (int i = 0; i < n_files; i++) {
         WavIn &f = in[(size_t)i];
         f.wav = wavs[i]; f.len = lens[i]; f.hide = nullptr; f.n_hide = 0;
-        const int rc = wav_encode_check(f.wav, f.len, 128, nullptr, 0, &f.w, &f.count);
+        const int rc = wav_encode_plan(c->opt[MP3S_OPT_WAV_IMPORT] != 0, f.wav, f.len, 128, nullptr, 0, &f.p);
         if (rc) return rc;
-        idx[(size_t)i] = i; total += f.count;
+        idx[(size_t)i] = i; total += f.p.count;
     }
     *n_frames = total;
     if (total > cap_frames) return fail(MP3S_E_ARG, "%lld frames, room for %lld", (long long)total, (long long)cap_frames);
     std::vector<EncSeg> segs;
     std::vector<WavRun> runs;
+    std::vector<WavImportRun> iruns;
     void *d_pcm = nullptr;
     int64_t n_all = 0;
-    int rc = wav_to_device(c, in, idx, segs, runs, &d_pcm, &n_all);
+    int rc = wav_to_device(c, in, idx, segs, runs, iruns, &d_pcm, &n_all);
     if (!rc) rc = mp3s_dev_download(c, pcm, d_pcm, (size_t)n_all * 4608);
     else (void)hipStreamSynchronize(c->stream);
     return rc;

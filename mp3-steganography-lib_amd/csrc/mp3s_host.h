@@ -159,6 +159,8 @@ int wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_info *
 // MP3S_E_UNSUPPORTED with *msg where the reference ends in IndexError (mono; a file that ends inside its last frame).  The ONE
 // statement of the rule: mp3s_encode_file, mp3s_encode_files and the pipe's encode jobs all ask here.
 int wav_frame_count(const mp3s_wav_info &w, int64_t *count, const char **msg);
+// the opt-in reader of MP3S_OPT_WAV_IMPORT (rules: mp3s_wav_import_info in include/mp3s.h): MP3S_OK, or a code with *msg
+int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out, const char **msg);
 // the 44-byte header scipy.io.wavfile.write emits for int16 data
 void wav_header(int64_t n_rows, int nch, int rate, uint8_t *out44);
 // reference steganography.py:10-24, 42-50

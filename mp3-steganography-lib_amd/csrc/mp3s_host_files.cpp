@@ -140,6 +140,75 @@ int wav_frame_count(const mp3s_wav_info &w, int64_t *count_out, const char **msg
     return MP3S_OK;
 }
 
+// The opt-in reader (MP3S_OPT_WAV_IMPORT; the rules are stated at mp3s_wav_import_info in include/mp3s.h): a RIFF chunk walk over the
+// whole file instead of a tag search in its first 128 bytes, and every sample format a WAV file usually has.  The reference's texts
+// are kept for what both readers refuse.
+int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *o, const char **msg)
+{
+    memset(o, 0, sizeof *o);
+    *msg = "Bad WAVE file.";
+    if (len < 12 || memcmp(file, "RIFF", 4) || memcmp(file + 8, "WAVE", 4)) return MP3S_E_EXIT;
+    uint64_t fmt_at = 0, fmt_size = 0, data_at = 0, data_size = 0;
+    bool have_fmt = false, have_data = false;
+    for (uint64_t pos = 12; pos + 8 <= len;) {   // (a chunk header cut by the end of the file ends the walk)
+        uint32_t size = 0;
+        le(file, len, (long)pos + 4, 4, &size);
+        if (!memcmp(file + pos, "data", 4)) {
+            if (!have_fmt) return MP3S_E_EXIT;
+            have_data = true; data_at = pos + 8; data_size = size;
+            break;
+        }
+        if (!have_fmt && !memcmp(file + pos, "fmt ", 4)) { have_fmt = true; fmt_at = pos + 8; fmt_size = size; }
+        pos += 8 + (uint64_t)size;
+        // the pad byte of an odd chunk is zero; a writer that left it out (the reference's reader never asked for it: it searches the
+        // tags) has the next chunk's id there, and that is taken as it stands
+        if ((size & 1u) && pos < len && file[pos] == 0) pos++;
+    }
+    if (!have_fmt || !have_data) return MP3S_E_EXIT;
+    *msg = "Unsupported WAVE file, compression used instead of PCM.";
+    if (fmt_size != 16 && fmt_size != 18 && fmt_size != 40) return MP3S_E_EXIT;
+    *msg = "short WAVE header";
+    if (fmt_at + fmt_size > len) return MP3S_E_MALFORMED;
+    uint32_t tag = 0, ch = 0, rate = 0, bits = 0;
+    le(file, len, (long)fmt_at, 2, &tag); le(file, len, (long)fmt_at + 2, 2, &ch);
+    le(file, len, (long)fmt_at + 4, 4, &rate); le(file, len, (long)fmt_at + 14, 2, &bits);
+    *msg = "Unsupported WAVE file, compression used instead of PCM.";
+    if (tag == 0xfffe) {   // WAVE_FORMAT_EXTENSIBLE: the tag is the start of the sub-format GUID, the width is the container's
+        if (fmt_size != 40) return MP3S_E_EXIT;
+        le(file, len, (long)fmt_at + 24, 2, &tag);
+        if (tag == 0xfffe) return MP3S_E_EXIT;
+    }
+    if (tag != 1 && tag != 3) return MP3S_E_EXIT;
+    o->channels = (int32_t)ch; o->samplerate = (int32_t)rate; o->bits_per_sample = (int32_t)bits; o->bitrate = bitrate_kbps;
+    *msg = "WAVE header with zero channels (ZeroDivisionError in the reference)";
+    if (ch == 0) return MP3S_E_MALFORMED;
+    *msg = "more than two channels";
+    if (ch > 2) return MP3S_E_UNSUPPORTED;
+    *msg = "Unsupported sampling frequency.";
+    if (rate != 32000 && rate != 44100 && rate != 48000) return MP3S_E_EXIT;
+    *msg = "Unsupported WAVE file, samples not int8, int16 or int32 type.";
+    if (tag == 3) {
+        if (bits != 32) return MP3S_E_EXIT;
+        o->format = MP3S_WAV_F32;
+    } else {
+        if (bits != 8 && bits != 16 && bits != 24 && bits != 32) return MP3S_E_EXIT;
+        o->format = bits == 8 ? MP3S_WAV_U8 : bits == 16 ? MP3S_WAV_S16 : bits == 24 ? MP3S_WAV_S24 : MP3S_WAV_S32;
+    }
+    o->block_align = (int32_t)(ch * (bits / 8));   // (computed: the field in the file is not trusted)
+    int sri, bri, whole;
+    *msg = "Unsupported bitrate configuration.";
+    if (stream_params(o->samplerate, bitrate_kbps, &sri, &bri, &whole)) return MP3S_E_EXIT;
+    const uint64_t left = len - data_at;
+    const uint64_t bytes = data_size == 0 || data_size == 0xffffffffu || data_size > left ? left : data_size;   // (0 / all ones: to the end of the file)
+    o->data_offset = (int64_t)data_at;
+    o->n_samples = (int64_t)(bytes / (uint64_t)o->block_align);   // (a cut last sample is dropped)
+    o->n_frames = (o->n_samples + 1151) / 1152;
+    *msg = "no samples";
+    if (o->n_samples == 0) return MP3S_E_UNSUPPORTED;
+    *msg = "";
+    return MP3S_OK;
+}
+
 // the 44 bytes scipy.io.wavfile.write puts in front of int16 data (reference MP3_Parser.py:86-93 -> scipy)
 void wav_header(int64_t n_rows, int nch, int rate, uint8_t *h)
 {

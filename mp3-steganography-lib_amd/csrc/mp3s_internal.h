@@ -355,6 +355,24 @@ void tables_guess_of(const mp3s_frame_side *side, long n_frames, int extra, std:
 // what mp3s_encode_file checks of a file before the device sees it, in its order (header, frame count, message arguments);
 // MP3S_OK with *w and *count (frames), or the code and text the one-file call fails with
 int wav_encode_check(const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, mp3s_wav_info *w, int64_t *count);
+// ... and what the device is told about the file: by the reference's reader (import false: wav_encode_check; always for k_wav_gather)
+// or by the rules of MP3S_OPT_WAV_IMPORT (wav_import_parse; k_wav_gather for 16-bit stereo of whole frames, k_wav_import otherwise)
+struct WavPlan {
+    int samplerate = 0, format = 0, channels = 0;
+    int64_t data_offset = 0, count = 0 /* frames */, n_samples = 0 /* per channel */;
+    size_t need = 0;      // bytes of the file that go into the image: everything up to the last sample taken
+    bool gather = true;   // the frames are contiguous int16 stereo in the file
+};
+int wav_encode_plan(bool import, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p);
+// the records of the two kernels for stream `k` of a batch whose image holds the file at `img`
+inline void wav_plan_record(const WavPlan &p, size_t img, uint32_t first_frame, std::vector<WavRun> &runs, std::vector<WavImportRun> &iruns)
+{
+    if (p.gather) runs.push_back({(uint64_t)img + (uint64_t)p.data_offset, first_frame, (uint32_t)p.count});
+    else iruns.push_back({(uint64_t)img + (uint64_t)p.data_offset, (uint64_t)p.n_samples, first_frame, (uint32_t)p.count, (uint32_t)p.format, (uint32_t)p.channels});
+}
+// mp3s_encode_files with the reader named by the caller (a pipe keeps the option's value of the day it was created)
+int encode_files_as(mp3s_ctx *c, bool import, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                    const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status);
 
 // ---------------------------------------------------------------- one file as chunks through the overlapped stages (run_file.cpp)
 constexpr int kRunFallback = 1;          // run_file: not for this path -- the caller takes the synchronous one (same bytes)

@@ -68,6 +68,8 @@ struct Job {
     bool encode = false, enc_hide = false;
     std::vector<int32_t> enc_kbps;
     size_t o_runs = 0; int run_frames = 0;   // the gather's records inside the packed inputs, the longest stream's frames
+    size_t o_iruns = 0; int irun_frames = 0; // ... and k_wav_import's (a pipe created under MP3S_OPT_WAV_IMPORT)
+    std::vector<WavRun> wav_runs; std::vector<WavImportRun> wav_iruns;
     enum State { QUEUED, ISSUED, SLOW_DONE } state = QUEUED;
     // fast path
     bool walked = false;                 // side info and main data are taken apart on the device (k_dec_parse)
@@ -149,6 +151,7 @@ struct mp3s_pipe {
     hipStream_t s_img = nullptr;         // the file pieces' own copy stream (the packed inputs of a chunk must not queue behind them)
     FileUp up;
     bool internal = false;               // the context's own (run_file): no worker threads, jobs issued by the caller
+    bool wav_import = false;             // MP3S_OPT_WAV_IMPORT of the context when the pipe was created: how its encode jobs read their WAV files
     size_t max_job_bytes = 0;
     size_t max_frames = 0;               // frames a job can have at most (the context's own pipe cuts its chunks by frames); 0: from the bytes, 96 per frame
     std::vector<Slot> slots;

@@ -622,10 +622,13 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
         if (hipMalloc((void **)&s.d_wav, cap) != hipSuccess) { (void)hipGetLastError(); s.d_wav = nullptr; return false; }
         s.wav_cap = cap;
     }
-    WavRun *runs = reinterpret_cast<WavRun *>(s.h_stage + s.o_in + s.in_cap);    // (moved down behind the encoder's inputs below)
-    if ((size_t)nf * sizeof(WavRun) > s.pack_cap - s.in_cap) return false;
+    // the records of the two kernels (k_wav_import's only under MP3S_OPT_WAV_IMPORT): put behind the encoder's inputs below
+    std::vector<WavRun> &runs = j.wav_runs;
+    std::vector<WavImportRun> &iruns = j.wav_iruns;
+    runs.clear(); iruns.clear();
+    if ((size_t)nf * (P->wav_import ? sizeof(WavImportRun) : sizeof(WavRun)) > s.pack_cap - s.in_cap) return false;
     long n = 0;
-    int64_t longest = 0;
+    int64_t longest = 0, ilongest = 0;
     size_t img = 0, run_lo = 0, run_hi = 0;
     std::vector<Upload> lay;             // every file's place in the image
     lay.reserve((size_t)nf);
@@ -633,21 +636,23 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
         const uint8_t *file = j.files[i].first;
         const uint8_t *hide = j.enc_hide ? j.msgs[i].first : nullptr;
         const int n_hide = j.enc_hide ? (int)j.msgs[i].second : 0;
-        mp3s_wav_info w;
-        int64_t count = 0;
-        if (wav_encode_check(file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w, &count)) return false;
+        WavPlan w;
+        if (wav_encode_plan(P->wav_import, file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w)) return false;
+        const int64_t count = w.count;
         if (i == 0) { j.rate = w.samplerate; j.kbps = j.enc_kbps[0]; }
         else if (w.samplerate != j.rate || j.enc_kbps[(size_t)i] != j.kbps) return false;   // more than one device batch
         if ((size_t)(n + count) > s.side_cap) return false;
-        const size_t need = (size_t)w.data_offset + (size_t)count * 4608;        // (inside the file: wav_frame_count)
+        const size_t need = w.need;              // (inside the file; mono and 8-bit files need less of the image per frame than 4 608 bytes, 24/32-bit stereo more)
         img = (img + 15) & ~(size_t)15;
         if (img + need + kWavSlack > s.wav_cap) return false;
-        runs[i].src = (uint64_t)img + (uint64_t)w.data_offset; runs[i].first_frame = (uint32_t)n; runs[i].n_frames = (uint32_t)count;
+        wav_plan_record(w, img, (uint32_t)n, runs, iruns);
         j.stream_first[(size_t)i] = (uint32_t)n;
         j.segs[(size_t)i].n_frames = (int)count; j.segs[(size_t)i].hide = hide; j.segs[(size_t)i].n_hide = n_hide;
         lay.push_back({img, file, need});
         img += need;
-        n += (long)count; longest = std::max(longest, count);
+        n += (long)count;
+        if (w.gather) longest = std::max(longest, count);
+        else ilongest = std::max(ilongest, count);
     }
     // the files' bytes, as they are: long files go up from where they lie, short ones (below kDirectUpload) are laid end to end in
     // page-locked staging first and travel in runs.  The staging is as large as the short files of the jobs seen so far asked for
@@ -672,7 +677,7 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
         }
     }
     if (run_hi > run_lo) j.ups.push_back({run_lo, s.h_wav + run_lo, run_hi - run_lo});
-    j.n_total = (int)n; j.run_frames = (int)longest;
+    j.n_total = (int)n; j.run_frames = (int)longest; j.irun_frames = (int)ilongest;
     j.L = EncLayout();
     j.o_small = s.o_in;
     const size_t small_room = (small_bytes(nf) + 15) & ~(size_t)15;
@@ -685,8 +690,11 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
     if (!j.res->big[0].reserve(j.L.mp3_bytes) || !j.res->big[2].reserve(small_bytes(j.L.n_segs))) return false;
     j.res->mp3 = j.res->big[0].data();
     j.o_runs = (j.o_encblk + j.L.bytes + 15) & ~(size_t)15;
-    std::memmove(s.h_stage + j.o_runs, runs, (size_t)nf * sizeof(WavRun));
-    j.pack_end = j.o_runs + (size_t)nf * sizeof(WavRun);
+    j.o_iruns = j.o_runs + ((runs.size() * sizeof(WavRun) + 15) & ~(size_t)15);
+    j.pack_end = j.o_iruns + iruns.size() * sizeof(WavImportRun);
+    if (j.pack_end > s.o_in + s.pack_cap) return false;
+    if (!runs.empty()) std::memcpy(s.h_stage + j.o_runs, runs.data(), runs.size() * sizeof(WavRun));
+    if (!iruns.empty()) std::memcpy(s.h_stage + j.o_iruns, iruns.data(), iruns.size() * sizeof(WavImportRun));
     return j.pack_end <= s.o_in + s.pack_cap;
 }
 
@@ -716,7 +724,8 @@ int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
         HIPCHK(hipEventRecord(s.e_in, c->stream));
         HIPCHK(hipStreamWaitEvent(P->s_huff, s.e_in, 0));
     } else if (P->enc_used[set]) HIPCHK(hipStreamWaitEvent(P->s_huff, P->e_enc[set], 0));
-    if (launch_wav_gather(P->s_huff, s.d_wav, (const WavRun *)(s.d_stage + j.o_runs), (int)j.files.size(), j.run_frames, (int16_t *)d_keep))
+    if (launch_wav_gather(P->s_huff, s.d_wav, (const WavRun *)(s.d_stage + j.o_runs), (int)j.wav_runs.size(), j.run_frames, (int16_t *)d_keep) ||
+        launch_wav_import(P->s_huff, s.d_wav, (const WavImportRun *)(s.d_stage + j.o_iruns), (int)j.wav_iruns.size(), j.irun_frames, (int16_t *)d_keep))
         return fail(MP3S_E_HIP, "gathering the WAV samples failed");
     HIPCHK(hipEventRecord(s.e_huff, P->s_huff));
     HIPCHK(hipStreamWaitEvent(c->stream, s.e_huff, 0));
@@ -822,7 +831,7 @@ void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held
     if (j.encode) {
         std::vector<int32_t> nh(nf);
         for (int i = 0; i < nf; i++) { mp[i] = j.msgs[i].first; nh[i] = (int32_t)j.msgs[i].second; }
-        j.slow_rc = mp3s_encode_files(P->c, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
+        j.slow_rc = encode_files_as(P->c, P->wav_import, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
                                       &j.slow_owner, j.slow_out.data(), j.slow_st.data());
         j.slow_err = mp3s_last_error();
     } else if (j.block) {
@@ -995,6 +1004,7 @@ int pipe_create(mp3s_ctx *c, int depth, size_t max_job_bytes, int scan_threads, 
     HIPCHK(hipSetDevice(c->device));
     std::unique_ptr<mp3s_pipe> P(new mp3s_pipe());
     P->c = c; P->depth = depth; P->internal = internal; P->max_job_bytes = max_job_bytes;
+    P->wav_import = c->opt[MP3S_OPT_WAV_IMPORT] != 0;
     auto destroy = [&](int code, const char *what) {
         for (auto &s : P->slots) free_slot(s);                // (the streams belong to the device: pick_lanes)
         for (hipEvent_t e : P->e_dec) if (e) (void)hipEventDestroy(e);

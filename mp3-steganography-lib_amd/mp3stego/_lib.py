@@ -121,6 +121,14 @@ class WavInfo(C.Structure):
                 ("num_of_samples", C.c_int64), ("data_offset", C.c_int64), ("n_values", C.c_int64)]
 
 
+class WavImport(C.Structure):
+    _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("samplerate", C.c_int32), ("bits_per_sample", C.c_int32),
+                ("block_align", C.c_int32), ("bitrate", C.c_int32), ("data_offset", C.c_int64), ("n_samples", C.c_int64), ("n_frames", C.c_int64)]
+
+
+WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32 = 1, 2, 3, 4, 5
+
+
 class File(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("kbps", C.c_int32), ("sampling_rate", C.c_int32),
                 ("channels", C.c_int32), ("n_frames", C.c_int32), ("too_long", C.c_int32), ("n_bits", C.c_int32),
@@ -178,7 +186,7 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_hide_message", "mp3s_clear_file", "mp3s_hide_message_fd", "mp3s_clear_file_fd", "mp3s_decode_file_fd", "mp3s_hide_messages", "mp3s_reencode_block", "mp3s_reveal_message",
            "mp3s_pipe_create", "mp3s_pipe_destroy", "mp3s_pipe_submit", "mp3s_pipe_submit_decode", "mp3s_pipe_collect", "mp3s_pipe_get_stats",
            "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
-           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci"]
+           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info"]
 
 _lib = None
 _lock = threading.Lock()
@@ -255,6 +263,7 @@ def lib():
         L.mp3s_encode_pcm.argtypes = [vp, vp, i64, i32, i32, i32, vp, i32, pvp, C.POINTER(Encoded)]
         psz = C.POINTER(sz)
         L.mp3s_wav_parse.argtypes = [vp, sz, i32, C.POINTER(WavInfo)]
+        L.mp3s_wav_import_info.argtypes = [vp, sz, i32, C.POINTER(WavImport)]
         L.mp3s_wav_header.argtypes = [i64, i32, i32, vp]
         L.mp3s_message_frame.argtypes = [vp, sz, pvp, pvp, psz]
         L.mp3s_message_reveal.argtypes = [vp, sz, pvp, pvp, psz]
@@ -358,7 +367,7 @@ class Context:
             self.handle = None
 
     OPTIONS = {"select": 1, "redo": 2, "fast_imdct": 3, "pipe_tail": 4, "chunk_frames": 5, "device_parse": 6, "file_pipeline": 7,
-               "scan_threads": 8, "first_chunk_frames": 9, "file_up": 10, "huf_lanes": 11, "numa": 12, "float_fast": 13, "fail_chunk": 14, "fused_decode": 15, "fused_encode": 16, "pipe_dec": 17, "rate_signals": 18, "pipe_signals": 19}
+               "scan_threads": 8, "first_chunk_frames": 9, "file_up": 10, "huf_lanes": 11, "numa": 12, "float_fast": 13, "fail_chunk": 14, "fused_decode": 15, "fused_encode": 16, "pipe_dec": 17, "rate_signals": 18, "pipe_signals": 19, "wav_import": 20}
 
     def set_option(self, name, value):
         """options of the context (include/mp3s.h MP3S_OPT_*); returns the value the option had"""
@@ -815,7 +824,10 @@ class Context:
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
         n, files, lens, _, _, _, keep = _encode_args(wavs, 128, None, None)
-        cap = sum(len(w) for w in wavs) // 4608 + n
+        if self.get_option("wav_import"):            # a frame of mono 8-bit samples is 1 152 bytes of its file
+            cap = sum(wav_import_info(w, 128)["n_frames"] for w in wavs)
+        else:
+            cap = sum(len(w) for w in wavs) // 4608 + n
         pcm, got = np.zeros((cap, 1152, 2), dtype=np.int16), C.c_int64()
         check(lib().mp3s_debug_wav_gather(self.handle, files, lens, n, pcm.ctypes.data, cap, C.byref(got)))
         del keep
@@ -1045,6 +1057,25 @@ def wav_parse(data: bytes, bitrate=320):
     w = WavInfo()
     check(lib().mp3s_wav_parse(buf.ctypes.data if len(data) else None, len(data), int(bitrate), C.byref(w)))
     return {k: getattr(w, k) for k, _ in WavInfo._fields_}
+
+
+def wav_import_info(data: bytes, bitrate=320):
+    """WAV header by the rules of the "wav_import" option (include/mp3s.h mp3s_wav_import_info): chunk walk over the whole file, mono /
+    stereo, 8/16/24/32-bit PCM, float32, extensible.  -> dict(format, channels, samplerate, bits_per_sample, block_align, bitrate,
+    data_offset, n_samples, n_frames); raises Mp3sError (E_EXIT carries the reference's text where it has one).  No GPU."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    w = WavImport()
+    check(lib().mp3s_wav_import_info(buf.ctypes.data if len(data) else None, len(data), int(bitrate), C.byref(w)))
+    return {k: getattr(w, k) for k, _ in WavImport._fields_}
+
+
+def wav_import_default():
+    """the default of the "wav_import" option for a context created now (MP3S_WAV_IMPORT, as mp3s_ctx_create reads it)"""
+    v = os.environ.get("MP3S_WAV_IMPORT", "")
+    try:
+        return bool(v) and int(v) != 0
+    except ValueError:
+        return False
 
 
 def wav_header(n_rows, nch, rate):

@@ -11,6 +11,26 @@ from mp3stego import _lib
 from mp3stego.encoder.wav_reader import WavReader
 
 
+class _ImportedWav:
+    """what Encoder needs of a WavReader for a file that only the import rules read (mp3s_wav_import_info)"""
+
+    def __init__(self, file_path: str, bit_rate: int):
+        self.file_path = file_path
+        self.bitrate = bit_rate
+        with open(file_path, 'rb') as f:
+            self.data = f.read()
+        try:
+            w = _lib.wav_import_info(self.data, bit_rate)
+        except _lib.Mp3sError as e:
+            if e.code == _lib.E_EXIT:
+                sys.exit(e.text)
+            raise ValueError(str(e)) from None
+        self.num_of_channels = w["channels"]
+        self.samplerate = w["samplerate"]
+        self.bits_per_sample = w["bits_per_sample"]
+        self.num_of_samples = w["n_samples"]
+
+
 class Encoder:
     """
     Creates an mp3 file from a wav file.
@@ -26,7 +46,14 @@ class Encoder:
         self.__output_file_path = output_file_path
         if not os.path.exists(self.__file_path):
             sys.exit(f'File {self.__file_path} not found.')
-        self.__wav_file = WavReader(self.__file_path, bitrate)
+        try:
+            self.__wav_file = WavReader(self.__file_path, bitrate)
+        except (SystemExit, ValueError):
+            # MP3S_WAV_IMPORT=1 (the "wav_import" option's default): a header only the import rules accept is passed through to the
+            # native call; what both readers refuse keeps the reference's exit
+            if not _lib.wav_import_default():
+                raise
+            self.__wav_file = _ImportedWav(self.__file_path, bitrate)
         self.__hide_str = hide_str
         self.hide_str_offset = 0
 

@@ -8,6 +8,10 @@ repeat; (c) from the same set and from the four in rotation.  Host clock around 
 returns finished results), device events for the resident half; every shape is warmed up first; profiler off.
 
     python tools/encode_bench.py [--out profiles/r07_encode_batch.json] [--repeats 5] [--pipe-seconds 2] [--only long|short]
+
+--format u8|s16|s24|s32|f32 and --channels 1|2 write the same audio as WAV files of that sample format and channel count and turn the
+context's "wav_import" option on (k_wav_import converts them on the device); --wav-import 1 turns it on for the canonical 16-bit stereo
+files too (they keep k_wav_gather: the figure to hold against the option's off state).
 """
 import argparse
 import json
@@ -23,12 +27,19 @@ sys.path.insert(0, os.path.join(ROOT, "mp3-steganography-lib_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def wav_of(pcm, rate):
+def wav_of(pcm, rate, fmt="s16", channels=2):
+    """-> (the WAV file, the int16 stereo rows the encoder gets from it)"""
     from mp3stego import _lib
-    return _lib.wav_header(pcm.shape[0], 2, rate) + np.ascontiguousarray(pcm, dtype="<i2").tobytes()
+    if fmt == "s16" and channels == 2:
+        return _lib.wav_header(pcm.shape[0], 2, rate) + np.ascontiguousarray(pcm, dtype="<i2").tobytes(), pcm
+    import wav_import_files as W
+    f = {"u8": W.U8, "s16": W.S16, "s24": W.S24, "s32": W.S32, "f32": W.F32}[fmt]
+    p = (pcm if channels == 2 else pcm[:, 0]).astype(np.int64)
+    s = {"u8": (p >> 8) + 128, "s16": p, "s24": p << 8, "s32": p << 16, "f32": (p / 32768.0).astype(np.float32)}[fmt]
+    return W.wav_file(s, f, rate=rate), W.stereo_frames(s, f)
 
 
-def pipe_ms_per_job(_lib, ctx, sets, kbps, seconds, want):
+def pipe_ms_per_job(_lib, ctx, sets, kbps, seconds, want, frames):
     wavs, turn = sets[0], [0]
 
     def submit():
@@ -37,7 +48,6 @@ def pipe_ms_per_job(_lib, ctx, sets, kbps, seconds, want):
 
     # (slots for the job's MP3 bytes -- 418 per frame at 44.1 kHz / 128 kbit/s -- with a fifth to spare; their frame capacity, 1/96 of
     #  that, is what the slot's WAV image is made from)
-    frames = sum(len(w) for w in wavs) // 4608
     pipe = _lib.Pipe(ctx, depth=3, max_job_bytes=max(1 << 20, frames * 500), scan_threads=2, max_files=max(1024, len(wavs)))
     try:
         for _ in range(4):                                     # warm-up: every slot has seen the shape
@@ -123,17 +133,23 @@ def main():
     ap.add_argument("--pipe-seconds", type=float, default=2.0)
     ap.add_argument("--only", choices=["long", "short"], default=None)
     ap.add_argument("--no-pipe", action="store_true", help="(a) and (b) only: the kernel-trace run")
+    ap.add_argument("--format", choices=["u8", "s16", "s24", "s32", "f32"], default="s16")
+    ap.add_argument("--channels", type=int, choices=[1, 2], default=2)
+    ap.add_argument("--wav-import", type=int, choices=[0, 1], default=None, help="the context's wav_import option (default: on for what only it reads)")
     args = ap.parse_args()
     from mp3stego import _lib
     from synth_pcm import synth_pcm
     ctx = _lib.Context(0)
-    result = {"device": ctx.device_name(), "repeats": args.repeats, "clock": "host perf_counter around calls that return finished results", "workloads": {}}
+    canonical = args.format == "s16" and args.channels == 2
+    ctx.set_option("wav_import", (0 if canonical else 1) if args.wav_import is None else args.wav_import)
+    result = {"device": ctx.device_name(), "repeats": args.repeats, "format": args.format, "channels": args.channels, "wav_import": ctx.get_option("wav_import"), "clock": "host perf_counter around calls that return finished results", "workloads": {}}
     loads = {"long": ("one 10 000-frame file, 44.1 kHz, 128 kbit/s", [synth_pcm(10000, seed=1234)]),
              "short": ("250 files of 40 frames, 44.1 kHz, 128 kbit/s", [synth_pcm(40, seed=2000 + i) for i in range(250)])}
     for name, (what, pcms) in loads.items():
         if args.only and name != args.only:
             continue
-        wavs = [wav_of(p, 44100) for p in pcms]
+        made = [wav_of(p, 44100, args.format, args.channels) for p in pcms]
+        wavs, pcms = [m[0] for m in made], [m[1] for m in made]         # (pcms: what the encoder sees, for the resident floor)
         n_bytes = sum(len(w) for w in wavs)
         frames = sum(p.shape[0] // 1152 for p in pcms)
         one_by_one = lambda: [ctx.encode_file(w, 128) for w in wavs]
@@ -176,7 +192,7 @@ def main():
         r["floor_encode_half_resident_median_ms"] = statistics.median(half)
         if not args.no_pipe:
             for mode, sets in (("same", [wavs]), ("rotating", rot)):
-                ms, jobs, st = pipe_ms_per_job(_lib, ctx, sets, 128, args.pipe_seconds, want)
+                ms, jobs, st = pipe_ms_per_job(_lib, ctx, sets, 128, args.pipe_seconds, want, frames)
                 r["inputs"][mode].update({"c_pipe_ms_per_job": ms, "c_pipe_jobs_timed": jobs, "c_pipe_stats_with_warm_up": st})
             r["floor_ms"] = max(r["inputs"]["rotating"]["floor_upload_median_ms"], r["floor_encode_half_resident_median_ms"])
         result["workloads"][name] = r
