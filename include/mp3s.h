@@ -175,7 +175,13 @@ int mp3s_ctx_wait_last(mp3s_ctx *ctx, mp3s_ctx *other);
                                     * mono and stereo, 8/16/24/32-bit PCM, float32, WAVE_FORMAT_EXTENSIBLE, any length; the samples become the encoder's
                                     * int16 stereo frames on the device (k_wav_import); 0 (default): the reference's reader, refusals and over-reads
                                     * (mp3s_wav_parse) [MP3S_WAV_IMPORT=1 -> 1] */
-#define MP3S_OPT_COUNT 21
+#define MP3S_OPT_WAV_RESAMPLE 21   /* the encode calls of MP3S_OPT_WAV_IMPORT resample files of other sampling rates on the device (k_wav_resample, rules at
+                                    * mp3s_wav_resample_info).  0 (default): off, every call behaves as without the option.  1: a file whose rate is not
+                                    * 32 000 / 44 100 / 48 000 Hz is resampled to the target of the auto rule, files at a supported rate are untouched.
+                                    * 32000 / 44100 / 48000: every file not already at that rate is resampled to it.  Any other value: MP3S_E_ARG.  A
+                                    * non-zero value implies the reader of MP3S_OPT_WAV_IMPORT for the encode calls; a pipe keeps the value its context had
+                                    * when the pipe was created [MP3S_WAV_RESAMPLE=1|32000|44100|48000] */
+#define MP3S_OPT_COUNT 22
 /* what became of the one-file calls of this context (mp3s_hide_message, mp3s_clear_file, mp3s_decode_file, mp3s_decode_stream,
  * mp3s_hide_message_chunked): files that went through the overlapped stages as chunks, their chunks, chunks that were run
  * again because they depended on a carry the guess got wrong, chunks whose chains the host resolved, and files that took
@@ -249,8 +255,10 @@ int mp3s_synth_mode(mp3s_ctx *ctx, double eps_scale, int64_t *exact_samples);
 int mp3s_bench_copy(mp3s_ctx *ctx, size_t bytes, int iters, double *gb_per_s);
 /* per-kernel HIP-event timing on the same stream: enable, run, then collect the summed milliseconds and launch
  * counts of the kernels in this order: dec_imdct, dec_synth, enc_analysis, enc_mdct, rate_loop, dec_huffman,
- * enc_pack, chain (the pair of mp3s_chain_resolve_dev counts as one) (n >= MP3S_N_KERNELS) */
-#define MP3S_N_KERNELS 8
+ * enc_pack, chain (the pair of mp3s_chain_resolve_dev counts as one), wav_resample (mp3s_encode_files only).  n >= MP3S_N_KERNELS fills all of them; a caller with room for the first MP3S_N_KERNELS_MIN only
+ * (the list as it was before wav_resample joined it at its end) gets those, n below that is MP3S_E_ARG */
+#define MP3S_N_KERNELS 9
+#define MP3S_N_KERNELS_MIN 8
 int mp3s_profile_enable(mp3s_ctx *ctx, int on);
 /* An event pair costs a few microseconds of stream time per launch: restrict the timing to the kernels in `mask` (bit k =
  * kernel k in the order above; all by default).  Takes effect with the next mp3s_profile_enable(ctx, 1). */
@@ -667,7 +675,8 @@ int mp3s_wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_i
  *    field in the file is not trusted.  Anything else: MP3S_E_EXIT with the reference's "compression used instead of PCM" / "samples
  *    not int8, int16 or int32 type" text (64-bit float: the latter).
  *  - 1 or 2 channels; 0 is MP3S_E_MALFORMED, more than 2 MP3S_E_UNSUPPORTED.  32 000 / 44 100 / 48 000 Hz and the bitrate table as
- *    for mp3s_wav_parse, same texts (no resampling).
+ *    for mp3s_wav_parse, same texts; files of other rates are resampled to one of the three under MP3S_OPT_WAV_RESAMPLE only
+ *    (mp3s_wav_resample_info states the rules).
  *  - data bytes = min(declared size, bytes left in the file); a declared size of 0 or 0xFFFFFFFF means "to the end of the file".
  *    n_samples = data bytes / block_align (a cut last sample is dropped); none: MP3S_E_UNSUPPORTED "no samples".  Bytes behind the
  *    samples are never audio.
@@ -692,6 +701,37 @@ typedef struct {
     int64_t n_frames;        /* ceil(n_samples / 1152) */
 } mp3s_wav_import;
 int mp3s_wav_import_info(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out);
+/* The resampler of MP3S_OPT_WAV_RESAMPLE: what a WAV file of any sampling rate is to the encode calls.  No device, no context.  `mode` takes
+ * the option's non-zero values (1 / 32000 / 44100 / 48000; anything else MP3S_E_ARG).  Everything but the rate is judged by the rules
+ * of mp3s_wav_import_info, same codes and texts; the bitrate is checked against out_rate.  An extension beyond the reference.
+ *  - target rate.  Forced mode: `mode`.  Auto (1): a supported rate stays; otherwise the candidates are the supported rates >= the
+ *    file's rate (all three if it is above 48 000), the one with the smallest L wins, ties go to the highest rate:
+ *    8000 -> 32000, 11025 -> 44100, 16000 -> 32000, 22050 -> 44100, 24000 -> 48000, 37800 -> 44100, 88200 -> 44100, 96000 -> 48000.
+ *  - ratio.  g = gcd(in, out), L = out / g, M = in / g.  L > 1280, more than 256 taps or a rate of 0: MP3S_E_EXIT "Unsupported
+ *    sampling frequency.".  L = M = 1: the file is not resampled and takes the path of MP3S_OPT_WAV_IMPORT.
+ *  - filter.  rho = min(1, L / M), H = ceil(16 / rho), T = 2 H taps per phase.  Prototype h(t) = 0.95 rho sinc(0.95 rho t) w(t / H), t in
+ *    input samples, sinc(x) = sin(pi x) / (pi x), w the 4-term Blackman-Harris window 0.35875 + 0.48829 cos(pi u) + 0.14128 cos(2 pi u)
+ *    + 0.01168 cos(3 pi u) on (-1, 1], zero outside.
+ *  - positions.  Output sample n sits at x = n M / L: i0 = floor(n M / L), p = n M mod L.  Tap k (0 <= k < T) multiplies input sample
+ *    i0 - H + 1 + k; its t is k - H + 1 - p / L.
+ *  - coefficients.  c[p][k] = rint(h(t) 2^15) in double; the residual 32768 - sum_k c[p][k] is added to the phase's largest tap (the
+ *    first of equal ones), so DC gain is exactly 1.  sum_k |c[p][k]| of a phase exceeds 65535 (69 292 for L / M = 2 / 1), so ONE int32 sum
+ *    could overflow on full-scale input: the device adds the taps k < 2 floor(H / 2) and the taps behind them apart and joins the two
+ *    sums in 64 bits.  No table where sum |c| of either part exceeds 65535: 65535 x 32768 + 2^14 < 2^31, each part fits int32.
+ *  - output.  y[n] = clamp((sum_k c[p][k] x[i0 - H + 1 + k] + 2^14) >> 15, -32768, 32767), arithmetic shift, x = 0 outside [0, n_in),
+ *    n = 0 .. n_out - 1 with n_out = ceil(n_in L / M); the rest of the last frame is zero.  x is the int16 the import rules make of the
+ *    file's sample; a mono file is computed once and written to both channels.
+ * mp3s_file.sampling_rate of a result is out_rate, channels 2. */
+typedef struct {
+    mp3s_wav_import in;        /* as mp3s_wav_import_info, but samplerate = the file's own rate, n_samples / n_frames of the INPUT */
+    int32_t out_rate, L, M;    /* out_rate / in_rate = L / M in lowest terms; L = M = 1: not resampled */
+    int32_t taps, half;        /* T = 2 H taps per phase, H */
+    int64_t n_out, n_frames;   /* ceil(n_in * L / M); ceil(n_out / 1152) */
+} mp3s_wav_resample;
+int mp3s_wav_resample_info(const uint8_t *file, size_t len, int bitrate_kbps, int mode, mp3s_wav_resample *out);
+/* the integer tap table the device uses for the ratio L / M: taps[L][T], *T = taps per phase; cap = room in int32 values (MP3S_E_ARG with
+ * *T set when it is too small, or for a ratio the resampler refuses) */
+int mp3s_wav_resample_taps(int L, int M, int32_t *taps /* [L][T] */, int cap, int32_t *T);
 /* replaces: scipy.io.wavfile.write header as used by MP3_Parser.write_to_wav -- reference decoder/MP3_Parser.py:86-93 */
 int mp3s_wav_header(int64_t n_rows, int nch, int rate, uint8_t out44[44]);
 /* replaces: str_to_binary_str(str(len(m)) + "#" + m) -- reference steganography.py:10-24, 42-50.  bits are 0/1 bytes. */

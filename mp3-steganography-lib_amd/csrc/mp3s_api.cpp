@@ -134,6 +134,8 @@ int mp3s_ctx_create(int device, mp3s_ctx **out)
         c->opt[MP3S_OPT_RATE_SIGNALS] = env("MP3S_RATE_SIGNALS", 0) != 0;
         c->opt[MP3S_OPT_PIPE_SIGNALS] = env("MP3S_PIPE_SIGNALS", 0) & 3;
         c->opt[MP3S_OPT_WAV_IMPORT] = env("MP3S_WAV_IMPORT", 0) != 0;
+        const int64_t rs = env("MP3S_WAV_RESAMPLE", 0);
+        c->opt[MP3S_OPT_WAV_RESAMPLE] = rs == 1 || rs == 32000 || rs == 44100 || rs == 48000 ? rs : 0;
     }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
@@ -166,6 +168,7 @@ void mp3s_ctx_destroy(mp3s_ctx *c)
     if (c->scratch_enc) hipFree(c->scratch_enc);
     if (c->d_sync) hipFree(c->d_sync);
     for (void *q : c->pool) if (q) hipFree(q);
+    for (const mp3s_ctx::ResampleTaps &t : c->res_taps) hipFree(t.d);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->ev_order) hipEventDestroy(c->ev_order);
@@ -192,7 +195,9 @@ int mp3s_ctx_set_option(mp3s_ctx *c, int option, int64_t value)
     if (!c || option <= 0 || option >= MP3S_OPT_COUNT) return fail(MP3S_E_ARG, "unknown option %d", option);
     if (value < 0 || ((option == MP3S_OPT_CHUNK_FRAMES || option == MP3S_OPT_FIRST_CHUNK_FRAMES) && value != 0 && value < 4) || (option == MP3S_OPT_SCAN_THREADS && value > 64))
         return fail(MP3S_E_ARG, "option %d: value %lld out of range", option, (long long)value);
-    const bool number = option == MP3S_OPT_CHUNK_FRAMES || option == MP3S_OPT_SCAN_THREADS || option == MP3S_OPT_FIRST_CHUNK_FRAMES ||
+    if (option == MP3S_OPT_WAV_RESAMPLE && value != 0 && value != 1 && value != 32000 && value != 44100 && value != 48000)
+        return fail(MP3S_E_ARG, "option %d: %lld is not 0, 1, 32000, 44100 or 48000", option, (long long)value);
+    const bool number = option == MP3S_OPT_WAV_RESAMPLE || option == MP3S_OPT_CHUNK_FRAMES || option == MP3S_OPT_SCAN_THREADS || option == MP3S_OPT_FIRST_CHUNK_FRAMES ||
                         option == MP3S_OPT_HUF_LANES || option == MP3S_OPT_FAIL_CHUNK || option == MP3S_OPT_PIPE_SIGNALS;
     c->opt[option] = number ? value : (option == MP3S_OPT_PIPE_TAIL ? std::min<int64_t>(value, 2) : (value != 0));
     return MP3S_OK;
@@ -364,7 +369,8 @@ int mp3s_profile_select(mp3s_ctx *c, unsigned mask)
 
 int mp3s_profile_collect(mp3s_ctx *c, double *total_ms, int64_t *launches, int n)
 {
-    if (!c || !total_ms || !launches || n < K_COUNT) return fail(MP3S_E_ARG, "bad argument (need %d slots)", (int)K_COUNT);
+    // (a caller built when the list had eight kernels gets those eight: the list only grows at its end)
+    if (!c || !total_ms || !launches || n < MP3S_N_KERNELS_MIN) return fail(MP3S_E_ARG, "bad argument (need %d slots)", (int)MP3S_N_KERNELS_MIN);
     HIPCHK(hipStreamSynchronize(c->stream));
     Profiler &p = c->prof;
     for (int i = 0; i < p.n_pairs; i++) {
@@ -380,7 +386,7 @@ int mp3s_profile_collect(mp3s_ctx *c, double *total_ms, int64_t *launches, int n
         p.dropped = 0;
         return fail(MP3S_E_ARG, "%ld timed launches had no event pair left (collect at least every %d launches)", lost, Profiler::MAX_PAIRS);
     }
-    for (int k = 0; k < K_COUNT; k++) { total_ms[k] = p.total_ms[k]; launches[k] = p.count[k]; }
+    for (int k = 0; k < K_COUNT && k < n; k++) { total_ms[k] = p.total_ms[k]; launches[k] = p.count[k]; }
     static_assert(K_COUNT == MP3S_N_KERNELS, "kernel list out of sync with mp3s.h");
     return MP3S_OK;
 }
@@ -765,6 +771,29 @@ int mp3s_wav_import_info(const uint8_t *file, size_t len, int bitrate_kbps, mp3s
     const char *msg = "";
     const int rc = wav_import_parse(file, len, bitrate_kbps, out, &msg);
     return rc ? fail(rc, "%s", msg) : MP3S_OK;
+}
+
+int mp3s_wav_resample_info(const uint8_t *file, size_t len, int bitrate_kbps, int mode, mp3s_wav_resample *out)
+{
+    if (!file || !len || !out) return fail(MP3S_E_ARG, "null pointer");
+    if (mode != 1 && mode != 32000 && mode != 44100 && mode != 48000) return fail(MP3S_E_ARG, "mode %d is not 1, 32000, 44100 or 48000", mode);
+    const char *msg = "";
+    mp3s_wav_import w;
+    const int rc = wav_import_parse(file, len, bitrate_kbps, &w, &msg, mode, out);
+    return rc ? fail(rc, "%s", msg) : MP3S_OK;
+}
+
+int mp3s_wav_resample_taps(int L, int M, int32_t *taps, int cap, int32_t *T)
+{
+    if (!taps || !T || cap < 0) return fail(MP3S_E_ARG, "bad argument");
+    std::vector<int32_t> c;
+    int t = 0;
+    *T = 0;
+    if (wav_resample_taps(L, M, c, &t)) return fail(MP3S_E_ARG, "no tap table for the ratio %d / %d", L, M);
+    *T = t;
+    if (c.size() > (size_t)cap) return fail(MP3S_E_ARG, "%zu taps, room for %d", c.size(), cap);
+    std::memcpy(taps, c.data(), c.size() * sizeof(int32_t));
+    return MP3S_OK;
 }
 
 int mp3s_wav_header(int64_t n_rows, int nch, int rate, uint8_t *out44)

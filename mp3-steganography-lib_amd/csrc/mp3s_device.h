@@ -19,7 +19,7 @@ constexpr int DEC_SYNTH_FAST_TW = 2;   // the fast int16 variant (k_dec_synth_fa
 
 // optional per-kernel HIP-event timing: when non-null, every kernel launch is bracketed by two events
 // recorded on the launch stream; mp3s_profile_collect() turns the pairs into per-kernel totals.
-enum KernelId { K_DEC_IMDCT = 0, K_DEC_SYNTH, K_ENC_ANALYSIS, K_ENC_MDCT, K_RATE_LOOP, K_DEC_HUFFMAN, K_ENC_PACK, K_CHAIN, K_COUNT };
+enum KernelId { K_DEC_IMDCT = 0, K_DEC_SYNTH, K_ENC_ANALYSIS, K_ENC_MDCT, K_RATE_LOOP, K_DEC_HUFFMAN, K_ENC_PACK, K_CHAIN, K_WAV_RESAMPLE, K_COUNT };
 struct Profiler {
     static constexpr int MAX_PAIRS = 8192;
     hipEvent_t ev[2 * MAX_PAIRS];
@@ -116,6 +116,15 @@ struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes
 // of its n_frames frames is zero
 struct WavImportRun { uint64_t src, n_samples; uint32_t first_frame, n_frames, format, channels; };   // 32 bytes
 constexpr size_t kWavSlack = 64;   // k_wav_gather reads up to 31 bytes behind the last sample taken, k_wav_import up to 40 (k_wav.hpp)
+// ... and of k_wav_resample (k_resample.hpp, MP3S_OPT_WAV_RESAMPLE): a stream whose n_in rows k_wav_import has laid as [L | R] dwords from dword
+// src_row of a scratch buffer; n_out rows are computed into its n_frames frames of the batch, the rest of them is zero.  taps: the packed
+// table of the ratio on the device (pack_resample_taps), span: the input rows a tile of kResTile output rows stages (resample_span)
+struct WavResampleRun { const uint32_t *taps; uint64_t src_row, n_in, n_out; uint32_t first_frame, n_frames, L, M, T, span, mono, taps_lds; };   // 64 bytes
+constexpr int kResTile = 1024;          // output rows of a tile: four per lane, one 16-byte store
+constexpr uint32_t kResTapsLds = 2048;  // tap pairs (dwords) of a table that is staged in LDS; a larger one is read through the cache
+inline uint32_t resample_span(uint32_t L, uint32_t M, uint32_t T) { return (uint32_t)(((uint64_t)(kResTile - 1) * M + L - 1) / L) + T; }
+int launch_wav_resample(hipStream_t stream, const uint32_t *d_rows, const WavResampleRun *d_runs, int n_runs, int max_frames /* of one run */,
+                        size_t lds_bytes /* the largest (span + staged tap pairs) * 4 of the runs */, int16_t *d_pcm, Profiler *prof);
 int launch_wav_import(hipStream_t stream, const uint8_t *d_image, const WavImportRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 

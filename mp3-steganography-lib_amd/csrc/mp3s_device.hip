@@ -25,6 +25,7 @@ __constant__ DevTables c_tab;
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
+#include "k_resample.hpp"
 
 namespace mp3s {
 
@@ -452,6 +453,20 @@ int launch_wav_import(hipStream_t stream, const uint8_t *d_image, const WavImpor
     const unsigned gx = (unsigned)std::min<size_t>(((size_t)max_frames * 288 + 255) / 256, 2048);
     for (int r0 = 0; r0 < n_runs; r0 += 32768)
         hipLaunchKernelGGL(k_wav_import, dim3(gx, (unsigned)std::min(n_runs - r0, 32768)), dim3(256), 0, stream, d_image, d_runs, r0, d_pcm);
+    return (int)hipGetLastError();
+}
+
+// k_wav_resample: one grid row per stream, tiles of kResTile output rows along x (ONE launch for a batch of up to 32 768 streams)
+int launch_wav_resample(hipStream_t stream, const uint32_t *d_rows, const WavResampleRun *d_runs, int n_runs, int max_frames, size_t lds_bytes,
+                        int16_t *d_pcm, Profiler *prof)
+{
+    if (n_runs <= 0 || max_frames <= 0) return 0;
+    if (lds_bytes > 64 * 1024) return (int)hipErrorInvalidValue;
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)max_frames * 1152 + kResTile - 1) / kResTile, 2048);
+    const int pp = prof ? prof->begin(stream, K_WAV_RESAMPLE) : -1;
+    for (int r0 = 0; r0 < n_runs; r0 += 32768)
+        hipLaunchKernelGGL(k_wav_resample, dim3(gx, (unsigned)std::min(n_runs - r0, 32768)), dim3(256), lds_bytes, stream, d_rows, d_runs, r0, d_pcm);
+    if (prof) prof->end(stream, pp);
     return (int)hipGetLastError();
 }
 

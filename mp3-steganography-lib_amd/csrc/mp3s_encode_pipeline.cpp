@@ -656,7 +656,7 @@ int mp3s_encode_file(mp3s_ctx *c, const uint8_t *wav, size_t len, int bitrate_kb
                      mp3s_buf **owner, mp3s_file *out)
 {
     if (!c || !wav || !owner || !out) return fail(MP3S_E_ARG, "null pointer");
-    if (c->opt[MP3S_OPT_WAV_IMPORT]) {
+    if (c->opt[MP3S_OPT_WAV_IMPORT] || c->opt[MP3S_OPT_WAV_RESAMPLE]) {
         // the import rules (mp3s_wav_import_info): the samples are converted on the device, so the file is a batch of one
         const int32_t kbps = bitrate_kbps, nh = n_hide;
         return mp3s_encode_files(c, &wav, &len, 1, &kbps, hide_bits || n_hide ? &hide_bits : nullptr, &nh, owner, out, nullptr);

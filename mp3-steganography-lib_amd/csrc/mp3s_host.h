@@ -160,7 +160,13 @@ int wav_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_info *
 // statement of the rule: mp3s_encode_file, mp3s_encode_files and the pipe's encode jobs all ask here.
 int wav_frame_count(const mp3s_wav_info &w, int64_t *count, const char **msg);
 // the opt-in reader of MP3S_OPT_WAV_IMPORT (rules: mp3s_wav_import_info in include/mp3s.h): MP3S_OK, or a code with *msg
-int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out, const char **msg);
+// With `resample` (MP3S_OPT_WAV_RESAMPLE: 1 / 32000 / 44100 / 48000) any rate wav_resample_plan takes passes, out->samplerate stays the
+// file's own, the bitrate is checked against the target rate and *rs (optional) is filled (mp3s_wav_resample_info)
+int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out, const char **msg, int resample = 0, mp3s_wav_resample *rs = nullptr);
+// target rate, ratio L / M in lowest terms and filter size (T = 2 H taps per phase) of the resampler; non-zero: the rate is refused
+int wav_resample_plan(int in_rate, int mode, int *out_rate, int *L, int *M, int *T, int *H);
+// its integer tap table c[L][T] (2^15 scale, every phase sums to 32768, sum |c| <= 65535 over the taps below 2 (H / 2) and over the rest); non-zero: no table for this ratio
+int wav_resample_taps(int L, int M, std::vector<int32_t> &c, int *T);
 // the 44-byte header scipy.io.wavfile.write emits for int16 data
 void wav_header(int64_t n_rows, int nch, int rate, uint8_t *out44);
 // reference steganography.py:10-24, 42-50

@@ -1,6 +1,7 @@
 // Container formats and message framing on the host: WAV header in/out, "<count>#<text>" framing
 // and the reveal parse.  Byte shuffling only -- nothing here is on the device path.
 #include <stdio.h>
+#include <math.h>
 #include <string.h>
 
 #include "mp3s_host.h"
@@ -143,9 +144,11 @@ int wav_frame_count(const mp3s_wav_info &w, int64_t *count_out, const char **msg
 // The opt-in reader (MP3S_OPT_WAV_IMPORT; the rules are stated at mp3s_wav_import_info in include/mp3s.h): a RIFF chunk walk over the
 // whole file instead of a tag search in its first 128 bytes, and every sample format a WAV file usually has.  The reference's texts
 // are kept for what both readers refuse.
-int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *o, const char **msg)
+int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *o, const char **msg, int resample, mp3s_wav_resample *rs)
 {
     memset(o, 0, sizeof *o);
+    if (rs) memset(rs, 0, sizeof *rs);
+    int out_rate = 0, rL = 1, rM = 1, rT = 0, rH = 0;
     *msg = "Bad WAVE file.";
     if (len < 12 || memcmp(file, "RIFF", 4) || memcmp(file + 8, "WAVE", 4)) return MP3S_E_EXIT;
     uint64_t fmt_at = 0, fmt_size = 0, data_at = 0, data_size = 0;
@@ -185,7 +188,10 @@ int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav
     *msg = "more than two channels";
     if (ch > 2) return MP3S_E_UNSUPPORTED;
     *msg = "Unsupported sampling frequency.";
-    if (rate != 32000 && rate != 44100 && rate != 48000) return MP3S_E_EXIT;
+    if (!resample) {
+        if (rate != 32000 && rate != 44100 && rate != 48000) return MP3S_E_EXIT;
+        out_rate = (int)rate;
+    } else if (rate > 0x7fffffffu || wav_resample_plan((int)rate, resample, &out_rate, &rL, &rM, &rT, &rH)) return MP3S_E_EXIT;
     *msg = "Unsupported WAVE file, samples not int8, int16 or int32 type.";
     if (tag == 3) {
         if (bits != 32) return MP3S_E_EXIT;
@@ -197,7 +203,7 @@ int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav
     o->block_align = (int32_t)(ch * (bits / 8));   // (computed: the field in the file is not trusted)
     int sri, bri, whole;
     *msg = "Unsupported bitrate configuration.";
-    if (stream_params(o->samplerate, bitrate_kbps, &sri, &bri, &whole)) return MP3S_E_EXIT;
+    if (stream_params(out_rate, bitrate_kbps, &sri, &bri, &whole)) return MP3S_E_EXIT;
     const uint64_t left = len - data_at;
     const uint64_t bytes = data_size == 0 || data_size == 0xffffffffu || data_size > left ? left : data_size;   // (0 / all ones: to the end of the file)
     o->data_offset = (int64_t)data_at;
@@ -206,7 +212,76 @@ int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav
     *msg = "no samples";
     if (o->n_samples == 0) return MP3S_E_UNSUPPORTED;
     *msg = "";
+    if (rs) {
+        rs->in = *o;
+        rs->out_rate = out_rate; rs->L = rL; rs->M = rM; rs->taps = rT; rs->half = rH;
+        rs->n_out = (int64_t)(((unsigned __int128)o->n_samples * (unsigned)rL + (unsigned)rM - 1) / (unsigned)rM);
+        rs->n_frames = (rs->n_out + 1151) / 1152;
+    }
     return MP3S_OK;
+}
+
+// The resampler of MP3S_OPT_WAV_RESAMPLE (the rules are stated at mp3s_wav_resample_info in include/mp3s.h), host part: the target
+// rate, the ratio and the integer tap table.  Everything the device computes with is an integer made here.
+int wav_resample_plan(int in_rate, int mode, int *out_rate, int *L, int *M, int *T, int *H)
+{
+    static const int kRates[3] = {32000, 44100, 48000};
+    if (in_rate <= 0) return 1;
+    auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
+    int target = 0;
+    if (mode != 1) target = mode;
+    else if (in_rate == 32000 || in_rate == 44100 || in_rate == 48000) target = in_rate;
+    else {
+        // the supported rates not below the file's (all three above 48 000 Hz): the smallest L, then the highest rate
+        int64_t best = 0;
+        for (int r : kRates) {
+            if (in_rate <= 48000 && r < in_rate) continue;
+            const int64_t l = r / gcd(r, in_rate);
+            if (!target || l <= best) { target = r; best = l; }
+        }
+    }
+    const int64_t g = gcd(target, in_rate);
+    const int64_t l = target / g, m = in_rate / g;
+    // rho = min(1, L / M); H = ceil(16 / rho)
+    const int64_t h = l >= m ? 16 : (16 * m + l - 1) / l;
+    if (l > 1280 || 2 * h > 256) return 1;
+    *out_rate = target; *L = (int)l; *M = (int)m; *H = (int)h; *T = (int)(2 * h);
+    return 0;
+}
+
+int wav_resample_taps(int L, int M, std::vector<int32_t> &c, int *T_out)
+{
+    if (L < 1 || M < 1 || L > 1280) return 1;
+    const int64_t h64 = L >= M ? 16 : (16 * (int64_t)M + L - 1) / L;
+    if (2 * h64 > 256) return 1;
+    const int H = (int)h64, T = 2 * H;
+    const double pi = 3.14159265358979323846;
+    const double rho = L >= M ? 1.0 : (double)L / (double)M, fc = 0.95 * rho;
+    c.assign((size_t)L * (size_t)T, 0);
+    for (int p = 0; p < L; p++) {
+        int32_t *row = c.data() + (size_t)p * (size_t)T;
+        int64_t sum = 0;
+        int big = 0;
+        for (int k = 0; k < T; k++) {
+            const double t = (double)(k - H + 1) - (double)p / (double)L;
+            const double u = t / (double)H;
+            double w = 0.0;
+            if (u > -1.0 && u <= 1.0) w = 0.35875 + 0.48829 * cos(pi * u) + 0.14128 * cos(2.0 * pi * u) + 0.01168 * cos(3.0 * pi * u);
+            const double x = fc * t;
+            const double sinc = x == 0.0 ? 1.0 : sin(pi * x) / (pi * x);
+            row[k] = (int32_t)rint(fc * sinc * w * 32768.0);
+            sum += row[k];
+            if (row[k] > row[big]) big = k;           // (the first of equal taps)
+        }
+        row[big] += (int32_t)(32768 - sum);            // DC gain exactly 1
+        // the bound that keeps the device's sums inside int32: it adds the taps below 2 (H / 2) and the rest apart (65535 x 32768 + 2^14 < 2^31)
+        // and joins the two in 64 bits.  (One sum over the phase would not do: sum |c| is 69 292 for L / M = 2 / 1.)
+        int64_t mag[2] = {0, 0};
+        for (int k = 0; k < T; k++) mag[k >= 2 * (H / 2)] += row[k] < 0 ? -(int64_t)row[k] : row[k];
+        if (mag[0] > 65535 || mag[1] > 65535) return 1;
+    }
+    *T_out = T;
+    return 0;
 }
 
 // the 44 bytes scipy.io.wavfile.write puts in front of int16 data (reference MP3_Parser.py:86-93 -> scipy)

@@ -55,6 +55,9 @@ struct mp3s_ctx {
     Profiler prof;
     // device buffers of the stream pipelines, kept between calls (hipMalloc/hipFree cost more than a small file's work)
     static constexpr int kPoolSlots = 32;
+    // the packed tap tables of the resampler (MP3S_OPT_WAV_RESAMPLE), one per ratio the context has met (mp3s_encode_files.cpp)
+    struct ResampleTaps { int L, M, T; uint32_t *d; };
+    std::vector<ResampleTaps> res_taps;
     void *pool[kPoolSlots] = {nullptr};
     size_t pool_bytes[kPoolSlots] = {0};
     void *grab(int slot, size_t bytes)
@@ -362,8 +365,12 @@ struct WavPlan {
     int64_t data_offset = 0, count = 0 /* frames */, n_samples = 0 /* per channel */;
     size_t need = 0;      // bytes of the file that go into the image: everything up to the last sample taken
     bool gather = true;   // the frames are contiguous int16 stereo in the file
+    // MP3S_OPT_WAV_RESAMPLE, a file whose rate is not the target's: samplerate and count are the output's, n_samples the input's
+    bool resample = false;
+    int L = 1, M = 1, T = 0;
+    int64_t in_frames = 0 /* ceil(n_samples / 1152): what k_wav_import fills of the scratch */, n_out = 0;
 };
-int wav_encode_plan(bool import, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p);
+int wav_encode_plan(bool import, int resample, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p);
 // the records of the two kernels for stream `k` of a batch whose image holds the file at `img`
 inline void wav_plan_record(const WavPlan &p, size_t img, uint32_t first_frame, std::vector<WavRun> &runs, std::vector<WavImportRun> &iruns)
 {
@@ -371,7 +378,7 @@ inline void wav_plan_record(const WavPlan &p, size_t img, uint32_t first_frame, 
     else iruns.push_back({(uint64_t)img + (uint64_t)p.data_offset, (uint64_t)p.n_samples, first_frame, (uint32_t)p.count, (uint32_t)p.format, (uint32_t)p.channels});
 }
 // mp3s_encode_files with the reader named by the caller (a pipe keeps the option's value of the day it was created)
-int encode_files_as(mp3s_ctx *c, bool import, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+int encode_files_as(mp3s_ctx *c, bool import, int resample, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
                     const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status);
 
 // ---------------------------------------------------------------- one file as chunks through the overlapped stages (run_file.cpp)

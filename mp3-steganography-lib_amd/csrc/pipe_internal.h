@@ -152,6 +152,7 @@ struct mp3s_pipe {
     FileUp up;
     bool internal = false;               // the context's own (run_file): no worker threads, jobs issued by the caller
     bool wav_import = false;             // MP3S_OPT_WAV_IMPORT of the context when the pipe was created: how its encode jobs read their WAV files
+    int wav_resample = 0;                // ... and MP3S_OPT_WAV_RESAMPLE (non-zero implies the import reader)
     size_t max_job_bytes = 0;
     size_t max_frames = 0;               // frames a job can have at most (the context's own pipe cuts its chunks by frames); 0: from the bytes, 96 per frame
     std::vector<Slot> slots;

@@ -637,7 +637,8 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
         const uint8_t *hide = j.enc_hide ? j.msgs[i].first : nullptr;
         const int n_hide = j.enc_hide ? (int)j.msgs[i].second : 0;
         WavPlan w;
-        if (wav_encode_plan(P->wav_import, file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w)) return false;
+        if (wav_encode_plan(P->wav_import, P->wav_resample, file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w)) return false;
+        if (w.resample) return false;            // (a slot has no scratch at the source rate: mp3s_encode_files resamples the job's files)
         const int64_t count = w.count;
         if (i == 0) { j.rate = w.samplerate; j.kbps = j.enc_kbps[0]; }
         else if (w.samplerate != j.rate || j.enc_kbps[(size_t)i] != j.kbps) return false;   // more than one device batch
@@ -831,7 +832,7 @@ void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held
     if (j.encode) {
         std::vector<int32_t> nh(nf);
         for (int i = 0; i < nf; i++) { mp[i] = j.msgs[i].first; nh[i] = (int32_t)j.msgs[i].second; }
-        j.slow_rc = encode_files_as(P->c, P->wav_import, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
+        j.slow_rc = encode_files_as(P->c, P->wav_import, P->wav_resample, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
                                       &j.slow_owner, j.slow_out.data(), j.slow_st.data());
         j.slow_err = mp3s_last_error();
     } else if (j.block) {
@@ -1004,7 +1005,8 @@ int pipe_create(mp3s_ctx *c, int depth, size_t max_job_bytes, int scan_threads, 
     HIPCHK(hipSetDevice(c->device));
     std::unique_ptr<mp3s_pipe> P(new mp3s_pipe());
     P->c = c; P->depth = depth; P->internal = internal; P->max_job_bytes = max_job_bytes;
-    P->wav_import = c->opt[MP3S_OPT_WAV_IMPORT] != 0;
+    P->wav_resample = (int)c->opt[MP3S_OPT_WAV_RESAMPLE];
+    P->wav_import = c->opt[MP3S_OPT_WAV_IMPORT] != 0 || P->wav_resample != 0;
     auto destroy = [&](int code, const char *what) {
         for (auto &s : P->slots) free_slot(s);                // (the streams belong to the device: pick_lanes)
         for (hipEvent_t e : P->e_dec) if (e) (void)hipEventDestroy(e);

@@ -129,6 +129,11 @@ class WavImport(C.Structure):
 WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32 = 1, 2, 3, 4, 5
 
 
+class WavResample(C.Structure):
+    _fields_ = [("in_", WavImport), ("out_rate", C.c_int32), ("L", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("half", C.c_int32),
+                ("n_out", C.c_int64), ("n_frames", C.c_int64)]
+
+
 class File(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("kbps", C.c_int32), ("sampling_rate", C.c_int32),
                 ("channels", C.c_int32), ("n_frames", C.c_int32), ("too_long", C.c_int32), ("n_bits", C.c_int32),
@@ -186,7 +191,7 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_hide_message", "mp3s_clear_file", "mp3s_hide_message_fd", "mp3s_clear_file_fd", "mp3s_decode_file_fd", "mp3s_hide_messages", "mp3s_reencode_block", "mp3s_reveal_message",
            "mp3s_pipe_create", "mp3s_pipe_destroy", "mp3s_pipe_submit", "mp3s_pipe_submit_decode", "mp3s_pipe_collect", "mp3s_pipe_get_stats",
            "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
-           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info"]
+           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps"]
 
 _lib = None
 _lock = threading.Lock()
@@ -264,6 +269,8 @@ def lib():
         psz = C.POINTER(sz)
         L.mp3s_wav_parse.argtypes = [vp, sz, i32, C.POINTER(WavInfo)]
         L.mp3s_wav_import_info.argtypes = [vp, sz, i32, C.POINTER(WavImport)]
+        L.mp3s_wav_resample_info.argtypes = [vp, sz, i32, i32, C.POINTER(WavResample)]
+        L.mp3s_wav_resample_taps.argtypes = [i32, i32, vp, i32, C.POINTER(i32)]
         L.mp3s_wav_header.argtypes = [i64, i32, i32, vp]
         L.mp3s_message_frame.argtypes = [vp, sz, pvp, pvp, psz]
         L.mp3s_message_reveal.argtypes = [vp, sz, pvp, pvp, psz]
@@ -367,7 +374,7 @@ class Context:
             self.handle = None
 
     OPTIONS = {"select": 1, "redo": 2, "fast_imdct": 3, "pipe_tail": 4, "chunk_frames": 5, "device_parse": 6, "file_pipeline": 7,
-               "scan_threads": 8, "first_chunk_frames": 9, "file_up": 10, "huf_lanes": 11, "numa": 12, "float_fast": 13, "fail_chunk": 14, "fused_decode": 15, "fused_encode": 16, "pipe_dec": 17, "rate_signals": 18, "pipe_signals": 19, "wav_import": 20}
+               "scan_threads": 8, "first_chunk_frames": 9, "file_up": 10, "huf_lanes": 11, "numa": 12, "float_fast": 13, "fail_chunk": 14, "fused_decode": 15, "fused_encode": 16, "pipe_dec": 17, "rate_signals": 18, "pipe_signals": 19, "wav_import": 20, "wav_resample": 21}
 
     def set_option(self, name, value):
         """options of the context (include/mp3s.h MP3S_OPT_*); returns the value the option had"""
@@ -512,7 +519,7 @@ class Context:
         return g.value
 
     KERNELS = ("k_dec_imdct", "k_dec_synth", "k_enc_analysis", "k_enc_mdct", "k_rate_loop", "k_dec_huffman",
-               "k_enc_pack", "k_chain")
+               "k_enc_pack", "k_chain", "k_wav_resample")
 
     def profile_enable(self, on=True):
         check(lib().mp3s_profile_enable(self.handle, 1 if on else 0))
@@ -824,7 +831,9 @@ class Context:
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
         n, files, lens, _, _, _, keep = _encode_args(wavs, 128, None, None)
-        if self.get_option("wav_import"):            # a frame of mono 8-bit samples is 1 152 bytes of its file
+        if self.get_option("wav_resample"):          # the frames at the target rate
+            cap = sum(wav_resample_info(w, 128, self.get_option("wav_resample"))["n_frames"] for w in wavs)
+        elif self.get_option("wav_import"):          # a frame of mono 8-bit samples is 1 152 bytes of its file
             cap = sum(wav_import_info(w, 128)["n_frames"] for w in wavs)
         else:
             cap = sum(len(w) for w in wavs) // 4608 + n
@@ -1067,6 +1076,35 @@ def wav_import_info(data: bytes, bitrate=320):
     w = WavImport()
     check(lib().mp3s_wav_import_info(buf.ctypes.data if len(data) else None, len(data), int(bitrate), C.byref(w)))
     return {k: getattr(w, k) for k, _ in WavImport._fields_}
+
+
+def wav_resample_info(data: bytes, bitrate=320, mode=1):
+    """what a WAV file of any sampling rate is to the encode calls under the "wav_resample" option (include/mp3s.h
+    mp3s_wav_resample_info; mode = the option's value 1 / 32000 / 44100 / 48000) -> dict(in=<the dict of wav_import_info at the file's own
+    rate>, out_rate, L, M, taps, half, n_out, n_frames); raises Mp3sError like wav_import_info.  No GPU."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    w = WavResample()
+    check(lib().mp3s_wav_resample_info(buf.ctypes.data if len(data) else None, len(data), int(bitrate), int(mode), C.byref(w)))
+    out = {k: getattr(w, k) for k, _ in WavResample._fields_ if k != "in_"}
+    out["in"] = {k: getattr(w.in_, k) for k, _ in WavImport._fields_}
+    return out
+
+
+def wav_resample_taps(L, M):
+    """the integer tap table the device uses for the ratio L / M: int32 [L][T] (include/mp3s.h mp3s_wav_resample_taps).  No GPU."""
+    taps = np.zeros(max(1, int(L)) * 256, dtype=np.int32)
+    t = C.c_int32()
+    check(lib().mp3s_wav_resample_taps(int(L), int(M), taps.ctypes.data, taps.size, C.byref(t)))
+    return taps[:int(L) * t.value].reshape(int(L), t.value).copy()
+
+
+def wav_resample_default():
+    """the default of the "wav_resample" option for a context created now (MP3S_WAV_RESAMPLE, as mp3s_ctx_create reads it)"""
+    try:
+        v = int(os.environ.get("MP3S_WAV_RESAMPLE", "") or 0)
+    except ValueError:
+        return 0
+    return v if v in (1, 32000, 44100, 48000) else 0
 
 
 def wav_import_default():

@@ -20,7 +20,8 @@ class _ImportedWav:
         with open(file_path, 'rb') as f:
             self.data = f.read()
         try:
-            w = _lib.wav_import_info(self.data, bit_rate)
+            mode = _lib.wav_resample_default()
+            w = _lib.wav_resample_info(self.data, bit_rate, mode)["in"] if mode else _lib.wav_import_info(self.data, bit_rate)
         except _lib.Mp3sError as e:
             if e.code == _lib.E_EXIT:
                 sys.exit(e.text)
@@ -49,9 +50,10 @@ class Encoder:
         try:
             self.__wav_file = WavReader(self.__file_path, bitrate)
         except (SystemExit, ValueError):
-            # MP3S_WAV_IMPORT=1 (the "wav_import" option's default): a header only the import rules accept is passed through to the
-            # native call; what both readers refuse keeps the reference's exit
-            if not _lib.wav_import_default():
+            # MP3S_WAV_IMPORT=1 / MP3S_WAV_RESAMPLE (the defaults of the "wav_import" and "wav_resample" options): a header only the
+            # import rules accept, or a sampling rate only the resampler takes, is passed through to the native call; what they
+            # refuse too keeps the reference's exit
+            if not _lib.wav_import_default() and not _lib.wav_resample_default():
                 raise
             self.__wav_file = _ImportedWav(self.__file_path, bitrate)
         self.__hide_str = hide_str

@@ -12,6 +12,12 @@ returns finished results), device events for the resident half; every shape is w
 --format u8|s16|s24|s32|f32 and --channels 1|2 write the same audio as WAV files of that sample format and channel count and turn the
 context's "wav_import" option on (k_wav_import converts them on the device); --wav-import 1 turns it on for the canonical 16-bit stereo
 files too (they keep k_wav_gather: the figure to hold against the option's off state).
+
+--resample runs ONE other case instead: Context.encode_files on 250 files x 40 output frames of 16-bit stereo at 22 050 Hz with the
+"wav_resample" option on (k_wav_import + k_wav_resample on the device), against the same call on the same audio resampled on the host
+beforehand (tests/wav_resample_model.py with the library's tap table: the same rows, so the same MP3 bytes) to 44 100 Hz, option off;
+medians of --repeats alternating runs, and k_wav_resample's own time from the profile counters in a run of its own.  --resample-rate R
+takes files of R Hz instead (96000, 192000, 384000: the down-sampling ratios with their longer filters).
 """
 import argparse
 import json
@@ -126,6 +132,37 @@ def encode_half_resident_ms(_lib, ctx, pcms, want, repeats):
     return ms
 
 
+def resample_case(_lib, ctx, repeats, rate=22050):
+    from synth_pcm import synth_pcm
+    import wav_resample_model as R
+    plan = R.plan(rate, 1)
+    L, M, out_rate = plan["L"], plan["M"], plan["out_rate"]
+    assert 40 * M % L == 0, "a rate whose 40 output frames are whole input frames"
+    taps = _lib.wav_resample_taps(L, M)
+    low = [synth_pcm(40 * M // L, seed=3000 + i) for i in range(250)]         # e.g. 20 frames at 22 050 Hz = 40 frames at 44 100 Hz
+    wavs_low = [_lib.wav_header(p.shape[0], 2, rate) + np.ascontiguousarray(p, dtype="<i2").tobytes() for p in low]
+    wavs_pre = [wav_of(R.frames_of(R.resample(p, L, M, taps)), out_rate)[0] for p in low]
+    on = lambda: (ctx.set_option("wav_resample", 1), ctx.encode_files(wavs_low, 128))[1]
+    off = lambda: (ctx.set_option("wav_resample", 0), ctx.encode_files(wavs_pre, 128))[1]
+    assert [bytes(r["data"]) for r in on()] == [bytes(r["data"]) for r in off()], "the resampled batch's bytes differ from the pre-resampled one's"
+    on(); off()
+    on_ms, off_ms = [], []
+    for _ in range(repeats):
+        t0 = time.perf_counter(); on(); t1 = time.perf_counter(); off(); t2 = time.perf_counter()
+        on_ms.append((t1 - t0) * 1e3); off_ms.append((t2 - t1) * 1e3)
+    ctx.profile_select(["k_wav_resample"]); ctx.profile_enable(True)
+    for _ in range(repeats):
+        on()
+    ms, launches = ctx.profile_collect()["k_wav_resample"]
+    ctx.profile_enable(False); ctx.profile_select(None); ctx.set_option("wav_resample", 0)
+    rows_in, rows_out = sum(p.shape[0] for p in low), 250 * 40 * 1152
+    k_ms = ms / max(1, launches)
+    return {"what": "250 files x 40 output frames, %d -> %d Hz (L / M = %d / %d, %d taps), 128 kbit/s, 16-bit stereo" % (rate, out_rate, L, M, plan["taps"]), "resample_on_ms": on_ms, "pre_resampled_off_ms": off_ms,
+            "resample_on_median_ms": statistics.median(on_ms), "pre_resampled_off_median_ms": statistics.median(off_ms),
+            "ratio": statistics.median(on_ms) / statistics.median(off_ms), "k_wav_resample_ms_per_launch": k_ms, "k_wav_resample_launches": launches,
+            "k_wav_resample_bytes_read_written": 4 * (rows_in + rows_out), "k_wav_resample_gb_per_s": 4 * (rows_in + rows_out) / (k_ms * 1e-3) / 1e9 if k_ms else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -136,10 +173,20 @@ def main():
     ap.add_argument("--format", choices=["u8", "s16", "s24", "s32", "f32"], default="s16")
     ap.add_argument("--channels", type=int, choices=[1, 2], default=2)
     ap.add_argument("--wav-import", type=int, choices=[0, 1], default=None, help="the context's wav_import option (default: on for what only it reads)")
+    ap.add_argument("--resample-rate", type=int, default=22050, help="the files' sampling rate in the --resample case (22050, 96000, 192000, 384000 ...)")
+    ap.add_argument("--resample", action="store_true", help="only the wav_resample case: 250 files at 22 050 Hz against the same audio pre-resampled")
     args = ap.parse_args()
     from mp3stego import _lib
     from synth_pcm import synth_pcm
     ctx = _lib.Context(0)
+    if args.resample:
+        r = {"device": ctx.device_name(), "repeats": args.repeats, "clock": "host perf_counter around calls that return finished results", "resample": resample_case(_lib, ctx, args.repeats, args.resample_rate)}
+        ctx.close()
+        print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r["resample"].items() if not isinstance(v, list)}), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(r, indent=1, sort_keys=True) + "\n")
+        return
     canonical = args.format == "s16" and args.channels == 2
     ctx.set_option("wav_import", (0 if canonical else 1) if args.wav_import is None else args.wav_import)
     result = {"device": ctx.device_name(), "repeats": args.repeats, "format": args.format, "channels": args.channels, "wav_import": ctx.get_option("wav_import"), "clock": "host perf_counter around calls that return finished results", "workloads": {}}
