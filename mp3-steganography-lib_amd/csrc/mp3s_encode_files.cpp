@@ -17,14 +17,20 @@ int wav_encode_check(const uint8_t *wav, size_t len, int bitrate_kbps, const uin
     return MP3S_OK;
 }
 
-// the same for either reader.  With `import` (MP3S_OPT_WAV_IMPORT) the header is wav_import_parse's, with its codes and texts; a
+WavRead wav_read_of(const mp3s_ctx *c)
+{
+    const int resample = (int)c->opt[MP3S_OPT_WAV_RESAMPLE];
+    return {c->opt[MP3S_OPT_WAV_IMPORT] != 0 || resample != 0, resample};
+}
+
+// the same for either reader.  With how.import (MP3S_OPT_WAV_IMPORT) the header is wav_import_parse's, with its codes and texts; a
 // 16-bit stereo file of whole frames is what the strict reader makes of it (the compatibility rule), so it keeps k_wav_gather
-// With `resample` (MP3S_OPT_WAV_RESAMPLE, which implies the import reader) a file whose rate is not the target's is planned for
+// With how.resample (MP3S_OPT_WAV_RESAMPLE) a file whose rate is not the target's is planned for
 // k_wav_resample: samplerate and count are the OUTPUT's, n_samples and in_frames the input's
-int wav_encode_plan(bool import, int resample, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p)
+int wav_encode_plan(WavRead how, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p)
 {
     *p = WavPlan();
-    if (!import && !resample) {
+    if (!how.import) {
         mp3s_wav_info w;
         const int rc = wav_encode_check(wav, len, bitrate_kbps, hide_bits, n_hide, &w, &p->count);
         if (rc) return rc;
@@ -36,7 +42,7 @@ int wav_encode_plan(bool import, int resample, const uint8_t *wav, size_t len, i
     const char *msg = "";
     mp3s_wav_import w;
     mp3s_wav_resample rs;
-    const int rc = wav_import_parse(wav, len, bitrate_kbps, &w, &msg, resample, &rs);
+    const int rc = wav_import_parse(wav, len, bitrate_kbps, &w, &msg, how.resample, &rs);
     if (rc) return fail(rc, "%s", msg);
     if (n_hide < 0 || (n_hide > 0 && !hide_bits)) return fail(MP3S_E_ARG, "bad hide arguments");
     if (w.n_frames > 0x7fffffff / 8 || rs.n_frames > 0x7fffffff / 8) return fail(MP3S_E_ARG, "too many frames");
@@ -82,109 +88,44 @@ struct WavIn {
     WavPlan p;
 };
 
-// the files `idx` to the device: their images up, the gather (and, for what it does not take, the import kernel) queued on the context's stream -> *d_pcm_out = [n_all][1152][2] int16 in
-// the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is waited for; `runs` and the
-// callers' bytes are read by copies in flight until the stream is synchronised.
-// Streams of MP3S_OPT_WAV_RESAMPLE go the same way in two steps: k_wav_import lays their samples, at the source rate, into a scratch
-// buffer of their own (sruns), k_wav_resample computes their frames of the PCM buffer from there (rruns).
-struct WavRecords {
-    std::vector<WavRun> runs;
-    std::vector<WavImportRun> iruns, sruns;
-    std::vector<WavResampleRun> rruns;
-};
-
-int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, WavRecords &rec,
-                  void **d_pcm_out, int64_t *n_all_out)
+// the files `idx` to the device: their images up, the batch's kernels (launch_wav_batch) queued on the context's stream -> *d_pcm_out =
+// [b.n_all][1152][2] int16 in the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is
+// waited for; the batch's records and the callers' bytes are read by copies in flight until the stream is synchronised.
+// Buffers: image and records in pool slot 27 (the records behind the image and its slack), PCM in 7, the resampler's scratch in 28,
+// the short files' staging in h_blob.
+int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, WavBatch &b, void **d_pcm_out)
 {
-    std::vector<WavRun> &runs = rec.runs;
-    std::vector<WavImportRun> &iruns = rec.iruns, &sruns = rec.sruns;
-    std::vector<WavResampleRun> &rruns = rec.rruns;
     segs.assign(idx.size(), EncSeg());
-    runs.clear(); iruns.clear(); sruns.clear(); rruns.clear();
-    runs.reserve(idx.size());
-    std::vector<size_t> at(idx.size());
-    int64_t n_all = 0, max_frames = 0, max_iframes = 0, max_sframes = 0, max_rframes = 0, s_all = 0 /* frames of the resampler's scratch */;
-    size_t img = 0, staged = 0, res_lds = 0;
+    b.clear();
     HIPCHK(hipSetDevice(c->device));                               // (in front of every allocation below, the tap tables' included)
     for (size_t k = 0; k < idx.size(); k++) {
         const WavIn &f = in[(size_t)idx[k]];
         segs[k].n_frames = (int)f.p.count; segs[k].hide = f.hide; segs[k].n_hide = f.n_hide;
-        img = (img + 15) & ~(size_t)15;
-        at[k] = img;
-        if (f.p.resample) {
-            const WavPlan &p = f.p;
-            const uint32_t *d_taps = nullptr;
-            const int rc = resample_taps_dev(c, p.L, p.M, &d_taps);
-            if (rc) return rc;
-            const uint32_t span = resample_span((uint32_t)p.L, (uint32_t)p.M, (uint32_t)p.T), pairs = (uint32_t)p.L * (uint32_t)p.T / 2;
-            const bool lds = pairs <= kResTapsLds;
-            sruns.push_back({(uint64_t)img + (uint64_t)p.data_offset, (uint64_t)p.n_samples, (uint32_t)s_all, (uint32_t)p.in_frames, (uint32_t)p.format, (uint32_t)p.channels});
-            rruns.push_back({d_taps, (uint64_t)s_all * 1152, (uint64_t)p.n_samples, (uint64_t)p.n_out, (uint32_t)n_all, (uint32_t)p.count,
-                             (uint32_t)p.L, (uint32_t)p.M, (uint32_t)p.T, span, p.channels == 1 ? 1u : 0u, lds ? 1u : 0u});
-            res_lds = std::max(res_lds, ((size_t)span + (lds ? pairs : 0)) * 4);
-            s_all += p.in_frames;
-            max_sframes = std::max(max_sframes, p.in_frames); max_rframes = std::max(max_rframes, p.count);
-            if (s_all > 0x7fffffff / 8) return fail(MP3S_E_ARG, "encode batch too large");
-        } else wav_plan_record(f.p, img, (uint32_t)n_all, runs, iruns);
-        const size_t need = f.p.need;
-        if (need < kDirectUpload) staged = img + need;
-        img += need;
-        n_all += f.p.count;
-        if (f.p.gather) max_frames = std::max(max_frames, f.p.count);
-        else if (!f.p.resample) max_iframes = std::max(max_iframes, f.p.count);
-        if (n_all > 0x7fffffff / 8) return fail(MP3S_E_ARG, "encode batch too large");
+        const uint32_t *d_taps = nullptr;
+        int rc = f.p.resample ? resample_taps_dev(c, f.p.L, f.p.M, &d_taps) : MP3S_OK;
+        if (!rc) rc = b.add(f.p, f.wav, d_taps);
+        if (rc) return rc;
     }
-    const size_t runs_at = (img + kWavSlack + 15) & ~(size_t)15;
-    const size_t iruns_at = runs_at + ((runs.size() * sizeof(WavRun) + 15) & ~(size_t)15);
-    const size_t sruns_at = iruns_at + ((iruns.size() * sizeof(WavImportRun) + 15) & ~(size_t)15);
-    const size_t rruns_at = sruns_at + ((sruns.size() * sizeof(WavImportRun) + 15) & ~(size_t)15);
-    uint8_t *d_image = (uint8_t *)c->grab(27, rruns_at + rruns.size() * sizeof(WavResampleRun));
-    void *d_pcm = c->grab(7, (size_t)n_all * 4608);
-    void *d_rows = rruns.empty() ? nullptr : c->grab(28, (size_t)s_all * 4608);
-    if (!d_image || !d_pcm || (!rruns.empty() && !d_rows)) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of WAV input", (long long)n_all);
-    // long files go up from where they lie; short ones are laid end to end first, bytes as they are, and travel in runs
-    // (one copy per run instead of one per file: a copy from ordinary memory costs its thread 10 us and more whatever its size)
-    std::vector<uint8_t> &stage = c->h_blob;
-    if (stage.size() < staged) stage.resize(staged);
-    size_t run_lo = 0, run_hi = 0;
-    auto flush = [&]() {
-        if (run_hi > run_lo) HIPCHK(hipMemcpyAsync(d_image + run_lo, stage.data() + run_lo, run_hi - run_lo, hipMemcpyHostToDevice, c->stream));
-        run_lo = run_hi = 0;
-        return (int)MP3S_OK;
-    };
-    for (size_t k = 0; k < idx.size(); k++) {
-        const WavIn &f = in[(size_t)idx[k]];
-        const size_t need = f.p.need;
-        if (need >= kDirectUpload) {
-            const int rc = flush();
-            if (rc) return rc;
-            const double t0 = trace_on() ? now_ms() : 0;
-            HIPCHK(hipMemcpyAsync(d_image + at[k], f.wav, need, hipMemcpyHostToDevice, c->stream));
-            if (trace_on()) fprintf(stderr, "mp3s:   encode_files: queueing the copy of %zu bytes from the caller's memory took %.3f ms\n", need, now_ms() - t0);
-        } else {
-            if (run_hi == run_lo) run_lo = at[k];
-            std::memcpy(stage.data() + at[k], f.wav, need);
-            run_hi = at[k] + need;
-        }
+    b.place_records(b.img + kWavSlack);
+    uint8_t *d_image = (uint8_t *)c->grab(27, b.rec_end);
+    void *d_pcm = c->grab(7, (size_t)b.n_all * 4608);
+    void *d_rows = b.rruns.empty() ? nullptr : c->grab(28, (size_t)b.s_all * 4608);
+    if (!d_image || !d_pcm || (!b.rruns.empty() && !d_rows)) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of WAV input", (long long)b.n_all);
+    std::vector<Upload> ups;
+    plan_uploads(b.files, [&](size_t extent) { if (c->h_blob.size() < extent) c->h_blob.resize(extent); return c->h_blob.data(); }, ups);
+    for (const Upload &u : ups) {
+        const bool direct = u.src != c->h_blob.data() + u.dst;
+        const double t0 = direct && trace_on() ? now_ms() : 0;
+        HIPCHK(hipMemcpyAsync(d_image + u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+        if (direct && trace_on()) fprintf(stderr, "mp3s:   encode_files: queueing the copy of %zu bytes from the caller's memory took %.3f ms\n", u.bytes, now_ms() - t0);
     }
-    int rc = flush();
+    for (const WavBatch::Part &p : b.parts())
+        if (p.bytes) HIPCHK(hipMemcpyAsync(d_image + p.at, p.data, p.bytes, hipMemcpyHostToDevice, c->stream));
+    if (trace_on()) fprintf(stderr, "mp3s:   encode_files: %zu streams through k_wav_gather, %zu through k_wav_import\n", b.runs.size(), b.iruns.size());
+    if (trace_on() && !b.rruns.empty()) fprintf(stderr, "mp3s:   encode_files: %zu streams through k_wav_import and k_wav_resample\n", b.rruns.size());
+    const int rc = launch_wav_batch(c->stream, d_image, d_image, b, (int16_t *)d_pcm, (int16_t *)d_rows, &c->prof);
     if (rc) return rc;
-    if (!runs.empty()) HIPCHK(hipMemcpyAsync(d_image + runs_at, runs.data(), runs.size() * sizeof(WavRun), hipMemcpyHostToDevice, c->stream));
-    if (!iruns.empty()) HIPCHK(hipMemcpyAsync(d_image + iruns_at, iruns.data(), iruns.size() * sizeof(WavImportRun), hipMemcpyHostToDevice, c->stream));
-    if (trace_on()) fprintf(stderr, "mp3s:   encode_files: %zu streams through k_wav_gather, %zu through k_wav_import\n", runs.size(), iruns.size());
-    if (!rruns.empty()) {
-        HIPCHK(hipMemcpyAsync(d_image + sruns_at, sruns.data(), sruns.size() * sizeof(WavImportRun), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_image + rruns_at, rruns.data(), rruns.size() * sizeof(WavResampleRun), hipMemcpyHostToDevice, c->stream));
-        if (trace_on()) fprintf(stderr, "mp3s:   encode_files: %zu streams through k_wav_import and k_wav_resample\n", rruns.size());
-        if (launch_wav_import(c->stream, d_image, (const WavImportRun *)(d_image + sruns_at), (int)sruns.size(), (int)max_sframes, (int16_t *)d_rows) ||
-            launch_wav_resample(c->stream, (const uint32_t *)d_rows, (const WavResampleRun *)(d_image + rruns_at), (int)rruns.size(), (int)max_rframes, res_lds,
-                                (int16_t *)d_pcm, &c->prof))
-            return fail(MP3S_E_HIP, "resampling the WAV samples failed");
-    }
-    if (launch_wav_gather(c->stream, d_image, (const WavRun *)(d_image + runs_at), (int)runs.size(), (int)max_frames, (int16_t *)d_pcm) ||
-        launch_wav_import(c->stream, d_image, (const WavImportRun *)(d_image + iruns_at), (int)iruns.size(), (int)max_iframes, (int16_t *)d_pcm))
-        return fail(MP3S_E_HIP, "gathering the WAV samples failed");
-    *d_pcm_out = d_pcm; *n_all_out = n_all;
+    *d_pcm_out = d_pcm;
     return MP3S_OK;
 }
 
@@ -193,10 +134,9 @@ int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<i
 int encode_group(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, int samplerate, int kbps, mp3s_buf *top, mp3s_file *out)
 {
     std::vector<EncSeg> segs;
-    WavRecords rec;
+    WavBatch wb;
     void *d_pcm = nullptr;
-    int64_t n_all = 0;
-    int rc = wav_to_device(c, in, idx, segs, rec, &d_pcm, &n_all);
+    int rc = wav_to_device(c, in, idx, segs, wb, &d_pcm);
     if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
     std::unique_ptr<mp3s_buf> part(new mp3s_buf());
     int passes = 0;
@@ -216,7 +156,7 @@ int encode_group(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<in
 
 }  // namespace
 
-int encode_files_as(mp3s_ctx *c, bool import, int resample, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+int encode_files_as(mp3s_ctx *c, WavRead how, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
                     const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status)
 {
     if (!c || !wavs || !lens || !bitrate_kbps || !owner || !out || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");
@@ -231,7 +171,7 @@ int encode_files_as(mp3s_ctx *c, bool import, int resample, const uint8_t *const
         std::memset(&out[i], 0, sizeof out[i]);
         f.wav = wavs[i]; f.len = lens[i];
         f.hide = hide_bits ? hide_bits[i] : nullptr; f.n_hide = hide_bits ? n_hide[i] : 0;
-        st[(size_t)i] = wav_encode_plan(import, resample, f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.p);
+        st[(size_t)i] = wav_encode_plan(how, f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.p);
         if (st[(size_t)i]) { why[(size_t)i] = mp3s_last_error(); continue; }
         size_t g = 0;
         while (g < groups.size() && (groups[g].rate != f.p.samplerate || groups[g].kbps != bitrate_kbps[i])) g++;
@@ -265,7 +205,7 @@ int mp3s_encode_files(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *len
                       const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status)
 {
     if (!c || !wavs || !lens || !bitrate_kbps || !owner || !out || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");   // (before the context is looked at)
-    return encode_files_as(c, c->opt[MP3S_OPT_WAV_IMPORT] != 0, (int)c->opt[MP3S_OPT_WAV_RESAMPLE], wavs, lens, n_files, bitrate_kbps, hide_bits, n_hide, owner, out, status);
+    return encode_files_as(c, wav_read_of(c), wavs, lens, n_files, bitrate_kbps, hide_bits, n_hide, owner, out, status);
 }
 
 int mp3s_debug_wav_gather(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, int16_t *pcm, int64_t cap_frames, int64_t *n_frames)
@@ -273,22 +213,22 @@ int mp3s_debug_wav_gather(mp3s_ctx *c, const uint8_t *const *wavs, const size_t 
     if (!c || !wavs || !lens || !pcm || !n_frames || n_files <= 0) return fail(MP3S_E_ARG, "bad argument");
     std::vector<WavIn> in((size_t)n_files);
     std::vector<int> idx((size_t)n_files);
+    const WavRead how = wav_read_of(c);
     int64_t total = 0;
     for (int i = 0; i < n_files; i++) {
         WavIn &f = in[(size_t)i];
         f.wav = wavs[i]; f.len = lens[i]; f.hide = nullptr; f.n_hide = 0;
-        const int rc = wav_encode_plan(c->opt[MP3S_OPT_WAV_IMPORT] != 0, (int)c->opt[MP3S_OPT_WAV_RESAMPLE], f.wav, f.len, 128, nullptr, 0, &f.p);
+        const int rc = wav_encode_plan(how, f.wav, f.len, 128, nullptr, 0, &f.p);
         if (rc) return rc;
         idx[(size_t)i] = i; total += f.p.count;
     }
     *n_frames = total;
     if (total > cap_frames) return fail(MP3S_E_ARG, "%lld frames, room for %lld", (long long)total, (long long)cap_frames);
     std::vector<EncSeg> segs;
-    WavRecords rec;
+    WavBatch wb;
     void *d_pcm = nullptr;
-    int64_t n_all = 0;
-    int rc = wav_to_device(c, in, idx, segs, rec, &d_pcm, &n_all);
-    if (!rc) rc = mp3s_dev_download(c, pcm, d_pcm, (size_t)n_all * 4608);
+    int rc = wav_to_device(c, in, idx, segs, wb, &d_pcm);
+    if (!rc) rc = mp3s_dev_download(c, pcm, d_pcm, (size_t)wb.n_all * 4608);
     else (void)hipStreamSynchronize(c->stream);
     return rc;
 }

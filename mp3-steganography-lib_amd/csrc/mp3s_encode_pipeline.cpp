@@ -656,18 +656,15 @@ int mp3s_encode_file(mp3s_ctx *c, const uint8_t *wav, size_t len, int bitrate_kb
                      mp3s_buf **owner, mp3s_file *out)
 {
     if (!c || !wav || !owner || !out) return fail(MP3S_E_ARG, "null pointer");
-    if (c->opt[MP3S_OPT_WAV_IMPORT] || c->opt[MP3S_OPT_WAV_RESAMPLE]) {
+    if (wav_read_of(c).import) {
         // the import rules (mp3s_wav_import_info): the samples are converted on the device, so the file is a batch of one
         const int32_t kbps = bitrate_kbps, nh = n_hide;
         return mp3s_encode_files(c, &wav, &len, 1, &kbps, hide_bits || n_hide ? &hide_bits : nullptr, &nh, owner, out, nullptr);
     }
     mp3s_wav_info w;
-    int rc = mp3s_wav_parse(wav, len, bitrate_kbps, &w);
-    if (rc) return rc;
     int64_t count = 0;
-    const char *msg = "";
-    rc = wav_frame_count(w, &count, &msg);   // (mono, and a file that ends inside its last frame, are refused)
-    if (rc) return fail(rc, "%s", msg);
+    int rc = wav_encode_check(wav, len, bitrate_kbps, hide_bits, n_hide, &w, &count);   // (mono, and a file that ends inside its last frame, are refused)
+    if (rc) return rc;
     std::vector<int16_t> pcm((size_t)count * 2304);   // the data chunk may sit at an odd offset
     std::memcpy(pcm.data(), wav + w.data_offset, pcm.size() * 2);
     mp3s_encoded e;

@@ -5,12 +5,14 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -370,16 +372,53 @@ struct WavPlan {
     int L = 1, M = 1, T = 0;
     int64_t in_frames = 0 /* ceil(n_samples / 1152): what k_wav_import fills of the scratch */, n_out = 0;
 };
-int wav_encode_plan(bool import, int resample, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p);
-// the records of the two kernels for stream `k` of a batch whose image holds the file at `img`
-inline void wav_plan_record(const WavPlan &p, size_t img, uint32_t first_frame, std::vector<WavRun> &runs, std::vector<WavImportRun> &iruns)
-{
-    if (p.gather) runs.push_back({(uint64_t)img + (uint64_t)p.data_offset, first_frame, (uint32_t)p.count});
-    else iruns.push_back({(uint64_t)img + (uint64_t)p.data_offset, (uint64_t)p.n_samples, first_frame, (uint32_t)p.count, (uint32_t)p.format, (uint32_t)p.channels});
-}
-// mp3s_encode_files with the reader named by the caller (a pipe keeps the option's value of the day it was created)
-int encode_files_as(mp3s_ctx *c, bool import, int resample, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+// which reader a call or a pipe reads its WAV files with: made from the context's options in ONE place (a non-zero resample value
+// implies the import reader); a pipe keeps the value of the day it was created
+struct WavRead { bool import = false; int resample = 0; };
+WavRead wav_read_of(const mp3s_ctx *c);
+int wav_encode_plan(WavRead how, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p);
+// mp3s_encode_files with the reader named by the caller
+int encode_files_as(mp3s_ctx *c, WavRead how, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
                     const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status);
+
+// ---------------------------------------------------------------- files into a device image, WAV batches (wav_batch.cpp)
+// `bytes` from `src` to byte `dst` of a device image
+struct Upload { size_t dst; const uint8_t *src; size_t bytes; };
+// The copies that bring `files` (in image order) up: a long file goes from where it lies, short ones are laid into page-locked or
+// plain staging at their places in the image first, bytes as they are, and travel in runs -- one copy per run instead of one per
+// file (a copy from ordinary memory costs its thread 10 us and more whatever its size).  Whose staging it is and how it grows is the
+// caller's business: staging(extent) is asked once, when there is a short file, for room for bytes [0, extent) of the image.
+// false: it returned nullptr.  A copy u of a run has u.src == the staging + u.dst.
+bool plan_uploads(const std::vector<Upload> &files, const std::function<uint8_t *(size_t extent)> &staging, std::vector<Upload> &ups);
+
+// The layout of a batch of WAV files (one sampling rate and bitrate) on the device, for mp3s_encode_files and the pipe's encode jobs
+// alike: every file at a 16-byte aligned place of one byte image, the records of the kernels that make the batch's PCM buffer
+// [n_all][1152][2] int16 out of it -- k_wav_gather (runs), k_wav_import (iruns), and for the streams of MP3S_OPT_WAV_RESAMPLE
+// k_wav_import into a scratch of s_all frames at the source rate (sruns) and k_wav_resample from there (rruns) -- and the longest
+// stream per kernel (the grid).  Filled file by file in batch order; only the buffers are the caller's.
+struct WavBatch {
+    std::vector<Upload> files;           // per file: its place in the image, its bytes, how many of them the image takes
+    std::vector<uint32_t> first;         // ... and its first frame in the PCM buffer
+    std::vector<WavRun> runs;
+    std::vector<WavImportRun> iruns, sruns;
+    std::vector<WavResampleRun> rruns;
+    int64_t max_frames = 0, max_iframes = 0, max_sframes = 0, max_rframes = 0;
+    int64_t n_all = 0, s_all = 0;        // frames of the PCM buffer, of the resampler's scratch
+    size_t img = 0;                      // the image's end (kWavSlack readable bytes are needed behind it)
+    size_t res_lds = 0;                  // dynamic LDS of the k_wav_resample launch
+    // the record block [runs | iruns | sruns | rruns], every part 16-byte aligned: offsets from the start of the buffer that holds it
+    size_t o_runs = 0, o_iruns = 0, o_sruns = 0, o_rruns = 0, rec_end = 0;
+    struct Part { size_t at; const void *data; size_t bytes; };
+
+    void clear();                        // (the vectors keep their room: a job of a pipe fills the batch of the job before it)
+    // d_taps: the packed tap table of the stream's ratio on the device (a stream to resample only).  MP3S_OK, or the batch is too large
+    int add(const WavPlan &p, const uint8_t *wav, const uint32_t *d_taps);
+    void place_records(size_t base);     // the block at `base` (rounded up to 16) -> o_*, rec_end
+    std::array<Part, 4> parts() const;   // where each part of the block goes and what it is made of
+};
+// what makes the PCM buffer out of the image, queued on `stream`: import into the scratch d_rows and the resampler (when the batch
+// has such streams), the gather, the import.  d_records: the device buffer the batch's o_* count from
+int launch_wav_batch(hipStream_t stream, const uint8_t *d_image, const uint8_t *d_records, const WavBatch &b, int16_t *d_pcm, int16_t *d_rows, Profiler *prof);
 
 // ---------------------------------------------------------------- one file as chunks through the overlapped stages (run_file.cpp)
 constexpr int kRunFallback = 1;          // run_file: not for this path -- the caller takes the synchronous one (same bytes)

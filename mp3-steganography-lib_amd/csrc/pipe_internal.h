@@ -10,7 +10,6 @@
 #include "mp3s_internal.h"
 
 constexpr int kMaxFastFiles = 1024;
-constexpr size_t kDirectUpload = (size_t)256 << 10;   // a file at least this long goes up from the caller's memory in a copy of its own
 constexpr uint32_t kImageLead = 1024;                 // bytes in front of a chunk's first frame its reservoir pointers can name (511 + 8 x 38)
 constexpr int kRunDepth = 3;                          // chunks of one file in flight
 
@@ -34,8 +33,6 @@ struct Slot {
     hipEvent_t e_half = nullptr;         // the first of the bit packer's two launches is through (the last chunk of a one-file call)
     bool busy = false;
 };
-
-struct Upload { size_t dst; const uint8_t *src; size_t bytes; };   // into the slot's d_image
 
 // a chunk of one file (run_file): frames [w0, w0 + n_win) of the stream go to the device, of which the first `halo` only
 // rebuild decoder state (IMDCT overlap, synthesis fifo: < 1 frame, Frame.py:151-153, 81-92) and the next `lead` only
@@ -67,9 +64,7 @@ struct Job {
     // WAV -> MP3 (mp3s_pipe_submit_encode): files = the WAV images, msgs = per file {hide bits, their count}, enc_kbps per file
     bool encode = false, enc_hide = false;
     std::vector<int32_t> enc_kbps;
-    size_t o_runs = 0; int run_frames = 0;   // the gather's records inside the packed inputs, the longest stream's frames
-    size_t o_iruns = 0; int irun_frames = 0; // ... and k_wav_import's (a pipe created under MP3S_OPT_WAV_IMPORT)
-    std::vector<WavRun> wav_runs; std::vector<WavImportRun> wav_iruns;
+    WavBatch wav;                        // the files' places in the slot's d_wav, the kernels' records (inside the packed inputs) and grids
     enum State { QUEUED, ISSUED, SLOW_DONE } state = QUEUED;
     // fast path
     bool walked = false;                 // side info and main data are taken apart on the device (k_dec_parse)
@@ -151,8 +146,7 @@ struct mp3s_pipe {
     hipStream_t s_img = nullptr;         // the file pieces' own copy stream (the packed inputs of a chunk must not queue behind them)
     FileUp up;
     bool internal = false;               // the context's own (run_file): no worker threads, jobs issued by the caller
-    bool wav_import = false;             // MP3S_OPT_WAV_IMPORT of the context when the pipe was created: how its encode jobs read their WAV files
-    int wav_resample = 0;                // ... and MP3S_OPT_WAV_RESAMPLE (non-zero implies the import reader)
+    WavRead wav;                         // how its encode jobs read their WAV files: the context's options when the pipe was created
     size_t max_job_bytes = 0;
     size_t max_frames = 0;               // frames a job can have at most (the context's own pipe cuts its chunks by frames); 0: from the bytes, 96 per frame
     std::vector<Slot> slots;

@@ -90,7 +90,8 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
     uint8_t *fix = s.h_stage + s.o_in + s.in_cap;
     long n = 0;
     size_t img = 0;                  // bytes of d_image in use
-    size_t run_lo = 0, run_hi = 0;   // short files collected in h_image since the last flush
+    std::vector<Upload> lay;         // every file's place in the image
+    lay.reserve((size_t)nf);
     uint32_t md = 0;
     int max_p23 = 0;
     for (int i = 0; i < nf; i++) {
@@ -156,22 +157,17 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
             j.segs[i].tables_guess = j.guess[i].data(); j.segs[i].n_guess = (int)std::min<long>(w.tables_frames, got) * 4;
             j.segs[i].any_silent = w.any_silent ? 1 : 0;
         }
-        // the file's bytes: long files go up from where they lie, short ones are laid end to end in page-locked staging first
-        if (len >= kDirectUpload) {
-            if (run_hi > run_lo) { j.ups.push_back({run_lo, s.h_image + run_lo, run_hi - run_lo}); run_lo = run_hi = 0; }
-            j.ups.push_back({img, file, len});
-        } else {
-            if (!s.h_image && hipHostMalloc((void **)&s.h_image, s.image_cap, hipHostMallocDefault) != hipSuccess) { s.h_image = nullptr; return false; }
-            if (run_hi == run_lo) run_lo = img;
-            std::memcpy(s.h_image + img, file, len);
-            run_hi = img + len;
-        }
+        lay.push_back({img, file, len});
         img += len;
         n += got;
         md = w.md_cursor;
         if ((size_t)md + 64 > s.blob_cap) return false;
     }
-    if (run_hi > run_lo) j.ups.push_back({run_lo, s.h_image + run_lo, run_hi - run_lo});
+    // the files' bytes (plan_uploads): the short ones go through the slot's page-locked h_image, as large as the image, made on first need
+    if (!plan_uploads(lay, [&](size_t) {
+            if (!s.h_image && hipHostMalloc((void **)&s.h_image, s.image_cap, hipHostMallocDefault) != hipSuccess) s.h_image = nullptr;
+            return s.h_image;
+        }, j.ups)) return false;
     j.n_total = (int)n;
     j.L = EncLayout();
     j.max_p23 = max_p23;
@@ -622,63 +618,38 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
         if (hipMalloc((void **)&s.d_wav, cap) != hipSuccess) { (void)hipGetLastError(); s.d_wav = nullptr; return false; }
         s.wav_cap = cap;
     }
-    // the records of the two kernels (k_wav_import's only under MP3S_OPT_WAV_IMPORT): put behind the encoder's inputs below
-    std::vector<WavRun> &runs = j.wav_runs;
-    std::vector<WavImportRun> &iruns = j.wav_iruns;
-    runs.clear(); iruns.clear();
-    if ((size_t)nf * (P->wav_import ? sizeof(WavImportRun) : sizeof(WavRun)) > s.pack_cap - s.in_cap) return false;
-    long n = 0;
-    int64_t longest = 0, ilongest = 0;
-    size_t img = 0, run_lo = 0, run_hi = 0;
-    std::vector<Upload> lay;             // every file's place in the image
-    lay.reserve((size_t)nf);
+    // the batch (WavBatch): every file's place in the image and the kernels' records, put behind the encoder's inputs below
+    WavBatch &b = j.wav;
+    b.clear();
+    if ((size_t)nf * (P->wav.import ? sizeof(WavImportRun) : sizeof(WavRun)) > s.pack_cap - s.in_cap) return false;
     for (int i = 0; i < nf; i++) {
         const uint8_t *file = j.files[i].first;
         const uint8_t *hide = j.enc_hide ? j.msgs[i].first : nullptr;
         const int n_hide = j.enc_hide ? (int)j.msgs[i].second : 0;
         WavPlan w;
-        if (wav_encode_plan(P->wav_import, P->wav_resample, file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w)) return false;
+        if (wav_encode_plan(P->wav, file, j.files[i].second, j.enc_kbps[(size_t)i], hide, n_hide, &w)) return false;
         if (w.resample) return false;            // (a slot has no scratch at the source rate: mp3s_encode_files resamples the job's files)
-        const int64_t count = w.count;
         if (i == 0) { j.rate = w.samplerate; j.kbps = j.enc_kbps[0]; }
         else if (w.samplerate != j.rate || j.enc_kbps[(size_t)i] != j.kbps) return false;   // more than one device batch
-        if ((size_t)(n + count) > s.side_cap) return false;
-        const size_t need = w.need;              // (inside the file; mono and 8-bit files need less of the image per frame than 4 608 bytes, 24/32-bit stereo more)
-        img = (img + 15) & ~(size_t)15;
-        if (img + need + kWavSlack > s.wav_cap) return false;
-        wav_plan_record(w, img, (uint32_t)n, runs, iruns);
-        j.stream_first[(size_t)i] = (uint32_t)n;
-        j.segs[(size_t)i].n_frames = (int)count; j.segs[(size_t)i].hide = hide; j.segs[(size_t)i].n_hide = n_hide;
-        lay.push_back({img, file, need});
-        img += need;
-        n += (long)count;
-        if (w.gather) longest = std::max(longest, count);
-        else ilongest = std::max(ilongest, count);
+        if ((size_t)(b.n_all + w.count) > s.side_cap) return false;
+        // (what a file needs of the image lies inside the file; mono and 8-bit files need less per frame than 4 608 bytes, 24/32-bit stereo more)
+        if (((b.img + 15) & ~(size_t)15) + w.need + kWavSlack > s.wav_cap) return false;
+        if (b.add(w, file, nullptr)) return false;
+        j.stream_first[(size_t)i] = b.first.back();
+        j.segs[(size_t)i].n_frames = (int)w.count; j.segs[(size_t)i].hide = hide; j.segs[(size_t)i].n_hide = n_hide;
     }
-    // the files' bytes, as they are: long files go up from where they lie, short ones (below kDirectUpload) are laid end to end in
-    // page-locked staging first and travel in runs.  The staging is as large as the short files of the jobs seen so far asked for
-    // (+ a quarter), not as large as the image: the slot has no job in flight when it grows.
-    size_t staged = 0;
-    for (const Upload &u : lay) if (u.bytes < kDirectUpload) staged = u.dst + u.bytes;
-    if (staged > s.h_wav_cap) {
-        if (s.h_wav) (void)hipHostFree(s.h_wav);
-        s.h_wav = nullptr; s.h_wav_cap = 0;
-        const size_t cap = std::min(s.wav_cap, std::max<size_t>(staged + staged / 4, (size_t)1 << 20));
-        if (hipHostMalloc((void **)&s.h_wav, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s.h_wav = nullptr; return false; }
-        s.h_wav_cap = cap;
-    }
-    for (const Upload &u : lay) {
-        if (u.bytes >= kDirectUpload) {
-            if (run_hi > run_lo) { j.ups.push_back({run_lo, s.h_wav + run_lo, run_hi - run_lo}); run_lo = run_hi = 0; }
-            j.ups.push_back(u);
-        } else {
-            if (run_hi == run_lo) run_lo = u.dst;
-            std::memcpy(s.h_wav + u.dst, u.src, u.bytes);
-            run_hi = u.dst + u.bytes;
-        }
-    }
-    if (run_hi > run_lo) j.ups.push_back({run_lo, s.h_wav + run_lo, run_hi - run_lo});
-    j.n_total = (int)n; j.run_frames = (int)longest; j.irun_frames = (int)ilongest;
+    // the files' bytes (plan_uploads): the short ones go through the slot's page-locked h_wav, as large as the short files of the jobs
+    // seen so far asked for (+ a quarter), not as large as the image: the slot has no job in flight when it grows.
+    if (!plan_uploads(b.files, [&](size_t extent) {
+            if (extent <= s.h_wav_cap) return s.h_wav;
+            if (s.h_wav) (void)hipHostFree(s.h_wav);
+            s.h_wav = nullptr; s.h_wav_cap = 0;
+            const size_t cap = std::min(s.wav_cap, std::max<size_t>(extent + extent / 4, (size_t)1 << 20));
+            if (hipHostMalloc((void **)&s.h_wav, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s.h_wav = nullptr; return s.h_wav; }
+            s.h_wav_cap = cap;
+            return s.h_wav;
+        }, j.ups)) return false;
+    j.n_total = (int)b.n_all;
     j.L = EncLayout();
     j.o_small = s.o_in;
     const size_t small_room = (small_bytes(nf) + 15) & ~(size_t)15;
@@ -690,13 +661,12 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
     j.res.reset(new mp3s_buf());
     if (!j.res->big[0].reserve(j.L.mp3_bytes) || !j.res->big[2].reserve(small_bytes(j.L.n_segs))) return false;
     j.res->mp3 = j.res->big[0].data();
-    j.o_runs = (j.o_encblk + j.L.bytes + 15) & ~(size_t)15;
-    j.o_iruns = j.o_runs + ((runs.size() * sizeof(WavRun) + 15) & ~(size_t)15);
-    j.pack_end = j.o_iruns + iruns.size() * sizeof(WavImportRun);
+    b.place_records(j.o_encblk + j.L.bytes);
+    j.pack_end = b.rec_end;
     if (j.pack_end > s.o_in + s.pack_cap) return false;
-    if (!runs.empty()) std::memcpy(s.h_stage + j.o_runs, runs.data(), runs.size() * sizeof(WavRun));
-    if (!iruns.empty()) std::memcpy(s.h_stage + j.o_iruns, iruns.data(), iruns.size() * sizeof(WavImportRun));
-    return j.pack_end <= s.o_in + s.pack_cap;
+    for (const WavBatch::Part &p : b.parts())
+        if (p.bytes) std::memcpy(s.h_stage + p.at, p.data, p.bytes);
+    return true;
 }
 
 // ... and everything it does on the device, queued on the streams: images and inputs on the copy-up stream, the gather on the
@@ -725,9 +695,8 @@ int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
         HIPCHK(hipEventRecord(s.e_in, c->stream));
         HIPCHK(hipStreamWaitEvent(P->s_huff, s.e_in, 0));
     } else if (P->enc_used[set]) HIPCHK(hipStreamWaitEvent(P->s_huff, P->e_enc[set], 0));
-    if (launch_wav_gather(P->s_huff, s.d_wav, (const WavRun *)(s.d_stage + j.o_runs), (int)j.wav_runs.size(), j.run_frames, (int16_t *)d_keep) ||
-        launch_wav_import(P->s_huff, s.d_wav, (const WavImportRun *)(s.d_stage + j.o_iruns), (int)j.wav_iruns.size(), j.irun_frames, (int16_t *)d_keep))
-        return fail(MP3S_E_HIP, "gathering the WAV samples failed");
+    const int rw = launch_wav_batch(P->s_huff, s.d_wav, s.d_stage, j.wav, (int16_t *)d_keep, nullptr, nullptr);   // (no stream to resample, no scratch: prepare_encode)
+    if (rw) return rw;
     HIPCHK(hipEventRecord(s.e_huff, P->s_huff));
     HIPCHK(hipStreamWaitEvent(c->stream, s.e_huff, 0));
     const int units = L.units;
@@ -832,7 +801,7 @@ void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held
     if (j.encode) {
         std::vector<int32_t> nh(nf);
         for (int i = 0; i < nf; i++) { mp[i] = j.msgs[i].first; nh[i] = (int32_t)j.msgs[i].second; }
-        j.slow_rc = encode_files_as(P->c, P->wav_import, P->wav_resample, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
+        j.slow_rc = encode_files_as(P->c, P->wav, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
                                       &j.slow_owner, j.slow_out.data(), j.slow_st.data());
         j.slow_err = mp3s_last_error();
     } else if (j.block) {
@@ -1005,8 +974,7 @@ int pipe_create(mp3s_ctx *c, int depth, size_t max_job_bytes, int scan_threads, 
     HIPCHK(hipSetDevice(c->device));
     std::unique_ptr<mp3s_pipe> P(new mp3s_pipe());
     P->c = c; P->depth = depth; P->internal = internal; P->max_job_bytes = max_job_bytes;
-    P->wav_resample = (int)c->opt[MP3S_OPT_WAV_RESAMPLE];
-    P->wav_import = c->opt[MP3S_OPT_WAV_IMPORT] != 0 || P->wav_resample != 0;
+    P->wav = wav_read_of(c);
     auto destroy = [&](int code, const char *what) {
         for (auto &s : P->slots) free_slot(s);                // (the streams belong to the device: pick_lanes)
         for (hipEvent_t e : P->e_dec) if (e) (void)hipEventDestroy(e);
