@@ -510,6 +510,21 @@ int mp3s_parse_frames_dev(mp3s_ctx *ctx, const uint8_t *d_image, uint32_t image_
 /* replaces: __get_frame_huffman_tables + bit_from_huffman_tables -- reference decoder/Frame.py:676-685, decoder/util.py:67-81.
  * carry[4]: the third table index each (channel, granule) was left with by the frames in front (zeros at a stream's start), updated */
 int mp3s_stego_bits(const uint64_t *tsel, int64_t n_frames, int nch, uint8_t carry[4], mp3s_buf **owner, const uint8_t **bits, size_t *n_bits);
+/* The stego bits of a batch of walked streams in ONE launch (k_reveal: one workgroup per stream, one frame per thread, the frames of
+ * a stream in tiles of MP3S_REVEAL_TILE) -- the reveal of a file needs nothing else of it.
+ * replaces: __get_frame_huffman_tables + bit_from_huffman_tables for every frame of every stream -- reference decoder/Frame.py:676-685,
+ *           decoder/util.py:67-81, with the index a window-switching granule keeps from the granule before it resolved on
+ *           the device (a scan along the stream that restarts at every stream); no main data is read.
+ * d_image / image_base / d_refs / d_streams as for mp3s_parse_frames_dev (base, end, first_frame, n_frames of a stream reference mean
+ * what they mean there; d_refs[f].stream is the stream's index in d_streams), n_streams <= 65 535.  Stream s gets its bits packed
+ * eight to a byte, MSB first, the last byte zero-padded, from byte d_out_off[s] of d_packed (a multiple of 4; whole dwords are written:
+ * room for 4 * ceil(12 * n_frames / 32) bytes there), their count in d_n_bits[s] and d_status[s] = 0, or MP3S_RV_BAD_REF when one of
+ * its frame references names another stream or a place outside [base, end): nothing is read there and the bits are not to be used. */
+#define MP3S_REVEAL_TILE 256
+#define MP3S_RV_BAD_REF 1
+int mp3s_reveal_bits_dev(mp3s_ctx *ctx, const uint8_t *d_image, uint32_t image_base, const mp3s_frame_ref *d_refs,
+                         const mp3s_stream_ref *d_streams, int n_streams, const uint32_t *d_out_off, uint8_t *d_packed,
+                         int32_t *d_n_bits, int32_t *d_status);
 
 /* replaces: __format_bitstream for every frame of the batch -- reference encoder/MP3_Encoder.py:1097-1145 (stuffing),
  * 1266-1547; one workgroup per frame, one wavefront per granule*channel, code lengths prefix-summed across lanes.
@@ -837,6 +852,24 @@ int mp3s_hide_message_chunked(mp3s_ctx *ctx, const uint8_t *mp3, size_t len, con
  * counts are caught here too, Huffman-level damage is not) raises there and yields a message here.  The Python facade is
  * unaffected (Steganography.reveal_massage goes through mp3s_decode_file). */
 int mp3s_reveal_message(const uint8_t *mp3, size_t len, mp3s_buf **owner, mp3s_file *out);
+/* replaces: a loop of Steganography.reveal_massage over a list of files -- the counterpart of mp3s_hide_messages.  The files are
+ * walked from header to header on the context's scan threads (MP3S_OPT_SCAN_THREADS); the ones the walk calls regular (mp3s_walk_stream)
+ * go through the device as ONE batch whatever their sampling rates, bitrates and channel counts are -- nothing in the kernel depends on
+ * them, unlike hide and encode: one upload of the file images as the caller holds them, k_reveal (mp3s_reveal_bits_dev), one download
+ * of the packed bits and their counts.  (A list of more than 65 535 such files, or of 4 GiB of them, takes a launch per part: a frame
+ * reference names its stream in 16 bits and its place in 32.)  Every other file -- irregular streams, files without a sync, empty
+ * files -- is served by the byte-level scan on the host, into the same out[i].
+ * out[i] of every file mp3s_scan_stream accepts is what mp3s_reveal_message returns for that file: data / len = mp3s_message_reveal
+ * of the scan's bits, n_bits, bits (0/1 bytes, expanded on the host from the packed result), kbps, sampling_rate, channels, n_frames.
+ * status[i] = MP3S_OK or the code mp3s_scan_stream fails with for file i (its out[i] is zeroed; MP3S_E_ARG for a null file); with
+ * status == NULL the first such code fails the whole call -- the rule of mp3s_hide_messages.
+ * The leniency of mp3s_reveal_message holds here as well: no main data is decoded, so a file whose Huffman data is damaged but whose
+ * framing is sound yields its message, where the reference (and the facade, through mp3s_decode_file) refuses it. */
+int mp3s_reveal_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, mp3s_buf **owner, mp3s_file *out,
+                         int32_t *status);
+/* test aid: mp3s_reveal_messages with at most max_streams (1 .. 65 535) streams to a launch -- a short list in several launches */
+int mp3s_debug_reveal_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int max_streams,
+                               mp3s_buf **owner, mp3s_file *out, int32_t *status);
 
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference

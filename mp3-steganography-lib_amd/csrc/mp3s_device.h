@@ -109,6 +109,16 @@ constexpr int kParseInherits = 1, kParseMismatch = 2;
 int launch_parse(hipStream_t stream, const uint8_t *d_image, uint32_t image_base, const FrameRef *d_refs, const StreamRef *d_streams, int n_frames,
                  uint32_t md_base, mp3s_frame_side *d_side, mp3s_frame_hdr *d_hdr, uint8_t *d_blob, uint64_t *d_tsel, int32_t *d_status);
 
+// the stego bits of a batch of walked streams (k_reveal.hpp): per stream its bits packed eight to a byte, MSB first, from byte
+// d_out_off[s] (a multiple of 4) of d_packed -- room for reveal_packed_bytes(n_frames) there --, their count and a status word
+// (0, or kRevealBadRef: a frame reference of the stream names another stream or a place outside it; its bits are not to be used)
+constexpr int kRevealTile = MP3S_REVEAL_TILE; // frames a workgroup takes at a time
+constexpr int kRevealBadRef = MP3S_RV_BAD_REF;
+constexpr int kRevealMaxStreams = 65535;     // of one launch
+inline size_t reveal_packed_bytes(uint64_t n_frames) { return (size_t)((n_frames * 12 + 31) / 32 * 4); }   // whole dwords are written
+int launch_reveal(hipStream_t stream, const uint8_t *d_image, uint32_t image_base, const FrameRef *d_refs, const StreamRef *d_streams, int n_streams,
+                  const uint32_t *d_out_off, uint8_t *d_packed, int32_t *d_n_bits, int32_t *d_status);
+
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes

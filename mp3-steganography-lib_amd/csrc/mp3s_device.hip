@@ -22,6 +22,7 @@ __constant__ DevTables c_tab;
 #include "k_rate.hpp"
 #include "k_huffman.hpp"
 #include "k_parse.hpp"
+#include "k_reveal.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
@@ -377,6 +378,22 @@ int launch_parse(hipStream_t stream, const uint8_t *d_image, uint32_t image_base
     hipLaunchKernelGGL(k_dec_parse, dim3((n_frames + PARSE_WAVES - 1) / PARSE_WAVES), dim3(PARSE_WAVES * 64), 0, stream, d_image, image_base,
                        reinterpret_cast<const ParseFrameRef *>(d_refs), reinterpret_cast<const ParseStreamRef *>(d_streams), n_frames, md_base, d_side,
                        d_hdr, d_blob, d_tsel, d_status);
+    return (int)hipGetLastError();
+}
+
+static_assert(REVEAL_TILE == kRevealTile && REVEAL_BAD_REF == kRevealBadRef, "k_reveal's constants out of sync with mp3s_device.h");
+
+// k_reveal: one workgroup per stream (the grid's x: at most 65 535 streams a launch, what FrameRef::stream can name)
+int launch_reveal(hipStream_t stream, const uint8_t *d_image, uint32_t image_base, const FrameRef *d_refs, const StreamRef *d_streams, int n_streams,
+                  const uint32_t *d_out_off, uint8_t *d_packed, int32_t *d_n_bits, int32_t *d_status)
+{
+    if (n_streams <= 0) return 0;
+    if (n_streams > kRevealMaxStreams) return (int)hipErrorInvalidValue;
+    const HostTables &HT = host_tables();
+    uint32_t h0_mask = 0;
+    for (int t = 0; t < 32; t++) if (HT.in_h0[t]) h0_mask |= 1u << t;
+    hipLaunchKernelGGL(k_reveal, dim3((unsigned)n_streams), dim3(REVEAL_TILE), 0, stream, d_image, image_base, reinterpret_cast<const ParseFrameRef *>(d_refs),
+                       reinterpret_cast<const ParseStreamRef *>(d_streams), d_out_off, h0_mask, d_packed, d_n_bits, d_status);
     return (int)hipGetLastError();
 }
 

@@ -225,6 +225,7 @@ struct mp3s_buf {
     std::vector<uint8_t> bits;
     std::vector<int32_t> scfsi;
     std::vector<std::unique_ptr<mp3s_buf>> parts;   // results of the batches of a multi-file call
+    std::vector<std::vector<uint8_t>> lists;        // mp3s_reveal_messages: per file its text and its stego bits
     // encoder results: MP3 bytes and GrInfo records land in page-locked blocks and are handed out from there
     PinnedBlock big[3];              // MP3 bytes, GrInfo records, the small results (verdict, per-stream chain ends)
     uint8_t *mp3 = nullptr;

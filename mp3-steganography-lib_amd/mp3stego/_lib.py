@@ -191,7 +191,12 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_hide_message", "mp3s_clear_file", "mp3s_hide_message_fd", "mp3s_clear_file_fd", "mp3s_decode_file_fd", "mp3s_hide_messages", "mp3s_reencode_block", "mp3s_reveal_message",
            "mp3s_pipe_create", "mp3s_pipe_destroy", "mp3s_pipe_submit", "mp3s_pipe_submit_decode", "mp3s_pipe_collect", "mp3s_pipe_get_stats",
            "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
-           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps"]
+           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps",
+           "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages"]
+
+REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
+RV_BAD_REF = 1
+_EMPTY = C.c_char()          # where an empty file's pointer points (a null pointer is an argument error)
 
 _lib = None
 _lock = threading.Lock()
@@ -297,6 +302,9 @@ def lib():
         L.mp3s_walk_stream.argtypes = [vp, sz, pvp, C.POINTER(Walked)]
         L.mp3s_parse_frames_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, i32, C.c_uint32, vp, vp, vp, vp, vp]
         L.mp3s_stego_bits.argtypes = [vp, i64, i32, vp, pvp, pvp, psz]
+        L.mp3s_reveal_bits_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, i32, vp, vp, vp, vp]
+        L.mp3s_reveal_messages.argtypes = [vp, vp, vp, i32, pvp, vp, vp]
+        L.mp3s_debug_reveal_messages.argtypes = [vp, vp, vp, i32, i32, pvp, vp, vp]
         L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
@@ -461,6 +469,24 @@ class Context:
             for p in (d_img, d_refs, d_streams, d_side, d_hdr, d_blob, d_tsel, d_st):
                 if p is not None:
                     self.free(p)
+
+    def reveal_bits(self, data: bytes, walked):
+        """the stego bits of a walked stream on the device (mp3s_reveal_bits_dev, one stream): -> (packed uint8 array: eight bits
+        to a byte, MSB first, the last byte zero-padded; n_bits)"""
+        n = walked["n_frames"]
+        room = (12 * n + 31) // 32 * 4
+        d_img = self.to_device(np.frombuffer(data, dtype=np.uint8))
+        d_refs, d_streams = self.to_device(walked["refs"]), self.to_device(walked["stream"])
+        d_off, d_packed, d_out = self.to_device(np.zeros(1, dtype=np.uint32)), self.alloc(room), self.alloc(8)
+        try:
+            check(lib().mp3s_reveal_bits_dev(self.handle, d_img, 0, d_refs, d_streams, 1, d_off, d_packed, d_out, C.c_void_p(d_out.value + 4)))
+            n_bits, status = (int(v) for v in self.download(d_out, np.int32, (2,)))
+            if status:
+                raise Mp3sError(E_MALFORMED, f"k_reveal refused the stream's frame references (status {status})")
+            return self.download(d_packed, np.uint8, (room,))[:(n_bits + 7) // 8].copy(), n_bits
+        finally:
+            for p in (d_img, d_refs, d_streams, d_off, d_packed, d_out):
+                self.free(p)
 
     def wait_for(self, other):
         """work submitted to this context from now on starts after everything submitted to `other` so far"""
@@ -801,6 +827,35 @@ class Context:
                     res.append({"data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
                                 "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
                                 "hide_offset": f.hide_offset})
+            return res
+        finally:
+            lib().mp3s_buf_free(owner)
+
+    def reveal_messages(self, mp3s, _max_streams=None):
+        """reveal_message over a list of files as ONE device batch (mp3s_reveal_messages): the files the walk calls regular through
+        k_reveal, the others through the host scan.  Returns one entry per file: a dict with the keys of reveal_message(), or the
+        Mp3sError that file's scan raises.  _max_streams (test aid): at most that many streams to a launch."""
+        n = len(mp3s)
+        if n == 0:
+            return []
+        bufs = [np.frombuffer(m, dtype=np.uint8) for m in mp3s]
+        files = (C.c_void_p * n)(*[b.ctypes.data if len(b) else C.addressof(_EMPTY) for b in bufs])
+        lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+        out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
+        if _max_streams is None:
+            check(lib().mp3s_reveal_messages(self.handle, files, lens, n, C.byref(owner), out, status))
+        else:
+            check(lib().mp3s_debug_reveal_messages(self.handle, files, lens, n, int(_max_streams), C.byref(owner), out, status))
+        try:
+            res = []
+            for i in range(n):
+                f = out[i]
+                if status[i]:
+                    res.append(Mp3sError(status[i], f"file {i}"))
+                else:
+                    res.append({"data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+                                "channels": f.channels, "n_frames": f.n_frames, "too_long": False, "hide_offset": 0,
+                                "bits": _view(f.bits, np.uint8, (f.n_bits,))})
             return res
         finally:
             lib().mp3s_buf_free(owner)
