@@ -795,7 +795,8 @@ int mp3s_clear_file_fd(mp3s_ctx *ctx, const uint8_t *mp3, size_t len, int fd, mp
  * about what one long file of the same total length costs.  msgs[i] = UTF-8 message of file i, NULL = clear that file
  * (msgs itself NULL = clear all).  out[i] is byte-identical to what mp3s_hide_message / mp3s_clear_file give for file i
  * alone.  status[i] = MP3S_OK or the code file i alone would have failed with (its out[i] is zeroed); with status ==
- * NULL the first such code fails the whole call. */
+ * NULL the first such code fails the whole call.  Either way mp3s_last_error() holds the text of the FIRST failing file.
+ * This is the rule of every call that takes a list of files. */
 int mp3s_hide_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, const uint8_t *const *msgs,
                        const size_t *msg_lens, mp3s_buf **owner, mp3s_file *out, int32_t *status);
 /* replaces: a loop of Encoder(...).encode() over a list of WAV files -- reference encoder/encoder.py:21-58 (WAV_Reader.py:30-111 for

@@ -69,18 +69,16 @@ int mp3s_debug_parse_scanned_frame(const void *frame_side, const uint8_t *blob, 
 int mp3s_debug_walk_rate(const uint8_t *file, size_t len, double seconds, double *frames_per_s, int64_t *frames_per_pass)
 {
     if (!file || !frames_per_s || seconds <= 0) return fail(MP3S_E_ARG, "bad argument");
-    std::vector<FrameRef> refs(len / 24 + 16);
-    std::vector<uint8_t> tables(refs.size() * 4);
+    std::vector<FrameRef> refs;
+    std::vector<uint8_t> tables;
     const double t0 = now_ms();
     int64_t frames = 0, per_pass = 0;
     double t = t0;
     do {
         FrameWalker w;
-        if (w.open(file, len)) return fail(MP3S_E_MALFORMED, "malformed or unsupported MP3 stream");
-        w.tables_wanted = 1000;
-        long n = 0;
-        while (!w.ended && !w.irregular && (size_t)n < refs.size()) n += w.next(refs.data() + n, (long)refs.size() - n, tables.data() + (size_t)n * 4, 0, 0);
+        const long n = std::max(0L, walk_whole(file, len, refs, w, &tables, 1000));   // (a stream without a frame is walked too)
         if (w.irregular) return fail(MP3S_E_UNSUPPORTED, "not a stream the walk takes");
+        if (!w.ended) return fail(MP3S_E_MALFORMED, "malformed or unsupported MP3 stream");
         frames += n; per_pass = n;
         t = now_ms();
     } while (t - t0 < seconds * 1e3);
@@ -680,19 +678,12 @@ int mp3s_walk_stream(const uint8_t *file, size_t len, mp3s_buf **owner, mp3s_wal
     std::memset(out, 0, sizeof *out);
     std::unique_ptr<mp3s_buf> b(new mp3s_buf());
     FrameWalker w;
-    const int rc = w.open(file, len);
-    if (rc) return fail(rc, "malformed or unsupported MP3 stream");
-    // refs and table counts live in the generic payload: [refs (16 bytes each) | tables (4 bytes each)]
-    const size_t cap = len / 24 + 16;          // no Layer III frame is shorter than 24 bytes
-    b->bytes.resize(cap * 20);
-    FrameRef *refs = reinterpret_cast<FrameRef *>(b->bytes.data());
-    uint8_t *tables = b->bytes.data() + cap * 16;
-    std::memset(tables, 0, cap * 4);
-    w.tables_wanted = 0x7fffffffffffffffL;
-    long n = 0;
-    while (!w.ended && !w.irregular && (size_t)n < cap) n += w.next(refs + n, (long)(cap - (size_t)n), tables + (size_t)n * 4, 0, 0);
+    const long n = std::max(0L, walk_whole(file, len, b->refs, w, &b->bits, 0x7fffffffffffffffL));   // (no frame: regular, and empty)
+    if (!w.irregular && !w.ended) return fail(w.error, "malformed or unsupported MP3 stream");
+    const FrameRef *refs = b->refs.data();
+    const uint8_t *tables = b->bits.data();
     *owner = b.release();
-    if (w.irregular || !w.ended) return MP3S_OK;   // regular = 0
+    if (w.irregular) return MP3S_OK;   // regular = 0
     out->regular = 1;
     out->n_frames = (int32_t)n; out->nch = w.nch; out->sampling_rate = w.sampling_rate; out->bit_rate = w.bit_rate;
     out->dup_last_frame = w.dup_last ? 1 : 0; out->max_part2_3_length = w.max_p23; out->any_silent = w.any_silent ? 1 : 0;

@@ -270,21 +270,24 @@ static int decode_streams_impl(mp3s_ctx *c, const uint8_t *const *files, const s
     m.parsed.resize(n_files); m.scanned.resize(n_files); m.pcm.assign(n_files, nullptr); m.files.resize(n_files);
     std::vector<int> group[3];
     size_t total = 0;
-    std::vector<int> frc(n_files, MP3S_OK);
+    FileStatus fs(n_files);
+    std::vector<int32_t> &frc = fs.st;
+    // (with status == NULL a file the front end refuses fails the call here, before any device work)
     for (int i = 0; i < n_files; i++) {
         if (!files[i]) {
-            if (!status) { delete b; return fail(MP3S_E_ARG, "file %d is null", i); }
-            frc[i] = MP3S_E_ARG;
+            fs.set(i, fail(MP3S_E_ARG, "file %d is null", i));
+            if (!status) { delete b; return frc[i]; }
             continue;
         }
         m.files[i] = {files[i], lens[i]};
         total += lens[i];
     }
     if (n_files == 1) m.scanned[0] = std::move(c->spare_scan);   // its capacity: no fresh pages for the blob of a long file
-    parallel_files(n_files, total, [&](int i) { if (!frc[i]) frc[i] = front_end(m, i); });
+    parallel_files(file_workers(n_files, total, host_threads16()), n_files, [&](int, int i) { if (!frc[i]) frc[i] = front_end(m, i); });
     for (int i = 0; i < n_files; i++) {
         if (frc[i]) {
-            if (!status) { delete b; return fail(frc[i], "file %d: malformed or unsupported MP3 stream", i); }
+            if (files[i]) fs.set(i, fail(frc[i], "file %d: malformed or unsupported MP3 stream", i));   // (a null file has its text)
+            if (!status) { delete b; return frc[i]; }
             m.parsed[i] = ParsedStream();        // nothing of it goes into a batch
             continue;
         }
@@ -295,17 +298,17 @@ static int decode_streams_impl(mp3s_ctx *c, const uint8_t *const *files, const s
             int rc = decode_group(c, m, group[nch], nch, out_format);
             if (rc && status && group[nch].size() > 1) {
                 // one stream spoils its batch (main data the host parser rejects): each file on its own, to name it.
-                // (The arena of this channel count is re-used per file, so the good files are decoded a second time as a
-                // batch once the bad ones are known.)
+                // Not run_groups: the arena of this channel count is re-used per file, so the good files are decoded a second
+                // time as a batch once the bad ones are known.
                 std::vector<int> good;
                 for (int i : group[nch]) {
-                    const int r1 = decode_group(c, m, std::vector<int>{i}, nch, out_format);
-                    if (r1) { frc[i] = r1; m.parsed[i] = ParsedStream(); m.pcm[i] = nullptr; }
+                    fs.set(i, decode_group(c, m, std::vector<int>{i}, nch, out_format));
+                    if (frc[i]) { m.parsed[i] = ParsedStream(); m.pcm[i] = nullptr; }
                     else good.push_back(i);
                 }
                 rc = good.empty() ? MP3S_OK : decode_group(c, m, good, nch, out_format);
             } else if (rc && status) {
-                frc[group[nch][0]] = rc; m.parsed[group[nch][0]] = ParsedStream(); m.pcm[group[nch][0]] = nullptr;
+                fs.set(group[nch][0], rc); m.parsed[group[nch][0]] = ParsedStream(); m.pcm[group[nch][0]] = nullptr;
                 rc = MP3S_OK;
             }
             if (rc) { delete b; return rc; }
@@ -313,7 +316,6 @@ static int decode_streams_impl(mp3s_ctx *c, const uint8_t *const *files, const s
     for (int i = 0; i < n_files; i++) {
         const ParsedStream &p = m.parsed[i];
         std::memset(&out[i], 0, sizeof out[i]);
-        if (status) status[i] = frc[i];
         if (frc[i]) continue;
         out[i].n_frames = p.n_frames; out[i].nch = p.nch; out[i].sampling_rate = p.sampling_rate; out[i].bit_rate = p.bit_rate;
         out[i].n_bits = (int32_t)p.bits.size(); out[i].n_rows = (int64_t)1152 * (p.n_frames + p.dup_last_frame);
@@ -321,6 +323,7 @@ static int decode_streams_impl(mp3s_ctx *c, const uint8_t *const *files, const s
     }
     if (n_files == 1) c->spare_scan = std::move(m.scanned[0]);   // (the result refers to the parse and the PCM only)
     m.files.clear();   // borrowed
+    finish_files(fs, status);   // (with status == NULL every failure has failed the call above)
     *owner = b;
     return MP3S_OK;
 }

@@ -142,14 +142,7 @@ int encode_group(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<in
     int passes = 0;
     rc = encode_batch(c, nullptr, (const int16_t *)d_pcm, segs, samplerate, kbps, part.get(), &passes, false);
     if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }     // (the records are the source of copies that may still be in flight)
-    for (size_t k = 0; k < idx.size(); k++) {
-        mp3s_file &o = out[idx[k]];
-        std::memset(&o, 0, sizeof o);
-        o.data = part->mp3 + segs[k].mp3_off; o.len = segs[k].mp3_len;
-        o.kbps = kbps; o.sampling_rate = samplerate; o.channels = 2; o.n_frames = segs[k].n_frames;
-        o.hide_offset = segs[k].hide_offset;
-        o.too_long = segs[k].hide_offset < (int64_t)segs[k].n_hide - 1 ? 1 : 0;
-    }
+    for (size_t k = 0; k < idx.size(); k++) file_from_seg(segs[k], part->mp3, kbps, samplerate, segs[k].hide_offset, &out[idx[k]]);
     top->parts.push_back(std::move(part));
     return MP3S_OK;
 }
@@ -162,38 +155,22 @@ int encode_files_as(mp3s_ctx *c, WavRead how, const uint8_t *const *wavs, const 
     if (!c || !wavs || !lens || !bitrate_kbps || !owner || !out || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");
     std::unique_ptr<mp3s_buf> top(new mp3s_buf());
     std::vector<WavIn> in((size_t)n_files);
-    std::vector<int32_t> st((size_t)n_files, MP3S_OK);
-    std::vector<std::string> why((size_t)n_files);
-    struct Group { int rate, kbps; std::vector<int> idx; };
-    std::vector<Group> groups;
+    FileStatus fs(n_files);
+    FileGroups groups;                       // by (sampling rate, kbps)
     for (int i = 0; i < n_files; i++) {
         WavIn &f = in[(size_t)i];
         std::memset(&out[i], 0, sizeof out[i]);
         f.wav = wavs[i]; f.len = lens[i];
         f.hide = hide_bits ? hide_bits[i] : nullptr; f.n_hide = hide_bits ? n_hide[i] : 0;
-        st[(size_t)i] = wav_encode_plan(how, f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.p);
-        if (st[(size_t)i]) { why[(size_t)i] = mp3s_last_error(); continue; }
-        size_t g = 0;
-        while (g < groups.size() && (groups[g].rate != f.p.samplerate || groups[g].kbps != bitrate_kbps[i])) g++;
-        if (g == groups.size()) groups.push_back({f.p.samplerate, bitrate_kbps[i], {}});
-        groups[g].idx.push_back(i);
+        fs.set(i, wav_encode_plan(how, f.wav, f.len, bitrate_kbps[i], f.hide, f.n_hide, &f.p));
+        if (!fs.st[(size_t)i]) groups.add(f.p.samplerate, bitrate_kbps[i], i);
     }
-    for (const Group &g : groups) {
-        const int rc = encode_group(c, in, g.idx, g.rate, g.kbps, top.get(), out);
-        if (!rc) continue;
-        (void)hipStreamSynchronize(c->stream);   // (copies of the failed batch may still read the callers' bytes and the staging)
-        // one file spoils its batch (a quantizer step that leaves the table ...): each file on its own, to name it
-        std::string first = mp3s_last_error();
-        for (int i : g.idx) {
-            st[(size_t)i] = g.idx.size() == 1 ? rc : encode_group(c, in, std::vector<int>{i}, g.rate, g.kbps, top.get(), out);
-            if (st[(size_t)i]) { why[(size_t)i] = g.idx.size() == 1 ? first : std::string(mp3s_last_error()); std::memset(&out[i], 0, sizeof out[i]); }
-        }
-    }
-    int first_bad = MP3S_OK;
-    for (int i = 0; i < n_files; i++) {
-        if (status) status[i] = st[(size_t)i];
-        if (st[(size_t)i] && !first_bad) { first_bad = st[(size_t)i]; fail(first_bad, "%s", why[(size_t)i].c_str()); }   // the text of the first file that failed
-    }
+    run_groups(groups, [&](int rate, int kbps, const std::vector<int> &idx) {
+        const int rc = encode_group(c, in, idx, rate, kbps, top.get(), out);
+        if (rc) for (int i : idx) std::memset(&out[i], 0, sizeof out[i]);
+        return rc;
+    }, fs, [&] { (void)hipStreamSynchronize(c->stream); });   // (copies of the failed batch may still read the callers' bytes and the staging)
+    const int first_bad = finish_files(fs, status);
     if (!status && first_bad) return first_bad;
     *owner = top.release();
     return MP3S_OK;

@@ -5,7 +5,6 @@
 #include <cerrno>
 #include "mp3s_internal.h"
 
-static inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // message bits the frames in front of a block have taken
 static int64_t cursor0(const EncSeg &s)
@@ -724,14 +723,7 @@ static int reencode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &id
     if (trace_on())
         fprintf(stderr, "mp3s:   %zu stream(s), %lld frames: decode %.3f ms, encode %.3f ms (%d rate passes)\n", idx.size(),
                 (long long)rows_frames, t1 - t0, now_ms() - t1, passes);
-    for (size_t k = 0; k < idx.size(); k++) {
-        mp3s_file &o = out[idx[k]];
-        std::memset(&o, 0, sizeof o);
-        o.data = part->mp3 + segs[k].mp3_off; o.len = segs[k].mp3_len;
-        o.kbps = kbps; o.sampling_rate = samplerate; o.channels = 2; o.n_frames = segs[k].n_frames;
-        o.hide_offset = segs[k].hide_offset;
-        o.too_long = segs[k].hide_offset < (int64_t)segs[k].n_hide - 1 ? 1 : 0;
-    }
+    for (size_t k = 0; k < idx.size(); k++) file_from_seg(segs[k], part->mp3, kbps, samplerate, segs[k].hide_offset, &out[idx[k]]);
     top->parts.push_back(std::move(part));
     return MP3S_OK;
 }
@@ -745,9 +737,9 @@ int mp3s_hide_messages(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *le
     mp3s_multi &m = *top->multi;
     m.parsed.resize(n_files); m.scanned.resize(n_files); m.pcm.assign(n_files, nullptr); m.files.resize(n_files);
     std::vector<std::vector<uint8_t>> bits(n_files);
-    std::vector<int32_t> st(n_files, MP3S_OK);
-    struct Group { int rate, kbps; std::vector<int> idx; };
-    std::vector<Group> groups;
+    FileStatus fs(n_files);
+    std::vector<int32_t> &st = fs.st;
+    FileGroups groups;                       // by (sampling rate, kbps)
     size_t total = 0;
     const double t0 = trace_on() ? now_ms() : 0;
     for (int i = 0; i < n_files; i++) {
@@ -757,37 +749,25 @@ int mp3s_hide_messages(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *le
         total += lens[i];
     }
     if (n_files == 1) m.scanned[0] = std::move(c->spare_scan);   // its capacity: no fresh pages for the blob of a long file
-    parallel_files(n_files, total, [&](int i) { if (!st[i]) st[i] = front_end(m, i); });
+    parallel_files(file_workers(n_files, total, host_threads16()), n_files, [&](int, int i) { if (!st[i]) st[i] = front_end(m, i); });
     const double t1 = trace_on() ? now_ms() : 0;
     for (int i = 0; i < n_files; i++) {
         int kbps = 0;
-        if (st[i]) { fail(st[i], st[i] == MP3S_E_ARG ? "file %d: null pointer" : "file %d: malformed or unsupported MP3 stream", i); continue; }
-        st[i] = reencode_check(m.parsed[i], &kbps);
+        if (st[i]) { fs.set(i, front_end_failed(st[i], i)); continue; }
+        fs.set(i, reencode_check(m.parsed[i], &kbps));
         if (st[i]) continue;
         if (msgs && msgs[i]) message_frame(msgs[i], msg_lens[i], bits[i]);
-        const int rate = m.parsed[i].sampling_rate;
-        size_t g = 0;
-        while (g < groups.size() && (groups[g].rate != rate || groups[g].kbps != kbps)) g++;
-        if (g == groups.size()) groups.push_back({rate, kbps, {}});
-        groups[g].idx.push_back(i);
+        groups.add(m.parsed[i].sampling_rate, kbps, i);
     }
     const double t2 = trace_on() ? now_ms() : 0;
-    for (const Group &g : groups) {
-        const int rc = reencode_group(c, m, g.idx, bits, g.rate, g.kbps, top.get(), out);
-        if (!rc) continue;
-        // one stream spoils its batch (main data the host parser rejects ...): each file on its own, to name it
-        for (int i : g.idx) st[i] = g.idx.size() == 1 ? rc : reencode_group(c, m, std::vector<int>{i}, bits, g.rate, g.kbps, top.get(), out);
-    }
+    run_groups(groups, [&](int rate, int kbps, const std::vector<int> &idx) { return reencode_group(c, m, idx, bits, rate, kbps, top.get(), out); },
+               fs, [] {});
     if (trace_on())
         fprintf(stderr, "mp3s: hide_messages, %d file(s): scan %.3f ms, messages + grouping %.3f ms, device batches %.3f ms\n", n_files,
                 t1 - t0, t2 - t1, now_ms() - t2);
     m.files.clear();   // borrowed pointers
     if (n_files == 1) c->spare_scan = std::move(m.scanned[0]);
-    int first_bad = MP3S_OK;
-    for (int i = 0; i < n_files; i++) {
-        if (status) status[i] = st[i];
-        if (st[i] && !first_bad) first_bad = st[i];
-    }
+    const int first_bad = finish_files(fs, status);
     if (!status && first_bad) return first_bad;
     *owner = top.release();
     return MP3S_OK;

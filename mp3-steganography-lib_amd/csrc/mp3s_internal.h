@@ -223,6 +223,7 @@ struct mp3s_buf {
     ScannedStream scanned;
     std::vector<uint8_t> bytes;      // generic payload (pcm / mp3)
     std::vector<uint8_t> bits;
+    std::vector<FrameRef> refs;      // mp3s_walk_stream: the frames (their table counts in bits)
     std::vector<int32_t> scfsi;
     std::vector<std::unique_ptr<mp3s_buf>> parts;   // results of the batches of a multi-file call
     std::vector<std::vector<uint8_t>> lists;        // mp3s_reveal_messages: per file its text and its stego bits
@@ -236,23 +237,96 @@ struct mp3s_buf {
 inline bool trace_on() { static const bool on = getenv("MP3S_TRACE") != nullptr; return on; }
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// f(i) for i in [0, n) on a few host threads: the front ends of the files of a batch are independent.  Small batches
-// (by bytes) stay on the calling thread -- starting a thread costs about what scanning 100 KB does.
-template <class F>
-void parallel_files(int n, size_t total_bytes, F f)
+// ---------------------------------------------------------------- the frame of the list-of-files calls (file_lists.cpp)
+// mp3s_decode_streams, mp3s_hide_messages, mp3s_encode_files, mp3s_reveal_messages and mp3s_pipe_collect answer per file by ONE
+// rule, made of the pieces below: out[i] zeroed, a code and a text per file, front ends on a few host threads, one device batch
+// per group of files, a failed batch run again file by file, the codes into status[] -- or, without one, the first failing
+// file's code as the call's -- and that file's text into mp3s_last_error().
+
+// x rounded up to a multiple of 16: where every part of a host-made block and every file of a device image begins
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Host threads for the front ends of n files of total_bytes, at most max_threads: small lists (by bytes) stay on the calling
+// thread -- starting a thread costs about what scanning 100 KB does.  host_threads16(): the max_threads of the calls that have
+// no context option to ask (MP3S_OPT_SCAN_THREADS: default_scan_threads).
+inline int file_workers(int n, size_t total_bytes, int max_threads)
 {
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int workers = (int)std::min<size_t>({(size_t)n, (size_t)std::min(hw ? hw : 1u, 16u), total_bytes / (256u << 10) + 1});
+    return (int)std::min<size_t>({(size_t)n, (size_t)max_threads, total_bytes / (256u << 10) + 1});
+}
+inline int host_threads16() { const unsigned hw = std::thread::hardware_concurrency(); return (int)std::min(hw ? hw : 1u, 16u); }
+// f(worker, i) for i in [0, n) on `workers` threads, the calling one (worker 0) included: the front ends of the files of a list
+// are independent.  The files are handed out one by one, in order; f(w, ...) runs on one thread at a time for every w.
+template <class F>
+void parallel_files(int workers, int n, F f)
+{
     if (workers <= 1) {
-        for (int i = 0; i < n; i++) f(i);
+        for (int i = 0; i < n; i++) f(0, i);
         return;
     }
     std::atomic<int> next{0};
-    auto run = [&]() { for (int i; (i = next.fetch_add(1)) < n;) f(i); };
+    auto run = [&](int w) { for (int i; (i = next.fetch_add(1)) < n;) f(w, i); };
     std::vector<std::thread> pool;
-    for (int w = 1; w < workers; w++) pool.emplace_back(run);
-    run();
+    for (int w = 1; w < workers; w++) pool.emplace_back(run, w);
+    run(0);
     for (auto &t : pool) t.join();
+}
+
+// A whole file through the FrameWalker: open, walk to the end into refs (which grows; refs.size() >= the count afterwards), with
+// `tables` ([frames][4], grown beside refs) the code-book counts for as long as tables_wanted says.  Returns the frame count, or
+// -1 when the file is not for the walk; the walker, which stays with the caller for what else it knows of the stream, tells why:
+// irregular, or ended without a frame, or neither -- open() failed, and w.error is its code.
+long walk_whole(const uint8_t *file, size_t len, std::vector<FrameRef> &refs, FrameWalker &w, std::vector<uint8_t> *tables = nullptr,
+                long tables_wanted = 0);
+
+// out = stream `seg` of a finished encode batch whose bytes lie at mp3_base: the ONE place an EncSeg becomes an mp3s_file.  The
+// caller says how many message bits the stream took (the host's count, or the device's cursor).
+struct EncSeg;
+void file_from_seg(const EncSeg &seg, const uint8_t *mp3_base, int kbps, int rate, int64_t hide_offset, mp3s_file *out);
+
+// The files of a list by a pair of keys ((sampling rate, kbps)), groups and members in arrival order: a group is one device batch,
+// and the order of the batches decides where the results lie in the owner.
+struct FileGroups {
+    struct Group { int a, b; std::vector<int> idx; };
+    std::vector<Group> groups;
+    void add(int a, int b, int i)
+    {
+        size_t g = 0;
+        while (g < groups.size() && (groups[g].a != a || groups[g].b != b)) g++;
+        if (g == groups.size()) groups.push_back({a, b, {}});
+        groups[g].idx.push_back(i);
+    }
+};
+
+// Code and text per file of a list call.  Whoever finds a file failing records both at that moment: set(i, code) keeps what
+// mp3s_last_error() says then (the text of the fail() that made the code) -- on the calling thread, that is: a front end on
+// another thread leaves its code in st[i] and the caller composes the text after the join (front_end_failed for the two texts
+// hide and reveal share).
+struct FileStatus {
+    std::vector<int32_t> st;
+    std::vector<std::string> why;
+    explicit FileStatus(int n) : st((size_t)n, MP3S_OK), why((size_t)n) {}
+    void set(int i, int code) { st[(size_t)i] = code; if (code) why[(size_t)i] = mp3s_last_error(); }
+};
+int front_end_failed(int code, int i);   // fail(code, "file %d: null pointer" for MP3S_E_ARG, "file %d: malformed or unsupported MP3 stream" otherwise)
+// The tail of every list call: the codes into status[] (when given) and the FIRST failing file's text into mp3s_last_error().
+// Returns that file's code (MP3S_OK: none failed), which fails the call when status == NULL.
+int finish_files(const FileStatus &fs, int32_t *status);
+
+// run(a, b, idx) -> code, for every group in order.  One file spoils its batch (main data the host parser rejects, a quantizer
+// step that leaves the table ...): a failed group of one fails its file, a larger one is run again file by file, run(a, b, {i}),
+// to name the file -- fs gets each file's code and text.  after_failure() runs between a failed batch and what follows it (the
+// caller that has copies in flight from its callers' bytes waits for them there).
+template <class Run, class After>
+void run_groups(const FileGroups &groups, Run run, FileStatus &fs, After after_failure)
+{
+    for (const FileGroups::Group &g : groups.groups) {
+        const int rc = run(g.a, g.b, g.idx);
+        if (!rc) continue;
+        if (g.idx.size() == 1) fs.set(g.idx[0], rc);
+        after_failure();
+        if (g.idx.size() > 1)
+            for (int i : g.idx) fs.set(i, run(g.a, g.b, std::vector<int>{i}));
+    }
 }
 
 // ---------------------------------------------------------------- decode pipeline (mp3s_decode_pipeline.cpp)

@@ -10,7 +10,6 @@ namespace {
 constexpr size_t kRevealMaxImage = 0xfffffff0u;   // offsets into the image are 32 bits wide
 
 struct RevFile {
-    int st = MP3S_OK;
     bool dev = false;                       // the walk vouches for the stream: its bits come from the device
     std::vector<FrameRef> refs;             // ... its frames, counted from the start of the file
     int32_t n_frames = 0, nch = 0, sampling_rate = 0, bit_rate = 0;
@@ -29,28 +28,11 @@ int host_reveal(const uint8_t *file, size_t len, HostScan &h, RevFile &r, std::v
     return MP3S_OK;
 }
 
-// f(worker, i) for i in [0, n) on `workers` threads (the calling one included)
-template <class F>
-void on_threads(int workers, int n, F f)
-{
-    if (workers <= 1) {
-        for (int i = 0; i < n; i++) f(0, i);
-        return;
-    }
-    std::atomic<int> next{0};
-    auto run = [&](int w) { for (int i; (i = next.fetch_add(1)) < n;) f(w, i); };
-    std::vector<std::thread> pool;
-    for (int w = 1; w < workers; w++) pool.emplace_back(run, w);
-    run(0);
-    for (auto &t : pool) t.join();
-}
-
 // the files `idx` (in image order) through k_reveal: bits[i] (0/1 bytes) and dev_status[i] for each
 int reveal_launch(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *lens, std::vector<RevFile> &rf, const std::vector<int> &idx,
                   std::vector<std::vector<uint8_t>> &lists)
 {
     const size_t ns = idx.size();
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     std::vector<Upload> files;
     std::vector<size_t> place(ns);
     size_t img = 0;
@@ -134,34 +116,29 @@ static int reveal_files(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *l
     std::unique_ptr<mp3s_buf> top(new mp3s_buf());
     top->lists.resize(2 * (size_t)n_files);   // per file: the text, the 0/1 bits
     std::vector<RevFile> rf((size_t)n_files);
+    FileStatus fs(n_files);
+    std::vector<int32_t> &st = fs.st;
     size_t total = 0;
     for (int i = 0; i < n_files; i++) {
         std::memset(&out[i], 0, sizeof out[i]);
-        if (!mp3s[i]) rf[(size_t)i].st = MP3S_E_ARG;
+        if (!mp3s[i]) st[(size_t)i] = MP3S_E_ARG;
         else total += lens[i];
     }
     // ---- front end: the walk, and the byte-level scan for what the walk does not take
-    const int workers = (int)std::min<size_t>({(size_t)n_files, (size_t)default_scan_threads(c), total / (256u << 10) + 1});
+    const int workers = file_workers(n_files, total, default_scan_threads(c));
     std::vector<HostScan> scratch((size_t)std::max(workers, 1));
     const double t0 = trace_on() ? now_ms() : 0;
-    on_threads(workers, n_files, [&](int w, int i) {
+    parallel_files(workers, n_files, [&](int w, int i) {
         RevFile &r = rf[(size_t)i];
-        if (r.st) return;
+        if (st[(size_t)i]) return;
         FrameWalker fw;
-        if (fw.open(mp3s[i], lens[i]) == 0 && lens[i] <= max_image) {
-            size_t cap = lens[i] / 96 + 64, n = 0;
-            r.refs.resize(cap);
-            while (!fw.ended && !fw.irregular) {
-                if (n == cap) { cap *= 2; r.refs.resize(cap); }
-                n += (size_t)fw.next(r.refs.data() + n, (long)(cap - n), nullptr, 0, 0);
-            }
-            if (fw.ended && !fw.irregular && n > 0 && n <= 0x7fffffff / 12) {
-                r.dev = true;
-                r.n_frames = (int32_t)n; r.nch = fw.nch; r.sampling_rate = fw.sampling_rate; r.bit_rate = fw.bit_rate;
-                return;
-            }
+        const long n = lens[i] <= max_image ? walk_whole(mp3s[i], lens[i], r.refs, fw) : -1;
+        if (n > 0 && n <= 0x7fffffff / 12) {
+            r.dev = true;
+            r.n_frames = (int32_t)n; r.nch = fw.nch; r.sampling_rate = fw.sampling_rate; r.bit_rate = fw.bit_rate;
+            return;
         }
-        r.st = host_reveal(mp3s[i], lens[i], scratch[(size_t)w], r, top->lists[2 * (size_t)i + 1], top->lists[2 * (size_t)i]);
+        st[(size_t)i] = host_reveal(mp3s[i], lens[i], scratch[(size_t)w], r, top->lists[2 * (size_t)i + 1], top->lists[2 * (size_t)i]);
     });
     const double t1 = trace_on() ? now_ms() : 0;
     // ---- the device's share, in launches of at most max_streams streams and max_image bytes of image
@@ -176,7 +153,7 @@ static int reveal_files(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *l
     };
     for (int i = 0; i < n_files && !rc; i++) {
         if (!rf[(size_t)i].dev) continue;
-        size_t at = (img + 15) & ~(size_t)15;
+        size_t at = up16(img);
         if ((int)idx.size() == max_streams || at + lens[i] > max_image) { flush(); at = 0; }
         idx.push_back(i);
         img = at + lens[i];
@@ -186,24 +163,20 @@ static int reveal_files(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *l
     // a stream the kernel flagged (a reference it would not follow): the host scan decides
     for (int i = 0; i < n_files; i++) {
         RevFile &r = rf[(size_t)i];
-        if (r.st || r.dev || !r.refs.size()) continue;
-        r.st = host_reveal(mp3s[i], lens[i], scratch[0], r, top->lists[2 * (size_t)i + 1], top->lists[2 * (size_t)i]);
+        if (st[(size_t)i] || r.dev || !r.refs.size()) continue;
+        st[(size_t)i] = host_reveal(mp3s[i], lens[i], scratch[0], r, top->lists[2 * (size_t)i + 1], top->lists[2 * (size_t)i]);
     }
     if (trace_on()) fprintf(stderr, "mp3s: reveal_messages, %d file(s): front end %.3f ms on %d thread(s), %d launch(es) %.3f ms\n", n_files, t1 - t0, workers, n_launches, now_ms() - t1);
-    int first_bad = MP3S_OK;
     for (int i = 0; i < n_files; i++) {
         const RevFile &r = rf[(size_t)i];
-        if (status) status[i] = r.st;
-        if (r.st) {
-            if (!first_bad) { first_bad = r.st; fail(r.st, r.st == MP3S_E_ARG ? "file %d: null pointer" : "file %d: malformed or unsupported MP3 stream", i); }
-            continue;
-        }
+        if (st[(size_t)i]) { fs.set(i, front_end_failed(st[(size_t)i], i)); continue; }
         const std::vector<uint8_t> &text = top->lists[2 * (size_t)i], &bits = top->lists[2 * (size_t)i + 1];
         mp3s_file &o = out[i];
         o.data = text.data(); o.len = text.size();
         o.kbps = r.bit_rate / 1000; o.sampling_rate = r.sampling_rate; o.channels = r.nch; o.n_frames = r.n_frames;
         o.n_bits = (int32_t)bits.size(); o.bits = bits.data();
     }
+    const int first_bad = finish_files(fs, status);
     if (!status && first_bad) return first_bad;
     *owner = top.release();
     return MP3S_OK;

@@ -98,7 +98,7 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
         const uint8_t *file = j.files[i].first;
         const size_t len = j.files[i].second;
         if (!file) return false;
-        img = (img + 15) & ~(size_t)15;
+        img = up16(img);
         if (img + len + 64 > s.image_cap || img + len > 0xfffffff0ull) return false;
         FrameWalker w;
         if (w.open(file, len)) return false;
@@ -174,7 +174,7 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
     size_t enc_bytes = 0;
     // pack: [small results, zeroed | encoder inputs | host-decoded frames | refs | streams], one copy up
     j.o_small = s.o_in;
-    const size_t small_room = (small_bytes(j.decode ? 1 : nf) + 15) & ~(size_t)15;
+    const size_t small_room = up16(small_bytes(j.decode ? 1 : nf));
     std::memset(s.h_stage + j.o_small, 0, kSmallHead);
     j.o_encblk = j.o_small + small_room;
     if (j.decode) {
@@ -188,11 +188,11 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
     }
     if (trace_on() && !j.decode) fprintf(stderr, "mp3s:   walk job %lld: %d stream(s), redo launches %d, variant entries %d, first stream: any_silent %d, tables known for %d units, reach %d\n",
                                          (long long)j.ticket, nf, (int)j.L.redo, j.L.n_entries, j.segs[0].any_silent, j.segs[0].n_guess, j.segs[0].reach);
-    j.o_fix = (j.o_encblk + enc_bytes + 15) & ~(size_t)15;
+    j.o_fix = up16(j.o_encblk + enc_bytes);
     if (j.o_fix != s.o_in + s.in_cap) std::memmove(s.h_stage + j.o_fix, fix, (size_t)j.n_fix * kPlaceEntry);
-    j.o_refs = (j.o_fix + (size_t)j.n_fix * kPlaceEntry + 15) & ~(size_t)15;
+    j.o_refs = up16(j.o_fix + (size_t)j.n_fix * kPlaceEntry);
     std::memmove(s.h_stage + j.o_refs, refs, (size_t)n * sizeof(FrameRef));
-    j.o_streams = (j.o_refs + (size_t)n * sizeof(FrameRef) + 15) & ~(size_t)15;
+    j.o_streams = up16(j.o_refs + (size_t)n * sizeof(FrameRef));
     std::memmove(s.h_stage + j.o_streams, streams, (size_t)nf * sizeof(StreamRef));
     j.pack_end = j.o_streams + (size_t)nf * sizeof(StreamRef);
     j.ck.on = false;
@@ -227,25 +227,25 @@ bool prepare_chunk(mp3s_pipe *P, Job &j, Slot &s, int max_p23)
     j.res.reset(new mp3s_buf());
     if (!j.res->big[2].reserve(small_bytes(1))) return false;
     if (k.decode && !j.res->big[1].reserve((size_t)k.n_win * 8 + 16)) return false;
-    j.o_fix = j.o_small + ((small_bytes(1) + 15) & ~(size_t)15);
+    j.o_fix = j.o_small + up16(small_bytes(1));
     if (k.fix) {
         if (s.fix_cap < 1) return false;
         std::memcpy(s.h_stage + j.o_fix, k.fix, kPlaceEntry);
         *reinterpret_cast<int32_t *>(s.h_stage + j.o_fix) = (int32_t)(k.n_win - 1);
         j.n_fix = 1;
     }
-    j.o_refs = (j.o_fix + (size_t)j.n_fix * kPlaceEntry + 15) & ~(size_t)15;
+    j.o_refs = up16(j.o_fix + (size_t)j.n_fix * kPlaceEntry);
     FrameRef *refs = reinterpret_cast<FrameRef *>(s.h_stage + j.o_refs);
     std::memcpy(refs, k.refs + k.w0, (size_t)k.n_win * sizeof(FrameRef));
     for (long f = 0; f < k.n_win; f++) { refs[f].stream = 0; refs[f].flags = 0; }
     if (k.fix) refs[k.n_win - 1].flags = MP3S_FS_HOST_DECODED;
-    j.o_streams = (j.o_refs + (size_t)k.n_win * sizeof(FrameRef) + 15) & ~(size_t)15;
+    j.o_streams = up16(j.o_refs + (size_t)k.n_win * sizeof(FrameRef));
     StreamRef *sr = reinterpret_cast<StreamRef *>(s.h_stage + j.o_streams);
     std::memset(sr, 0, sizeof *sr);
     sr->base = 0; sr->end = (uint32_t)k.file_len; sr->first_frame = 0; sr->n_frames = (uint32_t)k.n_win;
     if (j.file_wide) { sr->side_back[0] = (uint16_t)((uint32_t)k.w0 & 0xffffu); sr->side_back[1] = (uint16_t)((uint32_t)k.w0 >> 16); }
     FrameWalker::history(k.refs, k.w0, sr->prev_size);
-    j.o_encblk = (j.o_streams + sizeof(StreamRef) + 15) & ~(size_t)15;
+    j.o_encblk = up16(j.o_streams + sizeof(StreamRef));
     j.front_end = j.pack_end = j.o_encblk;
     if (j.pack_end > s.o_in + s.pack_cap) return false;
     j.max_p23 = max_p23;
@@ -274,17 +274,14 @@ bool prepare_block(mp3s_pipe *P, Job &j, Slot &s)
     const uint8_t *file = j.files[0].first;
     const size_t len = j.files[0].second;
     if (!file || len > 0xffff0000ull) return false;
-    FrameWalker w;
-    if (w.open(file, len) || w.ended) return false;
-    j.refs.resize(len / 24 + 16);
     j.bits.assign(1, {});
     if (j.msgs[0].first) {
         message_frame(j.msgs[0].first, j.msgs[0].second, j.bits[0]);
         if (j.bits[0].size() > 0x3fffff00) return false;
     }
-    long n = 0;
-    while (!w.ended && !w.irregular && (size_t)n < j.refs.size()) n += w.next(j.refs.data() + n, (long)j.refs.size() - n, nullptr, 0, 0);
-    if (w.irregular || !w.ended || n <= 0 || w.dup_last) return false;
+    FrameWalker w;
+    const long n = walk_whole(file, len, j.refs, w);
+    if (n <= 0 || w.dup_last) return false;
     int kbps = 0;
     if (reencode_params(w.sampling_rate, w.bit_rate, w.nch, n, 0, &kbps)) return false;
     const long base = n / j.world, rem = n % j.world;
@@ -394,7 +391,7 @@ bool prepare_fast(mp3s_pipe *P, Job &j, Slot &s, ParsedStream &p, size_t *blob_l
         j.res->bits = std::move(j.res_bits);
         return true;
     }
-    const size_t o_enc = ((size_t)n * sizeof(mp3s_frame_hdr) + 15) & ~(size_t)15;
+    const size_t o_enc = up16((size_t)n * sizeof(mp3s_frame_hdr));
     if (o_enc > s.in_cap || !encode_inputs(j, s, in + o_enc, s.in_cap - o_enc, P->c->opt[MP3S_OPT_SELECT] != 0)) return false;
     j.o_encblk = s.o_in + o_enc;
     j.res.reset(new mp3s_buf());
@@ -429,7 +426,7 @@ int issue_front(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23, boo
         for (const Upload &u : j.ups) HIPCHK(hipMemcpyAsync(s.d_image + u.dst, u.src, u.bytes, hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipMemcpyAsync(s.d_stage + j.o_small, s.h_stage + j.o_small, (inputs_later ? j.front_end : j.pack_end) - j.o_small, hipMemcpyHostToDevice, P->s_up));
     } else {
-        const size_t o_enc = j.o_encblk - s.o_in, in_bytes = j.decode ? ((size_t)n * sizeof(mp3s_frame_hdr) + 15) & ~(size_t)15 : o_enc + L.bytes;
+        const size_t o_enc = j.o_encblk - s.o_in, in_bytes = j.decode ? up16((size_t)n * sizeof(mp3s_frame_hdr)) : o_enc + L.bytes;
         HIPCHK(hipMemcpyAsync(d_blob, s.h_stage, blob_len, hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipMemcpyAsync(d_side, s.h_stage + s.o_side, (size_t)n * sizeof(mp3s_frame_side), hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipMemcpyAsync(s.d_stage + s.o_in, s.h_stage + s.o_in, in_bytes, hipMemcpyHostToDevice, P->s_up));
@@ -633,7 +630,7 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
         else if (w.samplerate != j.rate || j.enc_kbps[(size_t)i] != j.kbps) return false;   // more than one device batch
         if ((size_t)(b.n_all + w.count) > s.side_cap) return false;
         // (what a file needs of the image lies inside the file; mono and 8-bit files need less per frame than 4 608 bytes, 24/32-bit stereo more)
-        if (((b.img + 15) & ~(size_t)15) + w.need + kWavSlack > s.wav_cap) return false;
+        if (up16(b.img) + w.need + kWavSlack > s.wav_cap) return false;
         if (b.add(w, file, nullptr)) return false;
         j.stream_first[(size_t)i] = b.first.back();
         j.segs[(size_t)i].n_frames = (int)w.count; j.segs[(size_t)i].hide = hide; j.segs[(size_t)i].n_hide = n_hide;
@@ -652,7 +649,7 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
     j.n_total = (int)b.n_all;
     j.L = EncLayout();
     j.o_small = s.o_in;
-    const size_t small_room = (small_bytes(nf) + 15) & ~(size_t)15;
+    const size_t small_room = up16(small_bytes(nf));
     std::memset(s.h_stage + j.o_small, 0, kSmallHead);
     j.o_encblk = j.o_small + small_room;
     // (no stream to ask for table counts: the cursors are guessed at three per unit as mp3s_encode_pcm does, the selection on the
@@ -939,16 +936,16 @@ bool pipe_slot_ready(mp3s_pipe *P, Slot &s)
         // main data: the file minus headers plus alignment and 8 zero bytes per frame; frames: 96 bytes is the smallest
         // Layer III frame (32 kbit/s at 48 kHz); anything denser (false syncs) overflows the sink and takes the other path.
         // (The context's own pipe cuts its chunks by FRAMES and says how many a chunk can have: max_frames.)
-        s.blob_cap = (max_job_bytes + max_job_bytes / 8 + 4096 + 15) & ~(size_t)15;
+        s.blob_cap = up16(max_job_bytes + max_job_bytes / 8 + 4096);
         s.side_cap = P->max_frames > 0 ? P->max_frames + 16 : max_job_bytes / 96 + 16;
-        s.in_cap = (s.side_cap * (72 + 16) + max_job_bytes / 4 + (size_t)kMaxFastFiles * (sizeof(mp3s_chain_seg) + sizeof(mp3s_select_span)) + s.side_cap * 4 * MP3S_SELECT_VARIANTS * 8 + 4096 + 15) & ~(size_t)15;   // (+ variant entries: at most 10 per unit, 8 bytes each)
+        s.in_cap = up16(s.side_cap * (72 + 16) + max_job_bytes / 4 + (size_t)kMaxFastFiles * (sizeof(mp3s_chain_seg) + sizeof(mp3s_select_span)) + s.side_cap * 4 * MP3S_SELECT_VARIANTS * 8 + 4096);   // (+ variant entries: at most 10 per unit, 8 bytes each)
         s.o_side = s.blob_cap;
-        s.o_in = (s.o_side + s.side_cap * sizeof(mp3s_frame_side) + 15) & ~(size_t)15;
+        s.o_in = up16(s.o_side + s.side_cap * sizeof(mp3s_frame_side));
         s.fix_cap = internal ? 8 : std::min<size_t>(kMaxFastFiles, s.side_cap);     // (host-decoded last frames: one per file of a job; the context's own pipe runs ONE file's chunks)
-        s.pack_cap = (s.in_cap + s.fix_cap * kPlaceEntry + s.side_cap * sizeof(FrameRef) + (size_t)kMaxFastFiles * sizeof(StreamRef) + 256 + 15) & ~(size_t)15;
+        s.pack_cap = up16(s.in_cap + s.fix_cap * kPlaceEntry + s.side_cap * sizeof(FrameRef) + (size_t)kMaxFastFiles * sizeof(StreamRef) + 256);
         s.stage_bytes = s.o_in + s.pack_cap;
         s.o_dechdr = s.stage_bytes;
-        s.o_tsel = (s.o_dechdr + s.side_cap * sizeof(mp3s_frame_hdr) + 15) & ~(size_t)15;
+        s.o_tsel = up16(s.o_dechdr + s.side_cap * sizeof(mp3s_frame_hdr));
         s.image_cap = max_job_bytes + 2 * kImageLead + (size_t)kMaxFastFiles * 16 + 4096;
         s.mp3_cap = max_job_bytes + s.side_cap + 4096;
         if (hipHostMalloc((void **)&s.h_stage, s.stage_bytes, hipHostMallocDefault) != hipSuccess ||
@@ -1212,11 +1209,7 @@ int mp3s_pipe_collect(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3s_file
             const mp3s_chain_seg_out *so = (const mp3s_chain_seg_out *)(j->res->big[2].data() + kSmallHead);
             for (int i = 0; i < nf; i++) {
                 const EncSeg &sg = j->segs[(size_t)i];
-                std::memset(&out[i], 0, sizeof out[i]);
-                out[i].data = j->res->mp3 + sg.mp3_off; out[i].len = sg.mp3_len;
-                out[i].kbps = j->kbps; out[i].sampling_rate = j->rate; out[i].channels = 2; out[i].n_frames = sg.n_frames;
-                out[i].hide_offset = resolved ? sg.hide_offset : so[i].cursor - sg.hide_base;
-                out[i].too_long = out[i].hide_offset < (int64_t)sg.n_hide - 1 ? 1 : 0;
+                file_from_seg(sg, j->res->mp3, j->kbps, j->rate, resolved ? sg.hide_offset : so[i].cursor - sg.hide_base, &out[i]);
                 status[i] = MP3S_OK;
             }
             *owner = j->res.release();

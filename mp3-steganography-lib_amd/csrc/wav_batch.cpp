@@ -40,7 +40,7 @@ void WavBatch::clear()
 
 int WavBatch::add(const WavPlan &p, const uint8_t *wav, const uint32_t *d_taps)
 {
-    img = (img + 15) & ~(size_t)15;
+    img = up16(img);
     const uint64_t src = (uint64_t)img + (uint64_t)p.data_offset;
     if (p.resample) {
         const uint32_t span = resample_span((uint32_t)p.L, (uint32_t)p.M, (uint32_t)p.T), pairs = (uint32_t)p.L * (uint32_t)p.T / 2;
@@ -69,11 +69,10 @@ int WavBatch::add(const WavPlan &p, const uint8_t *wav, const uint32_t *d_taps)
 
 void WavBatch::place_records(size_t base)
 {
-    auto part = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
-    o_runs = part(base);
-    o_iruns = o_runs + part(runs.size() * sizeof(WavRun));
-    o_sruns = o_iruns + part(iruns.size() * sizeof(WavImportRun));
-    o_rruns = o_sruns + part(sruns.size() * sizeof(WavImportRun));
+    o_runs = up16(base);
+    o_iruns = o_runs + up16(runs.size() * sizeof(WavRun));
+    o_sruns = o_iruns + up16(iruns.size() * sizeof(WavImportRun));
+    o_rruns = o_sruns + up16(sruns.size() * sizeof(WavImportRun));
     rec_end = o_rruns + rruns.size() * sizeof(WavResampleRun);
 }
 

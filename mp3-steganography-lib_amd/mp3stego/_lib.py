@@ -342,6 +342,21 @@ def _view(ptr, dtype, shape):
     return np.frombuffer((C.c_char * n).from_address(ptr), dtype=dtype).reshape(shape).copy()
 
 
+def _file_list(files):
+    """a list of byte strings as the arrays of a list-of-files call -> (n, what has to stay alive beside them, pointers, lengths).
+    An empty file points at _EMPTY: a null pointer is an argument error, whatever numpy calls the address of an empty array."""
+    n = len(files)
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data if len(b) else C.addressof(_EMPTY) for b in bufs])
+    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    return n, (files, bufs), ptrs, lens
+
+
+def _per_file(out, status, make, n=None):
+    """the answer of a list-of-files call, one entry per file: make(out[i]), or the Mp3sError status[i] names"""
+    return [Mp3sError(status[i], f"file {i}") if status[i] else make(out[i]) for i in range(len(status) if n is None else n)]
+
+
 class _Owner:
     """keeps an mp3s_buf alive for the numpy arrays that look into it (no copy of large results)"""
 
@@ -615,21 +630,18 @@ class Context:
         """Decode many MP3 files as one device batch (one Huffman + one transform launch per channel count).
         per_file=True: a file that cannot be decoded yields the Mp3sError it alone would raise, the others are unaffected;
         otherwise the first such file fails the call."""
-        n = len(files)
-        if n == 0:
+        if len(files) == 0:
             return []
-        bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-        ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * n)(*[len(f) for f in files])
+        n, _keep, ptrs, lens = _file_list(files)
         owner = C.c_void_p()
         d = (Decoded * n)()
-        status = (C.c_int32 * n)()
+        status = (C.c_int32 * n)()                 # (stays zero without per_file: a failing file fails the call)
         check(lib().mp3s_decode_streams(self.handle, ptrs, lens, n, out_format, C.byref(owner), d, status if per_file else None))
         own = _Owner(owner)
         dt = {MP3S_PCM_I16: np.int16, MP3S_PCM_F32: np.float32, MP3S_PCM_F64: np.float64}[out_format]
-        return [Mp3sError(status[i], f"file {i}") if per_file and status[i] else
-                {"n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate,
-                 "pcm": _view_owned(x.pcm, dt, (x.n_rows, x.nch), own), "bits": _view(x.bits, np.uint8, (x.n_bits,))} for i, x in enumerate(d)]
+        return _per_file(d, status, lambda x: {
+            "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate,
+            "pcm": _view_owned(x.pcm, dt, (x.n_rows, x.nch), own), "bits": _view(x.bits, np.uint8, (x.n_bits,))})
 
     def encode_pcm(self, pcm_i16, samplerate, bitrate, hide_bits=None):
         pcm_i16 = np.ascontiguousarray(pcm_i16, dtype=np.int16)
@@ -804,30 +816,20 @@ class Context:
     def hide_messages(self, mp3s, messages):
         """hide_message / clear_file (message None) over a list of files as one device batch per (rate, bitrate).
         Returns one entry per file: the dict hide_message returns, or the Mp3sError that file alone would raise."""
-        n = len(mp3s)
-        if n != len(messages):
+        if len(mp3s) != len(messages):
             raise ValueError("one message (or None) per file")
-        if n == 0:
+        if len(mp3s) == 0:
             return []
-        bufs = [np.frombuffer(m, dtype=np.uint8) for m in mp3s]
+        n, _keep, files, lens = _file_list(mp3s)
         msgs = [None if t is None else np.frombuffer(t.encode("utf-8") or b"\0", dtype=np.uint8) for t in messages]
-        files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * n)(*[len(b) for b in bufs])
         mptr = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in msgs])
         mlen = (C.c_size_t * n)(*[0 if t is None else len(t.encode("utf-8")) for t in messages])
         out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_hide_messages(self.handle, files, lens, n, mptr, mlen, C.byref(owner), out, status))
         try:
-            res = []
-            for i in range(n):
-                f = out[i]
-                if status[i]:
-                    res.append(Mp3sError(status[i], f"file {i}"))
-                else:
-                    res.append({"data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                                "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-                                "hide_offset": f.hide_offset})
-            return res
+            return _per_file(out, status, lambda f: {
+                "data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+                "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long), "hide_offset": f.hide_offset})
         finally:
             lib().mp3s_buf_free(owner)
 
@@ -835,28 +837,19 @@ class Context:
         """reveal_message over a list of files as ONE device batch (mp3s_reveal_messages): the files the walk calls regular through
         k_reveal, the others through the host scan.  Returns one entry per file: a dict with the keys of reveal_message(), or the
         Mp3sError that file's scan raises.  _max_streams (test aid): at most that many streams to a launch."""
-        n = len(mp3s)
-        if n == 0:
+        if len(mp3s) == 0:
             return []
-        bufs = [np.frombuffer(m, dtype=np.uint8) for m in mp3s]
-        files = (C.c_void_p * n)(*[b.ctypes.data if len(b) else C.addressof(_EMPTY) for b in bufs])
-        lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+        n, _keep, files, lens = _file_list(mp3s)
         out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
         if _max_streams is None:
             check(lib().mp3s_reveal_messages(self.handle, files, lens, n, C.byref(owner), out, status))
         else:
             check(lib().mp3s_debug_reveal_messages(self.handle, files, lens, n, int(_max_streams), C.byref(owner), out, status))
         try:
-            res = []
-            for i in range(n):
-                f = out[i]
-                if status[i]:
-                    res.append(Mp3sError(status[i], f"file {i}"))
-                else:
-                    res.append({"data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                                "channels": f.channels, "n_frames": f.n_frames, "too_long": False, "hide_offset": 0,
-                                "bits": _view(f.bits, np.uint8, (f.n_bits,))})
-            return res
+            return _per_file(out, status, lambda f: {
+                "data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+                "channels": f.channels, "n_frames": f.n_frames, "too_long": False, "hide_offset": 0,
+                "bits": _view(f.bits, np.uint8, (f.n_bits,))})
         finally:
             lib().mp3s_buf_free(owner)
 
@@ -871,17 +864,11 @@ class Context:
         out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_encode_files(self.handle, files, lens, n, kbps, hptr, hlen, C.byref(owner), out, status))
         own = _Owner(owner)
-        res = []
-        for i in range(n):
-            f = out[i]
-            if status[i]:
-                res.append(Mp3sError(status[i], f"file {i}"))
-            else:
-                res.append({"data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-                            "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)})
         del keep
-        return res
+        return _per_file(out, status, lambda f: {
+            "data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
+            "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)})
 
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
@@ -910,16 +897,14 @@ def _encode_args(wavs, bitrate, hide_bits, messages):
         hide_bits = [None if m is None else np.array(message_frame(m), dtype=np.uint8) for m in messages]
     if hide_bits is not None and len(hide_bits) != n:
         raise ValueError("one bit string (or None) per file")
-    bufs = [np.frombuffer(w, dtype=np.uint8) for w in wavs]
-    files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+    _, keep, files, lens = _file_list(wavs)
     kbps = (C.c_int32 * n)(*rates)
     hbs = hptr = hlen = None
     if hide_bits is not None:
         hbs = [None if h is None or not len(h) else np.ascontiguousarray(h, dtype=np.uint8) for h in hide_bits]
         hptr = (C.c_void_p * n)(*[None if h is None else h.ctypes.data for h in hbs])
         hlen = (C.c_int32 * n)(*[0 if h is None else len(h) for h in hbs])
-    return n, files, lens, kbps, hptr, hlen, (wavs, bufs, hbs)
+    return n, files, lens, kbps, hptr, hlen, (keep, hbs)
 
 
 class Pipe:
@@ -945,9 +930,7 @@ class Pipe:
             raise ValueError("one message (or None) per file")
         if n > self._cap:
             raise ValueError(f"{n} files in one job, the pipe was made for {self._cap} (max_files)")
-        bufs = [np.frombuffer(m, dtype=np.uint8) for m in mp3s]
-        files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+        _, keep, files, lens = _file_list(mp3s)
         msgs = mptr = mlen = None
         if messages is not None:
             enc = [None if t is None else t.encode("utf-8") for t in messages]
@@ -959,7 +942,7 @@ class Pipe:
         if rc == E_BUSY:
             return None
         check(rc)
-        self._keep[t.value] = (mp3s, bufs, msgs, files, lens, mptr, mlen)
+        self._keep[t.value] = (keep, msgs, files, lens, mptr, mlen)
         return t.value
 
     def submit_decode(self, mp3s):
@@ -967,15 +950,13 @@ class Pipe:
         n = len(mp3s)
         if n > self._cap:
             raise ValueError(f"{n} files in one job, the pipe was made for {self._cap} (max_files)")
-        bufs = [np.frombuffer(m, dtype=np.uint8) for m in mp3s]
-        files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-        lens = (C.c_size_t * n)(*[len(b) for b in bufs])
+        _, keep, files, lens = _file_list(mp3s)
         t = C.c_int64()
         rc = lib().mp3s_pipe_submit_decode(self.handle, files, lens, n, C.byref(t))
         if rc == E_BUSY:
             return None
         check(rc)
-        self._keep[t.value] = (mp3s, bufs, files, lens)
+        self._keep[t.value] = (keep, files, lens)
         return t.value
 
     def submit_encode(self, wavs, bitrate=320, hide_bits=None, messages=None):
@@ -1034,16 +1015,10 @@ class Pipe:
         self._keep.pop(t.value, None)
         check(rc)
         own = _Owner(owner)
-        res = []
-        for i in range(nf.value):
-            f = self._out[i]
-            if self._status[i]:
-                res.append(Mp3sError(self._status[i], f"file {i}"))
-            else:
-                res.append({"data": Context._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-                            "hide_offset": f.hide_offset, "bits": _view(f.bits, np.uint8, (f.n_bits,))})
-        return t.value, res
+        return t.value, _per_file(self._out, self._status, lambda f: {
+            "data": Context._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
+            "hide_offset": f.hide_offset, "bits": _view(f.bits, np.uint8, (f.n_bits,))}, nf.value)
 
     def stats(self):
         s = PipeStats()
