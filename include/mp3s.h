@@ -872,6 +872,62 @@ int mp3s_reveal_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t
 int mp3s_debug_reveal_messages(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int max_streams,
                                mp3s_buf **owner, mp3s_file *out, int32_t *status);
 
+/* ---------------------------------------------------------------- (vi-b) how much fits: message capacity of MP3 and WAV files
+ * replaces: hiding something and looking at too_long.  The message cursor of the reference (__hide_str_offset, reference
+ *           encoder/MP3_Encoder.py:808-809, read at :1154-1168) advances by the number of non-zero table_select of every unit whose
+ *           xrmax != 0; how far it gets over a stream is how many message bits the stream takes.
+ * What capacity means here:
+ *   bits        the sum of mp3s_gr_out.n_tables over the stream's units with MP3S_RF_ACTIVE, after the chain check has made the records
+ *               final (what k_chain.hpp sums for hiding streams): the message bits the re-encode this call performed takes or would
+ *               take.  It depends on that encode alone and is exact for it.
+ *   without a message   the capacity of the CLEAR re-encode: mp3s_clear_file for an MP3, mp3s_encode_file without hide_bits for a WAV.
+ *   with a message      the call does the hide encode without producing the file: hide_offset and too_long are exactly what
+ *               mp3s_hide_messages / mp3s_encode_files report for that file and message, bits is the count of THAT encode.  For a
+ *               message that does not fit, bits == hide_offset: the exact capacity under that message.
+ *   the clear capacity is an ESTIMATE of the capacity under a message: a table swapped through IDX_TO_TRANSFORM_HUF changes a region's
+ *               bit count, which can move the quantizer step and, rarely, which regions are empty.  It estimates the capacity under a
+ *               particular message; it does not bound it.
+ *   text_bytes  the largest n such that an ASCII message of n bytes, framed by mp3s_message_frame ("<n>#" + message), has
+ *               n_hide - 1 <= bits -- the too_long rule of every hide call; 0 when not even "0#" fits (mp3s_capacity_text_bytes).
+ * The encode runs up to the chain check and stops there: no bit packing, no MP3 bytes.  k_capacity (mp3s_capacity_dev) counts on the
+ * device, and the verdict, the per-stream records and (on request) the profile come down in one small copy.  Message variants,
+ * selection and the device's re-runs are those of the hide calls.  Where the verdict says that the guesses of the first pass did not
+ * hold (mp3s_chain_resolve_dev: verdict != 0), the group goes through the full encode instead -- the host resolves the chains as for a
+ * hide call -- and is counted on the host from the final records; `fallback` tells which way a file went. */
+typedef struct {
+    int64_t bits;                    /* of the stream */
+    int32_t active_units;            /* its units with MP3S_RF_ACTIVE */
+    int32_t reserved;                /* 0 */
+} mp3s_capacity_seg; /* 16 bytes */
+/* k_capacity alone, asynchronous on the context's stream: d_gr = the records of a batch (unit order frame, ch, gr; n_tables 0 .. 3),
+ * d_segs = its streams (first_frame and n_frames are read), d_out [n_segs]; d_profile optional, uint32 [frames of the batch]: per frame
+ * the inclusive running sum of its stream's bits up to and including that frame (it restarts at every stream's first frame; the last
+ * frame's value equals bits; 12 bits a frame and fewer than 2^28 frames stay below 2^32).  A stream of 0 frames gets zeros. */
+int mp3s_capacity_dev(mp3s_ctx *ctx, const mp3s_gr_out *d_gr, const mp3s_chain_seg *d_segs, int n_segs, mp3s_capacity_seg *d_out,
+                      uint32_t *d_profile);
+typedef struct {
+    int64_t bits, hide_offset, text_bytes;
+    int32_t too_long, n_frames, kbps, sampling_rate, channels, active_units;
+    int32_t fallback;          /* 0: counted by k_capacity; 1: through the full path (verdict, or a file the batch does not take) */
+    int32_t reserved;
+    const uint32_t *profile;   /* [n_frames] running sum, or NULL */
+} mp3s_capacity;
+/* The capacity of a list of MP3 files: decoded and encoded per (sampling rate, bitrate) group exactly as mp3s_hide_messages does it (the
+ * PCM never leaves HBM), msgs / msg_lens by its rules (msgs[i] NULL = no message: the clear capacity; msgs NULL = none anywhere).
+ * status[i] and mp3s_last_error() follow the rule of every list call; a file mp3s_hide_messages refuses (a mono re-encode, an empty
+ * file, no sync ...) gets the same code, its out[i] zeroed.  Every file that call takes goes through the batch here as well.
+ * want_profile != 0: out[i].profile = the per-frame running sum (see mp3s_capacity_dev), owned by *owner. */
+int mp3s_capacity_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, const uint8_t *const *msgs,
+                        const size_t *msg_lens, int want_profile, mp3s_buf **owner, mp3s_capacity *out, int32_t *status);
+/* ... and of a list of WAV files: read, laid out and brought to the device as mp3s_encode_files does it (MP3S_OPT_WAV_IMPORT and
+ * MP3S_OPT_WAV_RESAMPLE apply as they do there, every refusal of the reader in force is the file's code here), bitrate_kbps / hide_bits /
+ * n_hide by its rules.  kbps, sampling_rate, channels and n_frames are what the encode call would report. */
+int mp3s_capacity_wavs(mp3s_ctx *ctx, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
+                       const uint8_t *const *hide_bits, const int32_t *n_hide, int want_profile, mp3s_buf **owner, mp3s_capacity *out,
+                       int32_t *status);
+/* text_bytes of a bit count (host only, no context): "1#a" is 24 bits, so 0 below 23 */
+int64_t mp3s_capacity_text_bytes(int64_t bits);
+
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference
  *           steganography.py:133-182, whose two serial frame loops (decoder/MP3_Parser.py:68-80, encoder/MP3_Encoder.py:

@@ -119,6 +119,10 @@ inline size_t reveal_packed_bytes(uint64_t n_frames) { return (size_t)((n_frames
 int launch_reveal(hipStream_t stream, const uint8_t *d_image, uint32_t image_base, const FrameRef *d_refs, const StreamRef *d_streams, int n_streams,
                   const uint32_t *d_out_off, uint8_t *d_packed, int32_t *d_n_bits, int32_t *d_status);
 
+// message capacity of the streams of an encode batch (k_capacity.hpp) from the records the chain check has made final: per stream its
+// record, and with d_profile (optional, [frames of the batch]) per frame the running sum of the stream's bits up to and including it
+int launch_capacity(hipStream_t stream, const mp3s_gr_out *d_gr, const mp3s_chain_seg *d_segs, int n_segs, mp3s_capacity_seg *d_out, uint32_t *d_profile);
+
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes

@@ -23,6 +23,7 @@ __constant__ DevTables c_tab;
 #include "k_huffman.hpp"
 #include "k_parse.hpp"
 #include "k_reveal.hpp"
+#include "k_capacity.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
@@ -394,6 +395,14 @@ int launch_reveal(hipStream_t stream, const uint8_t *d_image, uint32_t image_bas
     for (int t = 0; t < 32; t++) if (HT.in_h0[t]) h0_mask |= 1u << t;
     hipLaunchKernelGGL(k_reveal, dim3((unsigned)n_streams), dim3(REVEAL_TILE), 0, stream, d_image, image_base, reinterpret_cast<const ParseFrameRef *>(d_refs),
                        reinterpret_cast<const ParseStreamRef *>(d_streams), d_out_off, h0_mask, d_packed, d_n_bits, d_status);
+    return (int)hipGetLastError();
+}
+
+// k_capacity: one workgroup per stream; the records of stream s are d_gr[(first_frame + f) * 4 + k], its profile d_profile[first_frame + f]
+int launch_capacity(hipStream_t stream, const mp3s_gr_out *d_gr, const mp3s_chain_seg *d_segs, int n_segs, mp3s_capacity_seg *d_out, uint32_t *d_profile)
+{
+    if (n_segs <= 0) return 0;
+    hipLaunchKernelGGL(k_capacity, dim3((unsigned)n_segs), dim3(CAP_TILE), 0, stream, d_gr, d_segs, d_out, d_profile);
     return (int)hipGetLastError();
 }
 

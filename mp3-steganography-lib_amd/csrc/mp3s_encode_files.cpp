@@ -80,14 +80,6 @@ static int resample_taps_dev(mp3s_ctx *c, int L, int M, const uint32_t **d_out)
     return MP3S_OK;
 }
 
-namespace {
-
-struct WavIn {
-    const uint8_t *wav; size_t len;
-    const uint8_t *hide; int n_hide;
-    WavPlan p;
-};
-
 // the files `idx` to the device: their images up, the batch's kernels (launch_wav_batch) queued on the context's stream -> *d_pcm_out =
 // [b.n_all][1152][2] int16 in the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is
 // waited for; the batch's records and the callers' bytes are read by copies in flight until the stream is synchronised.
@@ -128,6 +120,8 @@ int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<i
     *d_pcm_out = d_pcm;
     return MP3S_OK;
 }
+
+namespace {
 
 // the files `idx` (one sampling rate and bitrate) as one batch: images up, gather, encode_batch on the PCM in HBM.  The batch's
 // bytes are kept in a new part of `top`; out[i] points into it.

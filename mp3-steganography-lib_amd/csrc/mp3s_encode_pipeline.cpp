@@ -240,6 +240,11 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
                                    (mp3s_chain_seg_out *)((uint8_t *)d.d_small + kSmallHead), &c->prof, !c->opt[MP3S_OPT_REDO] || !L.redo ? nullptr : &redo);
         if (e) rc = fail(MP3S_E_HIP, "chain launch: %s", hipGetErrorString((hipError_t)e));
     }
+    // a job without its tail: the streams are counted where they would have been packed (the same assumption about the verdict)
+    if (!rc && d.d_cap) {
+        const int e = launch_capacity(ts, d.d_out, d_segs, L.n_segs, d.d_cap, d.d_profile);
+        return e ? fail(MP3S_E_HIP, "capacity launch: %s", hipGetErrorString((hipError_t)e)) : (int)MP3S_OK;
+    }
     // packed on the assumption that the verdict is "nothing to redo" (the common case); the caller discards it otherwise
     if (!rc) {
         const bool halves = d.direct_status && d.pack_half && d.pack_split > 0 && d.pack_split < L.n;
@@ -578,6 +583,61 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     return rc;
 }
 
+// encode_batch without its tail (mp3s_internal.h): same pool slots, minus the MP3 bytes and the scalefactor selection (16, 17); the small
+// block (18) holds [verdict, chain ends | capacity records | profile] so that one copy brings all of it down.
+int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, bool want_profile,
+                   mp3s_buf *b, CapacityBatch *out)
+{
+    *out = CapacityBatch();
+    EncLayout L;
+    int rc = enc_layout(segs, samplerate, bitrate_kbps, L, c->opt[MP3S_OPT_SELECT] != 0);
+    if (rc) return rc;
+    const int n = L.n, units = L.units, n_all = L.n_all;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint8_t> &in = c->h_in;
+    in.resize(L.bytes);
+    rc = enc_fill(segs, L, in.data());
+    if (rc) return rc;
+    const size_t o_cap = up16(small_bytes(L.n_segs)), o_prof = o_cap + (size_t)L.n_segs * sizeof(mp3s_capacity_seg),
+                 down_bytes = o_prof + (want_profile ? (size_t)n * 4 : 0);
+    void *d_in = c->grab(9, L.bytes), *d_mdct_all = c->grab(10, (size_t)n_all * 2304 * 4), *d_ix = c->grab(12, (size_t)n * 2304 * 2),
+         *d_out = c->grab(13, (size_t)units * sizeof(mp3s_gr_out)), *d_en = c->grab(14, (size_t)units * 22 * 4),
+         *d_agg = c->grab(15, chain_agg_bytes(n)), *d_small = c->grab(18, down_bytes);
+    auto cleanup = [&]() { hipStreamSynchronize(c->stream); };   // the buffers stay in the context's pool
+    if (!d_in || !d_mdct_all || !d_ix || !d_out || !d_en || !d_agg || !d_small) {
+        cleanup();
+        return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame encode", n);
+    }
+    if (!b->big[2].reserve(down_bytes)) {
+        cleanup();
+        return fail(MP3S_E_NOMEM, "host memory for a %d-frame encode", n);
+    }
+    uint8_t *const small8 = b->big[2].data();
+    const int32_t *const small = (const int32_t *)small8;
+    const mp3s_chain_seg_out *const seg_out = (const mp3s_chain_seg_out *)(small8 + kSmallHead);
+    if (hipMemcpyAsync(d_in, in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
+    EncDev dev;
+    dev.d_pcm = pcm_dev; dev.d_in = (const uint8_t *)d_in; dev.d_mdct_all = (int32_t *)d_mdct_all; dev.d_ix = (int16_t *)d_ix;
+    dev.d_out = (mp3s_gr_out *)d_out; dev.d_en = (int32_t *)d_en; dev.d_agg = d_agg; dev.d_small = (int32_t *)d_small;
+    dev.d_cap = (mp3s_capacity_seg *)((uint8_t *)d_small + o_cap);
+    dev.d_profile = want_profile ? (uint32_t *)((uint8_t *)d_small + o_prof) : nullptr;
+    if (!rc && !enc_variant_buffers(c, L, dev)) rc = fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
+    if (!rc) rc = enc_issue(c, L, dev);
+    if (!rc && hipMemcpyAsync(small8, d_small, down_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "sync failed");
+    if (rc) { cleanup(); return rc; }
+    out->down_bytes = down_bytes;
+    if (small[0] != 0 || small[1] != 0) {
+        if (trace_on()) fprintf(stderr, "mp3s: capacity of %d frames: %d units still to redo (step range %d) -> the full encode counts\n", n, small[0], small[1]);
+        return MP3S_OK;
+    }
+    for (size_t si = 0; si < segs.size(); si++) segs[si].hide_offset = seg_out[si].cursor - segs[si].hide_base;
+    out->counted = true;
+    out->seg = (const mp3s_capacity_seg *)(small8 + o_cap);
+    out->profile = want_profile ? (const uint32_t *)(small8 + o_prof) : nullptr;
+    return MP3S_OK;
+}
+
 extern "C" {
 
 static int encode_core(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, int64_t n_samples_per_ch, int nch, int samplerate,
@@ -673,7 +733,7 @@ int mp3s_encode_file(mp3s_ctx *c, const uint8_t *wav, size_t len, int bitrate_kb
 }
 
 // what the reference's WAV reader / encoder would say to the WAV its decoder writes for this stream
-static int reencode_check(const ParsedStream &p, int *kbps_out)
+extern "C++" int reencode_check(const ParsedStream &p, int *kbps_out)
 {
     const int kbps = p.bit_rate / 1000;
     int sri, bri, whole;
@@ -687,14 +747,12 @@ static int reencode_check(const ParsedStream &p, int *kbps_out)
     return MP3S_OK;
 }
 
-// Decode the streams `idx` of m (stereo, one sampling rate and bitrate) on the device into HBM and encode them from
-// there as one batch: steganography.py:133-182 without the temporary WAV.  bits[i] = framed message of file i (empty:
-// nothing hidden).  The batch's bytes are kept in a new part of `top`; out[i] points into it.
-static int reencode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, const std::vector<std::vector<uint8_t>> &bits,
-                          int samplerate, int kbps, mp3s_buf *top, mp3s_file *out)
+// The front half of reencode_group (mp3s_internal.h): the streams as segments of an encode batch, decoded on the device into HBM.
+extern "C++" int reencode_decode(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, const std::vector<std::vector<uint8_t>> &bits,
+                                 std::vector<EncSeg> &segs, std::vector<std::vector<uint8_t>> &guess, void **d_keep_out, int64_t *rows_frames_out)
 {
-    std::vector<EncSeg> segs(idx.size());
-    std::vector<std::vector<uint8_t>> guess(idx.size());
+    segs.assign(idx.size(), EncSeg());
+    guess.assign(idx.size(), std::vector<uint8_t>());
     int64_t rows_frames = 0;
     for (size_t k = 0; k < idx.size(); k++) {
         const ParsedStream &p = m.parsed[idx[k]];
@@ -711,8 +769,24 @@ static int reencode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &id
     if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
     void *d_keep = c->grab(7, (size_t)rows_frames * 2304 * 2);
     if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
+    const int rc = decode_group(c, m, idx, 2, MP3S_PCM_I16, d_keep);
+    if (rc) return rc;
+    *d_keep_out = d_keep; *rows_frames_out = rows_frames;
+    return MP3S_OK;
+}
+
+// Decode the streams `idx` of m (stereo, one sampling rate and bitrate) on the device into HBM and encode them from
+// there as one batch: steganography.py:133-182 without the temporary WAV.  bits[i] = framed message of file i (empty:
+// nothing hidden).  The batch's bytes are kept in a new part of `top`; out[i] points into it.
+static int reencode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, const std::vector<std::vector<uint8_t>> &bits,
+                          int samplerate, int kbps, mp3s_buf *top, mp3s_file *out)
+{
+    std::vector<EncSeg> segs;
+    std::vector<std::vector<uint8_t>> guess;
+    int64_t rows_frames = 0;
+    void *d_keep = nullptr;
     const double t0 = trace_on() ? now_ms() : 0;
-    int rc = decode_group(c, m, idx, 2, MP3S_PCM_I16, d_keep);
+    int rc = reencode_decode(c, m, idx, bits, segs, guess, &d_keep, &rows_frames);
     if (rc) return rc;
     if (trace_on()) hipStreamSynchronize(c->stream);
     const double t1 = trace_on() ? now_ms() : 0;

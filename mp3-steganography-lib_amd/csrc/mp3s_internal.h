@@ -407,13 +407,16 @@ struct EncDev {
     int pack_split = 0; hipEvent_t pack_half = nullptr;
     // results of the variant entries (L.n_entries of them; read by the selection right behind the rate loop)
     int16_t *d_ixv = nullptr; mp3s_gr_out *d_outv = nullptr; int32_t *d_env = nullptr;
+    // a job without its tail (capacity_batch): with d_cap set the job ends behind the chain check -- k_capacity writes the streams' records
+    // there (and the per-frame profile, when d_profile is given) and the bit packer is not launched: d_mp3, d_sc and the pack fields are unused
+    mp3s_capacity_seg *d_cap = nullptr; uint32_t *d_profile = nullptr;
 };
 // the entries of a stream's first `reach` units (variant-major, the two "bits left" rows from MP3S_SELECT_TAIL_FIRST on: mp3s.h)
 void select_entries(int first_unit, int reach, int first_entry, int hide_end, int64_t bits_left, int32_t *ent_unit, int32_t *ent_cursor);
 // device buffers for L.n_entries variant entries from the context's pool (slots of the host's variants, free at that point)
 bool enc_variant_buffers(mp3s_ctx *c, const EncLayout &L, EncDev &d);
-// transforms -> rate loop on the guessed cursors -> chain check -> bit packing, all on c->stream, nothing waited for.
-// The packed bytes are final iff verdict[0] == 0 and verdict[1] == 0 (d_small[0], d_small[1]).
+// transforms -> rate loop on the guessed cursors -> chain check -> bit packing (with d.d_cap: k_capacity in its place), all on c->stream,
+// nothing waited for.  The packed bytes (the capacity records) are final iff verdict[0] == 0 and verdict[1] == 0 (d_small[0], d_small[1]).
 int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail = nullptr /* chain check + packing on this stream, ordered behind the rate loop through tail_from */,
               hipEvent_t tail_from = nullptr, hipEvent_t rate_after = nullptr /* the rate loop waits for this event (the previous job's tail) */,
               hipEvent_t pcm_read = nullptr /* recorded behind the encode transforms: the PCM they read may be overwritten */);
@@ -424,6 +427,23 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
                 int *passes_out);
 int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps,
                  mp3s_buf *b, int *passes_out, bool want_gr = true);
+// encode_batch without its tail: the same inputs, transforms, rate loop (message variants, selection) and chain check with the device's
+// re-runs, then k_capacity instead of the bit packer.  No MP3 buffer on either side; ONE copy brings down [verdict and chain ends |
+// capacity records | profile (want_profile)] into b->big[2].  out.counted: the verdict was 0 -- out.seg[k] is stream k's record,
+// out.profile the batch's profile (stream k's part begins at segs[k].first; null without want_profile), both inside b, and every
+// segs[k].hide_offset is what encode_batch gives.  Not counted: the guesses did not hold and nothing else of `out` means anything -- the
+// caller runs the batch through encode_batch (want_gr) and counts from the host copy of the records; the PCM is still where it was.
+struct CapacityBatch { bool counted = false; const mp3s_capacity_seg *seg = nullptr; const uint32_t *profile = nullptr; size_t down_bytes = 0; };
+int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, bool want_profile,
+                   mp3s_buf *b, CapacityBatch *out);
+// what the reference's WAV reader / encoder would say to the WAV its decoder writes for this stream: MP3S_OK with *kbps_out, or the code
+// and text mp3s_hide_message / mp3s_clear_file fail with
+int reencode_check(const ParsedStream &p, int *kbps_out);
+// the front half of a re-encode batch: the streams `idx` of m (stereo, one sampling rate and bitrate) become segs (bits[i] = framed
+// message of file i, empty: nothing hidden; guess keeps the table counts segs point into) and are decoded on the device into
+// *d_keep_out, int16 PCM that stays in HBM (pool slot 7), *rows_frames frames back to back
+int reencode_decode(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, const std::vector<std::vector<uint8_t>> &bits,
+                    std::vector<EncSeg> &segs, std::vector<std::vector<uint8_t>> &guess, void **d_keep_out, int64_t *rows_frames);
 // non-zero table indices per unit of a scanned stream, in the encoder's unit order (frame, channel, granule): see
 // EncSeg::tables_guess; `extra` more frames (the repeated last frame of a stream that ends in a bad header) repeat the last
 // mp3s_select_plan with a lower limit for each stream's reach (nullptr: none)
@@ -452,6 +472,17 @@ struct WavPlan {
 struct WavRead { bool import = false; int resample = 0; };
 WavRead wav_read_of(const mp3s_ctx *c);
 int wav_encode_plan(WavRead how, const uint8_t *wav, size_t len, int bitrate_kbps, const uint8_t *hide_bits, int n_hide, WavPlan *p);
+// a WAV file of a list call: its bytes, its message, its plan
+struct WavIn {
+    const uint8_t *wav; size_t len;
+    const uint8_t *hide; int n_hide;
+    WavPlan p;
+};
+struct WavBatch;
+// the files `idx` to the device: their images up, the batch's kernels (launch_wav_batch) queued on the context's stream -> *d_pcm_out =
+// [b.n_all][1152][2] int16 in the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is
+// waited for; the batch's records and the callers' bytes are read by copies in flight until the stream is synchronised.
+int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, WavBatch &b, void **d_pcm_out);
 // mp3s_encode_files with the reader named by the caller
 int encode_files_as(mp3s_ctx *c, WavRead how, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
                     const uint8_t *const *hide_bits, const int32_t *n_hide, mp3s_buf **owner, mp3s_file *out, int32_t *status);

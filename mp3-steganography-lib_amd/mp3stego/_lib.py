@@ -140,6 +140,16 @@ class File(C.Structure):
                 ("hide_offset", C.c_int64), ("bits", C.c_void_p)]
 
 
+class Capacity(C.Structure):
+    """mp3s_capacity: what mp3s_capacity_files / mp3s_capacity_wavs answer per file"""
+    _fields_ = [("bits", C.c_int64), ("hide_offset", C.c_int64), ("text_bytes", C.c_int64), ("too_long", C.c_int32), ("n_frames", C.c_int32),
+                ("kbps", C.c_int32), ("sampling_rate", C.c_int32), ("channels", C.c_int32), ("active_units", C.c_int32),
+                ("fallback", C.c_int32), ("reserved", C.c_int32), ("profile", C.c_void_p)]
+
+
+CAPACITY_SEG_DTYPE = np.dtype([("bits", "<i8"), ("active_units", "<i4"), ("reserved", "<i4")])
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_frames", C.c_int64), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
                 ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("reserved", C.c_int32)]
@@ -192,7 +202,8 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_pipe_create", "mp3s_pipe_destroy", "mp3s_pipe_submit", "mp3s_pipe_submit_decode", "mp3s_pipe_collect", "mp3s_pipe_get_stats",
            "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
            "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps",
-           "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages"]
+           "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages",
+           "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes"]
 
 REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
 RV_BAD_REF = 1
@@ -305,6 +316,11 @@ def lib():
         L.mp3s_reveal_bits_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, i32, vp, vp, vp, vp]
         L.mp3s_reveal_messages.argtypes = [vp, vp, vp, i32, pvp, vp, vp]
         L.mp3s_debug_reveal_messages.argtypes = [vp, vp, vp, i32, i32, pvp, vp, vp]
+        L.mp3s_capacity_dev.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.mp3s_capacity_files.argtypes = [vp, vp, vp, i32, vp, vp, i32, pvp, vp, vp]
+        L.mp3s_capacity_wavs.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, pvp, vp, vp]
+        L.mp3s_capacity_text_bytes.argtypes = [i64]
+        L.mp3s_capacity_text_bytes.restype = i64
         L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
@@ -870,6 +886,64 @@ class Context:
             "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
             "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)})
 
+    @staticmethod
+    def _capacity(x, own):
+        return {"bits": x.bits, "hide_offset": x.hide_offset, "text_bytes": x.text_bytes, "too_long": bool(x.too_long),
+                "n_frames": x.n_frames, "kbps": x.kbps, "sampling_rate": x.sampling_rate, "channels": x.channels,
+                "active_units": x.active_units, "fallback": x.fallback,
+                "profile": _view_owned(x.profile, np.uint32, (x.n_frames,), own) if x.profile else None}
+
+    def capacities(self, mp3s, messages=None, profile=False):
+        """how many message bits each of a list of MP3 files takes (mp3s_capacity_files): the re-encode of hide_messages up to its chain
+        check, counted by k_capacity -- no MP3 bytes are made.  messages: one str (or None: the clear capacity, an estimate) per file,
+        or None for none anywhere; with a message "hide_offset" / "too_long" are those of hide_messages.  profile: "profile" = the
+        per-frame running sum of the bits, uint32 [n_frames].  Returns one entry per file: a dict, or the Mp3sError hide_messages gives."""
+        if messages is not None and len(mp3s) != len(messages):
+            raise ValueError("one message (or None) per file")
+        if len(mp3s) == 0:
+            return []
+        n, _keep, files, lens = _file_list(mp3s)
+        mptr = mlen = None
+        if messages is not None:
+            msgs = [None if t is None else np.frombuffer(t.encode("utf-8") or b"\0", dtype=np.uint8) for t in messages]
+            mptr = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in msgs])
+            mlen = (C.c_size_t * n)(*[0 if t is None else len(t.encode("utf-8")) for t in messages])
+        out, status, owner = (Capacity * n)(), (C.c_int32 * n)(), C.c_void_p()
+        check(lib().mp3s_capacity_files(self.handle, files, lens, n, mptr, mlen, 1 if profile else 0, C.byref(owner), out, status))
+        own = _Owner(owner)
+        return _per_file(out, status, lambda x: self._capacity(x, own))
+
+    def wav_capacities(self, wavs, bitrate=320, hide_bits=None, messages=None, profile=False):
+        """capacities() for a list of WAV files (mp3s_capacity_wavs), arguments as for encode_files: the encode of encode_files up to
+        its chain check.  With hide_bits / messages "hide_offset" / "too_long" are those of encode_files."""
+        if len(wavs) == 0:
+            return []
+        n, files, lens, kbps, hptr, hlen, keep = _encode_args(wavs, bitrate, hide_bits, messages)
+        out, status, owner = (Capacity * n)(), (C.c_int32 * n)(), C.c_void_p()
+        check(lib().mp3s_capacity_wavs(self.handle, files, lens, n, kbps, hptr, hlen, 1 if profile else 0, C.byref(owner), out, status))
+        own = _Owner(owner)
+        del keep
+        return _per_file(out, status, lambda x: self._capacity(x, own))
+
+    def capacity_dev(self, gr, segs, profile=True):
+        """test aid: k_capacity alone (mp3s_capacity_dev) on the GR_OUT_DTYPE records `gr` and the CHAIN_SEG_DTYPE streams `segs`
+        -> (CAPACITY_SEG_DTYPE [len(segs)], uint32 [frames] or None)"""
+        gr = np.ascontiguousarray(gr, dtype=GR_OUT_DTYPE)
+        segs = np.ascontiguousarray(segs, dtype=CHAIN_SEG_DTYPE)
+        n_frames = len(gr) // 4
+        d_gr, d_segs = self.to_device(gr if len(gr) else np.zeros(1, dtype=GR_OUT_DTYPE)), self.to_device(segs)
+        d_out = self.alloc(len(segs) * CAPACITY_SEG_DTYPE.itemsize)
+        d_prof = self.alloc(max(n_frames, 1) * 4) if profile else None
+        try:
+            check(lib().mp3s_capacity_dev(self.handle, d_gr, d_segs, len(segs), d_out, d_prof))
+            out = self.download(d_out, CAPACITY_SEG_DTYPE, (len(segs),))
+            prof = self.download(d_prof, np.uint32, (n_frames,)) if profile else None
+        finally:
+            for p in (d_gr, d_segs, d_out, d_prof):
+                if p is not None:
+                    self.free(p)
+        return out, prof
+
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
         n, files, lens, _, _, _, keep = _encode_args(wavs, 128, None, None)
@@ -1088,6 +1162,11 @@ def reveal_message(mp3: bytes):
     r = Context._file(f, owner)
     r["data"] = bytes(r["data"])               # a message, not a file: plain bytes
     return r
+
+
+def capacity_text_bytes(bits):
+    """the longest ASCII message, in bytes, whose frame "<n>#..." takes at most bits + 1 message bits (mp3s_capacity_text_bytes)"""
+    return int(lib().mp3s_capacity_text_bytes(int(bits)))
 
 
 def wav_parse(data: bytes, bitrate=320):
