@@ -103,6 +103,12 @@ int orc_enc_rate_unit(OrcEncoder *e, int max_bits, const int32_t *xr576, int32_t
 /* test hook: one probe of the binary search's body (:973-990) at `step` on n spectra, fresh GrInfo; bits -1 = step outside steptab / silence */
 void orc_enc_probe_bits(OrcEncoder *e, long n, int step, const int32_t *xr, int32_t *bits, int32_t *big_values, int32_t *count1);
 void orc_enc_rate_units(OrcEncoder *e, long n, const int32_t *max_bits, const int32_t *xr, int32_t *ix, OrcGrInfo *out, int32_t *rc);
+/* test hook: the same loop for units in the middle of a stream: state_in [n][4] = inherited address1..3 and quantizerStepSize, hide_off [n] =
+ * cursor at the unit's start, hide_end [n] = the message ends at min(n_hide, hide_end); advance [n] = the cursor's advance, en22 [n][22] =
+ * calc_scfsi's en[gr][0..20], en_tot[gr] */
+void orc_enc_rate_units_from(OrcEncoder *e, long n, const int32_t *max_bits, const int32_t *xr, const int32_t *state_in,
+                             const int32_t *hide_off, const int32_t *hide_end, int32_t *ix, OrcGrInfo *out, int32_t *rc,
+                             int32_t *advance, int32_t *en22);
 void orc_enc_window_filter_subband(int32_t *s32, int32_t *x512, int32_t *off);
 int32_t orc_enc_quantize(int32_t *ix, int step_size, int32_t xrmax, const int32_t *xr, const int32_t *xrabs);
 

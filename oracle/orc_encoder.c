@@ -516,6 +516,40 @@ void orc_enc_rate_units(OrcEncoder *e, long n, const int32_t *max_bits, const in
     for (long i = 0; i < n; i++) rc[i] = orc_enc_rate_unit(e, max_bits[i], xr + i * 576, ix + i * 576, out + i);
 }
 
+/* Test hook: the rate loop of n granule*channels as units in the MIDDLE of a stream see it.  Unit i runs iterate_unit on a GrInfo preset with
+ * what the same (gr, ch) of the frame before left -- state_in[i] = address1, address2, address3, quantizerStepSize, none of which the
+ * reference resets (:788-803) -- with the message cursor at hide_off[i], and with the message `e` was made with cut at
+ * min(n_hide, hide_end[i]): bits at or beyond that are not there (:1257-1263 swap only while idx < len(hide_str)).  Per unit: ix (unsigned),
+ * the GrInfo with the addresses as left behind, rc (0 or ORC_ERR_STEP_RANGE), advance = what the unit added to the cursor (:808-809), and
+ * en22 = en[gr][0..20], en_tot[gr] of calc_scfsi (:840-857). */
+void orc_enc_rate_units_from(OrcEncoder *e, long n, const int32_t *max_bits, const int32_t *xr, const int32_t *state_in,
+                             const int32_t *hide_off, const int32_t *hide_end, int32_t *ix, OrcGrInfo *out, int32_t *rc,
+                             int32_t *advance, int32_t *en22)
+{
+    const long n_hide = e->n_hide;
+    for (long i = 0; i < n; i++) {
+        if (e->error) { rc[i] = e->error; continue; }
+        OrcGrInfo *c = &e->gi[0][0];
+        memcpy(e->mdct_freq[0][0], xr + i * 576, 576 * sizeof(int32_t));
+        memset(c, 0, sizeof *c);
+        memset(e->l3_enc[0][0], 0, sizeof e->l3_enc[0][0]);
+        c->address1 = state_in[4 * i + 0]; c->address2 = state_in[4 * i + 1]; c->address3 = state_in[4 * i + 2];
+        c->quantizerStepSize = state_in[4 * i + 3];
+        e->hide_off = hide_off[i];
+        e->n_hide = hide_end[i] < n_hide ? (hide_end[i] > 0 ? hide_end[i] : 0) : n_hide;
+        e->mean_bits = max_bits[i] * e->nch;
+        iterate_unit(e, 0, 0);
+        e->n_hide = n_hide;
+        memcpy(ix + i * 576, e->l3_enc[0][0], 576 * sizeof(int32_t));
+        out[i] = *c;
+        advance[i] = (int32_t)(e->hide_off - hide_off[i]);
+        memcpy(en22 + i * 22, e->en[0], 21 * sizeof(int32_t));
+        en22[i * 22 + 21] = e->en_tot[0];
+        rc[i] = e->error;
+        e->error = 0;
+    }
+}
+
 /* MP3_Encoder.py:1362-1392 */
 static void put_bits(OrcEncoder *e, uint32_t val, int N)
 {

@@ -99,6 +99,8 @@ def lib():
     L.orc_enc_quantize.restype = i32
     L.orc_enc_rate_units.argtypes = [vp, i64, ip, ip, ip, vp, ip]
     L.orc_enc_rate_units.restype = None
+    L.orc_enc_rate_units_from.argtypes = [vp, i64, ip, ip, ip, ip, ip, ip, vp, ip, ip, ip]
+    L.orc_enc_rate_units_from.restype = None
     L.orc_enc_probe_bits.argtypes = [vp, i64, i32, ip, ip, ip, ip]
     L.orc_enc_probe_bits.restype = None
     _lib = L
@@ -198,6 +200,34 @@ def rate_units(samplerate: int, max_bits: np.ndarray, xr: np.ndarray, hide_bits=
     finally:
         L.orc_enc_free(e)
     return {"ix": ix, "gi": gi, "rc": rc}
+
+
+def rate_units_from(samplerate: int, max_bits, xr: np.ndarray, state=None, hide_bits=None, cursor=None, hide_end=None):
+    """The same loop on n spectra as units in the middle of a stream see it: `state` int32 [n][4] = the (address1, address2, address3,
+    quantizerStepSize) the unit inherits (None: zeros), `cursor` [n] = the message cursor at its start (None: 0), `hide_end` [n] or one number:
+    the message ends at min(len(hide_bits), hide_end) (None: its own length).  Returns rate_units' three and "advance": int32 [n] (what the unit
+    added to the cursor), "en": int32 [n][22] (calc_scfsi's en[gr][0..20], en_tot[gr])."""
+    L = lib()
+    xr = np.ascontiguousarray(xr, dtype=np.int32).reshape(-1, 576)
+    n = xr.shape[0]
+
+    def per_unit(v, fill, shape):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(fill if v is None else v, dtype=np.int32), shape))
+    mb = per_unit(max_bits, 0, (n,))
+    st = per_unit(state, 0, (n, 4))
+    cur = per_unit(cursor, 0, (n,))
+    end = per_unit(hide_end, 2 ** 31 - 1, (n,))
+    hb = None if hide_bits is None or len(hide_bits) == 0 else bytes(int(b) + 48 for b in hide_bits)
+    e = L.orc_enc_new(samplerate, 2, 128, hb, 0 if hb is None else len(hb))
+    try:
+        ix = np.zeros((n, 576), dtype=np.int32)
+        gi = np.zeros(n, dtype=GRINFO_DTYPE)
+        rc, adv = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        en = np.zeros((n, 22), dtype=np.int32)
+        L.orc_enc_rate_units_from(e, n, mb, xr, st, cur, end, ix, gi.ctypes.data, rc, adv, en)
+    finally:
+        L.orc_enc_free(e)
+    return {"ix": ix, "gi": gi, "rc": rc, "advance": adv, "en": en}
 
 
 def probe_bits(samplerate: int, step: int, xr: np.ndarray):

@@ -48,3 +48,77 @@ def sparse_spectra(seed, n, base=32768):
             top = int(rng.integers(1, 200))
             xr[i, :top] = amp(top, 0.9, 1.9) * signs(top) * (rng.random(top) < 0.7)
     return np.clip(xr, -(2 ** 31 - 1), 2 ** 31 - 1).astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Families for the per-unit tests of the rate loop (tests/test_rate_units.py).  The quantiser (MP3_Encoder.py:373-415) takes
+# ln = round(|xr| / (2 * base)) and gives int(ln ** 0.75 - 0.0946 + 0.5) below ln = 10000, int((|xr| / (2 * base)) ** 0.75) from there on,
+# `base` being as above the |xr| that quantises to 1 at the aimed step (2 ** (30 + step / 4)).
+
+# the boundaries of the table choice (MP3_Encoder.py:1170-1264): below 15 by x_len, 15 = the first escape, then 15 + linmax and one more for
+# every linmax of books 16-23 and 24-31, and the two values around which quantize refuses (:392)
+EDGE_VALUES = (1, 2, 3, 5, 7, 14, 15) + tuple(15 + m + d for m in (1, 3, 7, 15, 63, 255, 1023, 8191) for d in (0, 1)) + (8192, 8193)
+
+
+def level_of(v):
+    """|xr| / base in the middle of the quantiser's bucket for the value v >= 1"""
+    if v == 8192:       # the last value quantize lets through: ln 165140.39 (8192 ** (4 / 3)) .. 165140.5 (rounds to 165140, the limit of :392)
+        return 2.0 * 165140.45
+    ln = (v + 0.0946) ** (4.0 / 3.0)
+    if ln < 9000:
+        ln = max(np.rint(ln), 1.0)
+        assert int(ln ** 0.75 - 0.0946 + 0.5) == v, v
+        return 2.0 * ln
+    return 2.0 * (v + 0.5) ** (4.0 / 3.0)
+
+
+def _finish(xr):
+    return np.clip(np.rint(xr), -(2 ** 31 - 1), 2 ** 31 - 1).astype(np.int32)
+
+
+def quiet(seed, n, base=32768):
+    """n spectra whose lines all quantise to 0 or 1 at the aimed step, so that the final step or some probe of the search has big_values == 0
+    and keeps the addresses it inherited (__subdivide, MP3_Encoder.py:1004-1006).  Density from a single line to all 576; every third spectrum
+    has its ones only above line 400."""
+    rng = np.random.default_rng(seed)
+    xr = np.zeros((n, 576))
+    for i in range(n):
+        lo = 400 if i % 3 == 2 else 0
+        m = 576 - lo
+        k = (1, m)[i % 7 == 3] if i % 7 in (0, 3) else int(np.ceil(m * np.exp(rng.uniform(np.log(1.0 / m), 0.0))))
+        p = lo + rng.choice(m, k, replace=False)
+        xr[i, p] = base * rng.uniform(1.02, 2.9, k) * (rng.integers(0, 2, k) * 2 - 1)
+    return _finish(xr)
+
+
+def escape_edges(seed, n, base=32768):
+    """n spectra of one to four lines whose largest value at the aimed step is EDGE_VALUES[i % len(EDGE_VALUES)], the other peaks anywhere
+    below it, over low-level noise (values 0, 1 and a few 2 on a part of the lines).  A peak that does not fit into 31 bits is clipped."""
+    rng = np.random.default_rng(seed)
+    xr = np.zeros((n, 576))
+    for i in range(n):
+        v = EDGE_VALUES[i % len(EDGE_VALUES)]
+        dens = rng.uniform(0.0, 0.25)
+        noisy = rng.random(576) < dens
+        xr[i, noisy] = base * rng.uniform(0.3, 3.4 if v > 1 else 2.9, int(noisy.sum()))
+        m = int(rng.integers(1, 5))
+        p = rng.choice(576, m, replace=False) if i % 2 else rng.choice(200, m, replace=False)
+        vals = np.concatenate([[v], rng.integers(1, v + 1, m - 1)])
+        xr[i, p] = [base * level_of(int(x)) for x in vals]
+        xr[i] *= rng.integers(0, 2, 576) * 2 - 1
+    return _finish(xr)
+
+
+def ties(seed, n, base=32768):
+    """n dense spectra of the values 0..3 at the aimed step, each with its own share of zeros (book 13 codes a pair of zeros in one bit, book
+    15 in three) and its own mix of the rest, up to a line of its own: the bit sums of the two candidate books of a region (13 and 15 below
+    15: MP3_Encoder.py:1190-1231 -- x_len 16 of book 13 ends the scan at once) come close to each other and meet exactly."""
+    rng = np.random.default_rng(seed)
+    lv = np.array([0.5] + [level_of(v) for v in (1, 2, 3)])
+    xr = np.zeros((n, 576))
+    for i in range(n):
+        z = rng.uniform(0.35, 0.65)              # (where the two sums of a region are close: book 15 wins below, 13 above)
+        w = np.concatenate([[z], (1.0 - z) * rng.dirichlet(np.ones(3))])
+        top = int(rng.integers(8, 577))
+        xr[i, :top] = base * lv[rng.choice(4, top, p=w)] * (rng.integers(0, 2, top) * 2 - 1)
+    return _finish(xr)
