@@ -928,6 +928,50 @@ int mp3s_capacity_wavs(mp3s_ctx *ctx, const uint8_t *const *wavs, const size_t *
 /* text_bytes of a bit count (host only, no context): "1#a" is 24 bits, so 0 below 23 */
 int64_t mp3s_capacity_text_bytes(int64_t bits);
 
+/* ---------------------------------------------------------------- (vi-c) what hiding changed: exact PCM difference of MP3 file pairs
+ * replaces: decoding both files (mp3s_decode_streams), pulling every PCM sample to the host -- 4.6 KB per frame and file -- and
+ *           subtracting in numpy.  Both PCM arrays are in HBM after the decode; they are compared there and a few bytes per pair come down.
+ * Which pair to compare: a re-encode delays the audio by the codec's delay, so a cover file and its stego file are NOT sample-aligned
+ * and their raw difference means nothing.  The meaningful pair is the CLEAR re-encode (mp3s_clear_file) against the HIDE re-encode
+ * (mp3s_hide_message) of the same input: the same delay, frames and bitrate, only the swapped Huffman tables differ.  The calls below
+ * compare any two lists pairwise at lag 0 (there is no lag argument); the Python facade's hide_distortions builds exactly that pair.
+ * Everything is exact integer arithmetic on int16 PCM, [frame][1152][nch] interleaved; per sample d = a - b:
+ *   err2 = sum d^2, sig2 = sum a^2, max_abs = max |d|, n_diff = samples with d != 0, first_diff = the smallest interleaved sample index
+ *   with d != 0 (inside the frame: 0xFFFFFFFF for none; of a pair: counted from its first compared sample, -1 for none).
+ * The results are bit for bit what numpy computes in int64. */
+typedef struct { uint32_t a_first, b_first, n_frames, out_first; } mp3s_pcm_pair;            /* 16 bytes: frames of 1152 rows in d_pcm; records at d_frames[out_first ..] */
+typedef struct { uint64_t err2, sig2; uint32_t max_abs, n_diff, first_diff, reserved; } mp3s_pcm_frame_diff;   /* 32 bytes */
+typedef struct { uint64_t err2, sig2, n_diff; int64_t first_diff; uint32_t max_abs, reserved; } mp3s_pcm_pair_diff; /* 40 bytes */
+/* the two kernels alone (k_pcmdiff.hpp), asynchronous on the context's stream: frames [a_first, a_first + n_frames) against frames
+ * [b_first, ...) of d_pcm (int16, nch = 1 or 2, 16-byte aligned) for every pair; pass 1 writes the frame records of pair p to
+ * d_frames[out_first .. out_first + n_frames) (the ranges of different pairs must not overlap), pass 2 the pair records d_out[n_pairs].
+ * A pair of 0 frames gets a zero record with first_diff -1.  h_pairs is the same table on the host: the launch geometry needs the frame
+ * counts (pass 1 runs one wave per compared frame, spread over the device whatever the mix of long and short pairs is); it is read
+ * before the call returns, the table made from it travels on the stream from a buffer the context keeps -- a second call on the context
+ * waits for the first one's table to have left.  Null pointers, n_pairs <= 0, another nch or a misaligned d_pcm: MP3S_E_ARG (checked
+ * without a device). */
+int mp3s_pcm_diff_dev(mp3s_ctx *ctx, const int16_t *d_pcm, int nch, const mp3s_pcm_pair *d_pairs, const mp3s_pcm_pair *h_pairs,
+                      int n_pairs, mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out);
+typedef struct {
+    uint64_t err2, sig2; int64_t n_samples, n_diff, first_diff, rows_a, rows_b;
+    uint32_t max_abs; int32_t channels, sampling_rate, n_frames;   /* n_frames = frames compared = min of the two */
+    double snr_db, psnr_db;
+    const mp3s_pcm_frame_diff *profile;  /* [n_frames] or NULL */
+} mp3s_pcm_distortion;
+/* File a[i] against file b[i], for a list of pairs, on the frame of the list-of-files calls: all 2 n files are scanned on the host
+ * threads; the valid pairs are grouped by channel count, and per group ONE decode batch (int16, as mp3s_decode_streams decodes) leaves
+ * the PCM of all its A and B streams in one device buffer, the two kernels run behind it on the same stream, and one small copy brings
+ * the pair records down -- and the frame records when want_profile != 0 (out[i].profile, owned by *owner).  No PCM comes down.
+ * Streams of different length compare their common prefix: n_frames = the smaller frame count, n_samples = n_frames * 1152 * channels;
+ * rows_a / rows_b = both lengths in rows, the frame the decoder repeats after a bad header included, as mp3s_decoded.n_rows counts it
+ * (that frame is PCM like any other and is compared).  The host derives, in double, from the exact integers:
+ *   snr_db = 10 log10(sig2 / err2), psnr_db = 10 log10(32767^2 n_samples / err2); both +infinity when err2 == 0.
+ * status[i] / mp3s_last_error() by the rule of mp3s_hide_messages: a pair one of whose files fails its front end gets that file's code
+ * (MP3S_E_ARG for a null file), a pair whose files differ in channel count or sampling rate MP3S_E_UNSUPPORTED with a text naming both
+ * values; the other pairs are unaffected; with status == NULL the first failing pair's code fails the call. */
+int mp3s_pcm_distortion_files(mp3s_ctx *ctx, const uint8_t *const *a, const size_t *a_lens, const uint8_t *const *b, const size_t *b_lens,
+                              int n_pairs, int want_profile, mp3s_buf **owner, mp3s_pcm_distortion *out, int32_t *status);
+
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference
  *           steganography.py:133-182, whose two serial frame loops (decoder/MP3_Parser.py:68-80, encoder/MP3_Encoder.py:

@@ -171,6 +171,7 @@ void mp3s_ctx_destroy(mp3s_ctx *c)
     if (c->ev1) hipEventDestroy(c->ev1);
     if (c->ev_order) hipEventDestroy(c->ev_order);
     if (c->ev_sel) hipEventDestroy(c->ev_sel);
+    if (c->ev_pcm_tiles) hipEventDestroy(c->ev_pcm_tiles);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }

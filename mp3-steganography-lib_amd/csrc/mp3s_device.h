@@ -123,6 +123,26 @@ int launch_reveal(hipStream_t stream, const uint8_t *d_image, uint32_t image_bas
 // record, and with d_profile (optional, [frames of the batch]) per frame the running sum of the stream's bits up to and including it
 int launch_capacity(hipStream_t stream, const mp3s_gr_out *d_gr, const mp3s_chain_seg *d_segs, int n_segs, mp3s_capacity_seg *d_out, uint32_t *d_profile);
 
+// the exact difference of pairs of frame runs of one int16 PCM buffer [frame][1152][nch] (k_pcmdiff.hpp): pass 1 writes a record per
+// compared frame (pair p's at d_frames[out_first ..]), pass 2 a record per pair.  Pass 1 takes kPcmDiffWaves frames to a workgroup and
+// finds them in d_tiles, which the host makes from the pairs' frame counts (pcm_diff_tiles; n_tiles = the grid): a pair of 0 frames has
+// no tile and gets its (zero) record from pass 2.  d_pcm must be 16-byte aligned.
+constexpr int kPcmDiffWaves = 4;
+struct PcmTile { uint32_t pair, first; };   // 8 bytes: frames [first, first + kPcmDiffWaves) of pair `pair`, cut at its n_frames
+// appends the tiles of pairs[0 .. n_pairs) to `tiles` (anything with push_back); false: more tiles than a grid takes
+template <class Tiles>
+bool pcm_diff_tiles(const mp3s_pcm_pair *pairs, int n_pairs, Tiles &tiles)
+{
+    uint64_t n = tiles.size();
+    for (int p = 0; p < n_pairs; p++) n += ((uint64_t)pairs[p].n_frames + kPcmDiffWaves - 1) / kPcmDiffWaves;
+    if (n > 0x7fffffffu) return false;
+    for (int p = 0; p < n_pairs; p++)
+        for (uint64_t f = 0; f < pairs[p].n_frames; f += kPcmDiffWaves) tiles.push_back(PcmTile{(uint32_t)p, (uint32_t)f});
+    return true;
+}
+int launch_pcm_diff(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_pair *d_pairs, int n_pairs, const PcmTile *d_tiles, int n_tiles,
+                    mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out);
+
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes

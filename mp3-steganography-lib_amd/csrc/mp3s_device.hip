@@ -24,6 +24,7 @@ __constant__ DevTables c_tab;
 #include "k_parse.hpp"
 #include "k_reveal.hpp"
 #include "k_capacity.hpp"
+#include "k_pcmdiff.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
@@ -403,6 +404,21 @@ int launch_capacity(hipStream_t stream, const mp3s_gr_out *d_gr, const mp3s_chai
 {
     if (n_segs <= 0) return 0;
     hipLaunchKernelGGL(k_capacity, dim3((unsigned)n_segs), dim3(CAP_TILE), 0, stream, d_gr, d_segs, d_out, d_profile);
+    return (int)hipGetLastError();
+}
+
+// k_pcm_diff_frames: one workgroup per tile of d_tiles (one wave per frame); k_pcm_diff_pairs behind it: one workgroup per pair
+int launch_pcm_diff(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_pair *d_pairs, int n_pairs, const PcmTile *d_tiles, int n_tiles,
+                    mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out)
+{
+    if (n_pairs <= 0) return 0;
+    if ((nch != 1 && nch != 2) || ((uintptr_t)d_pcm & 15)) return (int)hipErrorInvalidValue;
+    if (n_tiles > 0) {
+        if (nch == 2) hipLaunchKernelGGL(k_pcm_diff_frames<2>, dim3((unsigned)n_tiles), dim3(PCMDIFF_WAVES * 64), 0, stream, d_pcm, d_pairs, d_tiles, d_frames);
+        else hipLaunchKernelGGL(k_pcm_diff_frames<1>, dim3((unsigned)n_tiles), dim3(PCMDIFF_WAVES * 64), 0, stream, d_pcm, d_pairs, d_tiles, d_frames);
+        if (const hipError_t e = hipGetLastError()) return (int)e;
+    }
+    hipLaunchKernelGGL(k_pcm_diff_pairs, dim3((unsigned)n_pairs), dim3(PCMDIFF_TILE), 0, stream, d_pairs, d_frames, nch, d_out);
     return (int)hipGetLastError();
 }
 

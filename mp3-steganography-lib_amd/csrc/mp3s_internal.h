@@ -85,6 +85,10 @@ struct mp3s_ctx {
     // ... and the frame table / table counts of the file run_file is working on
     std::vector<FrameRef> h_refs;
     std::vector<uint8_t> h_tables;
+    // ... and the workgroup table of the last mp3s_pcm_diff_dev, which travels on the stream behind the call: ev_pcm_tiles (made on first
+    // use) is recorded behind its copy, the next call waits for it before it writes the table again
+    std::vector<PcmTile> h_pcm_tiles;
+    hipEvent_t ev_pcm_tiles = nullptr;
     int ensure_scratch(size_t bytes)
     {
         if (bytes <= scratch_bytes) return 0;

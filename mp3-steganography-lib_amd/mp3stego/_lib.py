@@ -150,6 +150,33 @@ class Capacity(C.Structure):
 CAPACITY_SEG_DTYPE = np.dtype([("bits", "<i8"), ("active_units", "<i4"), ("reserved", "<i4")])
 
 
+class PcmDistortion(C.Structure):
+    """mp3s_pcm_distortion: what mp3s_pcm_distortion_files answers per pair"""
+    _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("n_samples", C.c_int64), ("n_diff", C.c_int64), ("first_diff", C.c_int64),
+                ("rows_a", C.c_int64), ("rows_b", C.c_int64), ("max_abs", C.c_uint32), ("channels", C.c_int32), ("sampling_rate", C.c_int32),
+                ("n_frames", C.c_int32), ("snr_db", C.c_double), ("psnr_db", C.c_double), ("profile", C.c_void_p)]
+
+
+class PcmPair(C.Structure):
+    _fields_ = [("a_first", C.c_uint32), ("b_first", C.c_uint32), ("n_frames", C.c_uint32), ("out_first", C.c_uint32)]
+
+
+class PcmFrameDiff(C.Structure):
+    _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("max_abs", C.c_uint32), ("n_diff", C.c_uint32), ("first_diff", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PcmPairDiff(C.Structure):
+    _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("n_diff", C.c_uint64), ("first_diff", C.c_int64), ("max_abs", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+PCM_PAIR_DTYPE = np.dtype([("a_first", "<u4"), ("b_first", "<u4"), ("n_frames", "<u4"), ("out_first", "<u4")])
+PCM_FRAME_DIFF_DTYPE = np.dtype([("err2", "<u8"), ("sig2", "<u8"), ("max_abs", "<u4"), ("n_diff", "<u4"), ("first_diff", "<u4"), ("reserved", "<u4")])
+PCM_PAIR_DIFF_DTYPE = np.dtype([("err2", "<u8"), ("sig2", "<u8"), ("n_diff", "<u8"), ("first_diff", "<i8"), ("max_abs", "<u4"), ("reserved", "<u4")])
+NO_DIFF = 0xFFFFFFFF         # mp3s_pcm_frame_diff.first_diff of a frame without a differing sample
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_frames", C.c_int64), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
                 ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("reserved", C.c_int32)]
@@ -203,7 +230,8 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
            "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps",
            "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages",
-           "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes"]
+           "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes",
+           "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files"]
 
 REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
 RV_BAD_REF = 1
@@ -321,6 +349,8 @@ def lib():
         L.mp3s_capacity_wavs.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, pvp, vp, vp]
         L.mp3s_capacity_text_bytes.argtypes = [i64]
         L.mp3s_capacity_text_bytes.restype = i64
+        L.mp3s_pcm_diff_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp]
+        L.mp3s_pcm_distortion_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, pvp, vp, vp]
         L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
@@ -943,6 +973,65 @@ class Context:
                 if p is not None:
                     self.free(p)
         return out, prof
+
+    @staticmethod
+    def _distortion(x, own):
+        return {"err2": x.err2, "sig2": x.sig2, "n_samples": x.n_samples, "n_diff": x.n_diff, "first_diff": x.first_diff,
+                "rows_a": x.rows_a, "rows_b": x.rows_b, "max_abs": x.max_abs, "channels": x.channels, "sampling_rate": x.sampling_rate,
+                "n_frames": x.n_frames, "snr_db": x.snr_db, "psnr_db": x.psnr_db,
+                "profile": _view_owned(x.profile, PCM_FRAME_DIFF_DTYPE, (x.n_frames,), own) if x.profile else None}
+
+    def pcm_distortions(self, mp3s_a, mp3s_b, profile=False):
+        """the exact int16 PCM difference of mp3s_a[i] against mp3s_b[i] (mp3s_pcm_distortion_files): both lists are decoded on the
+        device, compared there at lag 0 over their common prefix, and a record per pair comes down -- no PCM does.  A cover file and
+        its stego file are not sample-aligned (the codec's delay); compare the clear re-encode with the hide re-encode of one input
+        (hide_distortions).  profile: "profile" = a PCM_FRAME_DIFF_DTYPE record per compared frame.  Returns one entry per pair: a
+        dict (the fields of mp3s_pcm_distortion), or the Mp3sError of the pair."""
+        if len(mp3s_a) != len(mp3s_b):
+            raise ValueError("one file of b per file of a")
+        if len(mp3s_a) == 0:
+            return []
+        n, _keep_a, fa, la = _file_list(mp3s_a)
+        _, _keep_b, fb, lb = _file_list(mp3s_b)
+        out, status, owner = (PcmDistortion * n)(), (C.c_int32 * n)(), C.c_void_p()
+        check(lib().mp3s_pcm_distortion_files(self.handle, fa, la, fb, lb, n, 1 if profile else 0, C.byref(owner), out, status))
+        own = _Owner(owner)
+        return [Mp3sError(status[i], f"pair {i}") if status[i] else self._distortion(out[i], own) for i in range(n)]
+
+    def hide_distortions(self, mp3s, messages, profile=False):
+        """what hiding `messages` in `mp3s` changes in the audio: hide_messages without any message (the clear re-encode) and with the
+        messages, then pcm_distortions(clear, hidden) over the files both calls took.  Returns one entry per file: the dict of
+        pcm_distortions + "too_long" and "hide_offset" of the hide call, or the exception either call gave for the file."""
+        if len(mp3s) != len(messages):
+            raise ValueError("one message (or None) per file")
+        clear = self.hide_messages(mp3s, [None] * len(mp3s))
+        hidden = self.hide_messages(mp3s, messages)
+        took = [i for i, (c, h) in enumerate(zip(clear, hidden)) if not isinstance(c, Exception) and not isinstance(h, Exception)]
+        diff = self.pcm_distortions([clear[i]["data"] for i in took], [hidden[i]["data"] for i in took], profile)
+        out = [c if isinstance(c, Exception) else h for c, h in zip(clear, hidden)]
+        for i, d in zip(took, diff):
+            if not isinstance(d, Exception):
+                d = dict(d, too_long=hidden[i]["too_long"], hide_offset=hidden[i]["hide_offset"])
+            out[i] = d
+        return out
+
+    def pcm_diff_dev(self, pcm, pairs, nch):
+        """test aid: k_pcm_diff_frames + k_pcm_diff_pairs alone (mp3s_pcm_diff_dev) on the int16 buffer `pcm` ([frames][1152][nch]) and
+        the PCM_PAIR_DTYPE records `pairs` -> (PCM_FRAME_DIFF_DTYPE [frame records: max(out_first + n_frames)], PCM_PAIR_DIFF_DTYPE [len(pairs)]);
+        frame records no pair names come back as 0xFF bytes"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        pairs = np.ascontiguousarray(pairs, dtype=PCM_PAIR_DTYPE)
+        n_rec = int((pairs["out_first"].astype(np.int64) + pairs["n_frames"]).max()) if len(pairs) else 0
+        d_pcm = self.to_device(pcm if pcm.size else np.zeros(8, dtype=np.int16))
+        d_pairs = self.to_device(pairs)
+        d_frames, d_out = self.alloc(max(n_rec, 1) * 32), self.alloc(len(pairs) * 40)
+        try:
+            check(lib().mp3s_dev_memset(self.handle, d_frames, 0xFF, max(n_rec, 1) * 32))
+            check(lib().mp3s_pcm_diff_dev(self.handle, d_pcm, int(nch), d_pairs, pairs.ctypes.data, len(pairs), d_frames, d_out))
+            return self.download(d_frames, PCM_FRAME_DIFF_DTYPE, (n_rec,)), self.download(d_out, PCM_PAIR_DIFF_DTYPE, (len(pairs),))
+        finally:
+            for p in (d_pcm, d_pairs, d_frames, d_out):
+                self.free(p)
 
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
