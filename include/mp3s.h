@@ -972,6 +972,58 @@ typedef struct {
 int mp3s_pcm_distortion_files(mp3s_ctx *ctx, const uint8_t *const *a, const size_t *a_lens, const uint8_t *const *b, const size_t *b_lens,
                               int n_pairs, int want_profile, mp3s_buf **owner, mp3s_pcm_distortion *out, int32_t *status);
 
+/* ---------------------------------------------------------------- (vi-d) a cover file against its stego file: lag search, difference at the lag
+ * replaces: decoding both files (mp3s_decode_streams), pulling every PCM sample to the host and a numpy loop over the lags.
+ * A re-encode delays the audio, so a file and its re-encode (a cover file and its stego file, a 128 kbit/s re-encode and its 320 kbit/s
+ * source) are not sample-aligned and section (vi-c), which has no lag argument, cannot judge them.  The calls below find the delay by
+ * an exhaustive integer search on the device and compare at it.  PCM is int16, [row][nch] interleaved; a pair is a run A of rows_a
+ * rows and a run B of rows_b rows.  Lag L pairs row i + L of A with row i of B, d = a[i+L] - b[i] per channel: for A = stego and
+ * B = cover a positive lag means the stego audio comes later.
+ * Search, with M = max_lag (0 .. MP3S_PCM_MAX_LAG) and search_rows >= 1: W = min(rows_a, rows_b) - 2M; a pair with W < 1 is not
+ * searched.  Otherwise S = min(W, search_rows) and the window is B rows [s0, s0 + S), s0 = M + (W - S) / 2 -- the middle of the file:
+ * the start of an MP3 is often silence, where every lag ties.  For every L in [-M, +M]
+ *   score[L + M] = sum over rows i in [s0, s0 + S) and the channels of (a[i+L] - b[i])^2        (uint64, exact)
+ * -- every lag sees the same B samples and the same count of samples.  The found lag minimises the score; among equal scores the
+ * smaller |L| wins, between +k and -k the +k.  n_best = the lags that reach the minimum (> 1: the answer is ambiguous).
+ * Comparison at a lag L, found or given: the overlap is B rows [i0, i1), i0 = max(0, -L), i1 = min(rows_b, rows_a - L),
+ * n_rows = max(0, i1 - i0); over its interleaved samples the fields of mp3s_pcm_pair_diff as in (vi-c) (sig2 = sum a^2, first_diff
+ * from the first compared sample, -1 for none), and one mp3s_pcm_frame_diff per chunk of 1152 rows counted from i0, the last chunk
+ * possibly partial.  At L = 0 on runs of whole frames this is exactly what mp3s_pcm_diff_dev computes. */
+#define MP3S_PCM_MAX_LAG 4608
+typedef struct { uint32_t a_first, a_rows, b_first, b_rows, out_first, reserved; } mp3s_pcm_run_pair;   /* 24 bytes: ROWS of d_pcm; chunk records at d_frames[out_first ..] */
+typedef struct {
+    int32_t lag; uint32_t n_best;            /* n_best 0: not searched (the lag was given, or the pair is too short: lag 0) -- then the next four are 0 */
+    uint64_t err2_best, err2_at_0;           /* score[lag + M], score[M] */
+    uint32_t search_first, search_rows;      /* s0, S */
+    uint32_t n_rows, n_chunks;               /* the overlap at the lag, ceil(n_rows / 1152) */
+} mp3s_pcm_lag;                              /* 40 bytes */
+/* the three passes alone (k_pcmalign.hpp) and k_pcm_diff_pairs behind them, asynchronous on the context's stream.  d_pcm is 16-byte
+ * aligned (and readable up to the next multiple of 4 bytes behind its last row, as every device allocation is); the runs lie anywhere in it.
+ * h_lags == NULL: search.  d_scores[n_pairs][2 max_lag + 1] gets every searched pair's scores (the row of a pair that is not searched
+ * is left as it was), d_lags[n_pairs] the lag records.  A pair with W < 1 gets n_best = 0, lag 0 and its comparison at lag 0.
+ * h_lags != NULL: lag h_lags[p] (|lag| <= MP3S_PCM_MAX_LAG) is taken for pair p, nothing is searched, max_lag and search_rows are
+ * only checked and d_scores may be NULL.  Either way pair p's chunk records go to d_frames[out_first .. out_first + n_chunks); the
+ * range must hold ceil(min(a_rows, b_rows) / 1152) records, the bound for every lag, and the ranges of different pairs must not overlap;
+ * records of the range past n_chunks are left as they were.  d_out[n_pairs] gets the pair records.  h_runs is the same table on the
+ * host, read (as h_lags is) before the call returns: the launch geometry needs the row counts.  Null pointers, n_pairs <= 0, another
+ * nch, max_lag outside 0 .. MP3S_PCM_MAX_LAG, search_rows < 1, a given lag beyond +-MP3S_PCM_MAX_LAG or a misaligned d_pcm:
+ * MP3S_E_ARG (checked without a device). */
+int mp3s_pcm_align_dev(mp3s_ctx *ctx, const int16_t *d_pcm, int nch, const mp3s_pcm_run_pair *d_runs, const mp3s_pcm_run_pair *h_runs,
+                       int n_pairs, int max_lag, int search_rows, const int32_t *h_lags /* NULL = search */, uint64_t *d_scores,
+                       mp3s_pcm_lag *d_lags, mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out);
+typedef struct {
+    mp3s_pcm_distortion at_lag;   /* as (vi-c), over the overlap at the lag: n_frames = chunks of 1152 rows, n_samples = n_rows * channels; profile [n_frames] or NULL */
+    mp3s_pcm_lag lag;
+    const uint64_t *scores;       /* [2 max_lag + 1] with want_profile when the pair was searched, else NULL */
+} mp3s_pcm_alignment;             /* 96 + 40 + 8 = 144 bytes */
+/* File a[i] against file b[i] on the frame of mp3s_pcm_distortion_files -- the same front end, grouping by channel count, one decode
+ * batch per group and status rules --, the three passes behind the decode and ONE copy down: 80 bytes a pair, with want_profile also
+ * 32 a chunk and 8 a score.  lags == NULL: every pair is searched; a pair too short for max_lag (W < 1) gets MP3S_E_UNSUPPORTED with
+ * a text naming its rows and max_lag, the other pairs are unaffected.  lags != NULL: lags[i] is taken for pair i. */
+int mp3s_pcm_alignment_files(mp3s_ctx *ctx, const uint8_t *const *a, const size_t *a_lens, const uint8_t *const *b, const size_t *b_lens,
+                             int n_pairs, int max_lag, int search_rows, const int32_t *lags /* NULL = search */, int want_profile,
+                             mp3s_buf **owner, mp3s_pcm_alignment *out, int32_t *status);
+
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference
  *           steganography.py:133-182, whose two serial frame loops (decoder/MP3_Parser.py:68-80, encoder/MP3_Encoder.py:

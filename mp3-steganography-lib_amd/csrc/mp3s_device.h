@@ -143,6 +143,25 @@ bool pcm_diff_tiles(const mp3s_pcm_pair *pairs, int n_pairs, Tiles &tiles)
 int launch_pcm_diff(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_pair *d_pairs, int n_pairs, const PcmTile *d_tiles, int n_tiles,
                     mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out);
 
+// the lag that aligns pairs of row runs of one int16 PCM buffer [row][nch] and their exact difference at it (k_pcmalign.hpp): pass 1
+// (k_pcm_lag_scores, only without d_given: d_scores[n_pairs][2 max_lag + 1]), pass 2 (k_pcm_lag_pick: d_lags, and d_geo for what
+// follows), pass 3 (k_pcm_diff_lagged: a record per chunk of 1152 rows of the overlap) and k_pcm_diff_pairs over d_geo.  d_tiles is
+// pcm_diff_tiles of pcm_align_bound_pairs: pass 3's grid stands on the bound ceil(min(a_rows, b_rows) / 1152) chunks a pair, which
+// holds for every lag.  d_pcm must be 16-byte aligned.
+constexpr int kPcmMaxLag = MP3S_PCM_MAX_LAG;
+int launch_pcm_align(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_run_pair *d_runs, int n_pairs, int max_lag, int search_rows,
+                     const int32_t *d_given, const PcmTile *d_tiles, int n_tiles, uint64_t *d_scores, mp3s_pcm_lag *d_lags, mp3s_pcm_pair *d_geo,
+                     mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out);
+// appends per run pair the mp3s_pcm_pair whose n_frames is that bound (the other fields 0): what pcm_diff_tiles takes
+template <class Pairs>
+void pcm_align_bound_pairs(const mp3s_pcm_run_pair *runs, int n_pairs, Pairs &pairs)
+{
+    for (int p = 0; p < n_pairs; p++) {
+        const uint32_t rows = runs[p].a_rows < runs[p].b_rows ? runs[p].a_rows : runs[p].b_rows;
+        pairs.push_back(mp3s_pcm_pair{0, 0, (uint32_t)(((uint64_t)rows + 1151) / 1152), 0});
+    }
+}
+
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes

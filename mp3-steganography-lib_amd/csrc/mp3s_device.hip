@@ -25,6 +25,7 @@ __constant__ DevTables c_tab;
 #include "k_reveal.hpp"
 #include "k_capacity.hpp"
 #include "k_pcmdiff.hpp"
+#include "k_pcmalign.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
@@ -419,6 +420,33 @@ int launch_pcm_diff(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3
         if (const hipError_t e = hipGetLastError()) return (int)e;
     }
     hipLaunchKernelGGL(k_pcm_diff_pairs, dim3((unsigned)n_pairs), dim3(PCMDIFF_TILE), 0, stream, d_pairs, d_frames, nch, d_out);
+    return (int)hipGetLastError();
+}
+
+// k_pcm_lag_scores: one workgroup (a wave) per (pair, tile of PCMALIGN_LAGS lags); k_pcm_lag_pick: one workgroup per pair;
+// k_pcm_diff_lagged: one workgroup per tile of d_tiles (one wave per chunk); k_pcm_diff_pairs over the geometry pass 2 wrote
+int launch_pcm_align(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_run_pair *d_runs, int n_pairs, int max_lag, int search_rows,
+                     const int32_t *d_given, const PcmTile *d_tiles, int n_tiles, uint64_t *d_scores, mp3s_pcm_lag *d_lags, mp3s_pcm_pair *d_geo,
+                     mp3s_pcm_frame_diff *d_frames, mp3s_pcm_pair_diff *d_out)
+{
+    if (n_pairs <= 0) return 0;
+    if ((nch != 1 && nch != 2) || ((uintptr_t)d_pcm & 15) || max_lag < 0 || max_lag > kPcmMaxLag || search_rows < 1) return (int)hipErrorInvalidValue;
+    if (!d_given) {
+        const int tiles_per_pair = (2 * max_lag + 1 + PCMALIGN_LAGS - 1) / PCMALIGN_LAGS;
+        if ((uint64_t)n_pairs * (uint64_t)tiles_per_pair > 0x7fffffffu) return (int)hipErrorInvalidValue;
+        const dim3 grid((unsigned)n_pairs * (unsigned)tiles_per_pair);
+        if (nch == 2) hipLaunchKernelGGL(k_pcm_lag_scores<2>, grid, dim3(64), 0, stream, d_pcm, d_runs, max_lag, search_rows, tiles_per_pair, d_scores);
+        else hipLaunchKernelGGL(k_pcm_lag_scores<1>, grid, dim3(64), 0, stream, d_pcm, d_runs, max_lag, search_rows, tiles_per_pair, d_scores);
+        if (const hipError_t e = hipGetLastError()) return (int)e;
+    }
+    hipLaunchKernelGGL(k_pcm_lag_pick, dim3((unsigned)n_pairs), dim3(PCMALIGN_PICK), 0, stream, d_runs, d_scores, d_given, max_lag, search_rows, d_lags, d_geo);
+    if (const hipError_t e = hipGetLastError()) return (int)e;
+    if (n_tiles > 0) {
+        if (nch == 2) hipLaunchKernelGGL(k_pcm_diff_lagged<2>, dim3((unsigned)n_tiles), dim3(PCMDIFF_WAVES * 64), 0, stream, d_pcm, d_geo, d_lags, d_tiles, d_frames);
+        else hipLaunchKernelGGL(k_pcm_diff_lagged<1>, dim3((unsigned)n_tiles), dim3(PCMDIFF_WAVES * 64), 0, stream, d_pcm, d_geo, d_lags, d_tiles, d_frames);
+        if (const hipError_t e = hipGetLastError()) return (int)e;
+    }
+    hipLaunchKernelGGL(k_pcm_diff_pairs, dim3((unsigned)n_pairs), dim3(PCMDIFF_TILE), 0, stream, d_geo, d_frames, nch, d_out);
     return (int)hipGetLastError();
 }
 

@@ -89,6 +89,8 @@ struct mp3s_ctx {
     // use) is recorded behind its copy, the next call waits for it before it writes the table again
     std::vector<PcmTile> h_pcm_tiles;
     hipEvent_t ev_pcm_tiles = nullptr;
+    // ... and the block [workgroup table | given lags] of the last mp3s_pcm_align_dev, by the same rule and behind the same event
+    std::vector<uint8_t> h_pcm_align;
     int ensure_scratch(size_t bytes)
     {
         if (bytes <= scratch_bytes) return 0;
@@ -346,6 +348,20 @@ int decode_transform_chunk(mp3s_ctx *c, const int16_t *d_is, const mp3s_granule_
                            hipEvent_t done = nullptr /* recorded behind the chunk's transforms (launch_decode) */);
 // decode the streams `idx` of m (one channel count) as one batch; d_keep: int16 PCM stays on the device there
 int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, int out_format, void *d_keep = nullptr);
+
+// ---------------------------------------------------------------- pairs of MP3 files (mp3s_distortion_files.cpp, mp3s_alignment_files.cpp)
+// frames of a stream's PCM, the frame the decoder repeats after a bad header (D12) included: what mp3s_decoded.n_rows counts, / 1152
+inline int64_t pcm_frames(const ParsedStream &p) { return (int64_t)p.n_frames + (p.dup_last_frame ? 1 : 0); }
+// out = a pair's record and what the host knows of its two streams: the ONE place a mp3s_pcm_pair_diff becomes an mp3s_pcm_distortion
+void distortion_from_record(const mp3s_pcm_pair_diff &r, const ParsedStream &a, const ParsedStream &b, int64_t n_frames, int64_t n_samples,
+                            const mp3s_pcm_frame_diff *profile, mp3s_pcm_distortion *out);
+// the front of the pair-list calls: all 2 n files as one list (file i = a[i], file n + i = b[i]) into m, per pair its code in fs, or
+// empty(i) (a stream without a frame: nothing for a decode batch), or valid(i) (same channel count and sampling rate: to be grouped)
+void pcm_pairs_front_end(const uint8_t *const *a, const size_t *a_lens, const uint8_t *const *b, const size_t *b_lens, int n_pairs, mp3s_multi &m,
+                         FileStatus &fs, const std::function<void(int)> &empty, const std::function<void(int)> &valid);
+// after decode_group of the streams (A, B of pair idx[0], A, B of pair idx[1], ...): a host re-parse inside it must have left the frame
+// counts the batch's layout was built on: na[k] / nb[k] = the frames of pair idx[k]'s streams as the layout took them
+int pcm_pairs_same_frames(const mp3s_multi &m, int n_pairs, const std::vector<int> &idx, const std::vector<int64_t> &na, const std::vector<int64_t> &nb);
 
 // ---------------------------------------------------------------- encode pipeline (mp3s_encode_pipeline.cpp)
 constexpr int kLongMessageBits = 1024;    // above: the first pass does not guess cursors at all

@@ -177,6 +177,29 @@ PCM_PAIR_DIFF_DTYPE = np.dtype([("err2", "<u8"), ("sig2", "<u8"), ("n_diff", "<u
 NO_DIFF = 0xFFFFFFFF         # mp3s_pcm_frame_diff.first_diff of a frame without a differing sample
 
 
+class PcmRunPair(C.Structure):
+    """mp3s_pcm_run_pair: rows of the PCM buffer"""
+    _fields_ = [("a_first", C.c_uint32), ("a_rows", C.c_uint32), ("b_first", C.c_uint32), ("b_rows", C.c_uint32), ("out_first", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PcmLag(C.Structure):
+    """mp3s_pcm_lag: the lag record of a pair"""
+    _fields_ = [("lag", C.c_int32), ("n_best", C.c_uint32), ("err2_best", C.c_uint64), ("err2_at_0", C.c_uint64), ("search_first", C.c_uint32),
+                ("search_rows", C.c_uint32), ("n_rows", C.c_uint32), ("n_chunks", C.c_uint32)]
+
+
+class PcmAlignment(C.Structure):
+    """mp3s_pcm_alignment: what mp3s_pcm_alignment_files answers per pair"""
+    _fields_ = [("at_lag", PcmDistortion), ("lag", PcmLag), ("scores", C.c_void_p)]
+
+
+PCM_RUN_PAIR_DTYPE = np.dtype([("a_first", "<u4"), ("a_rows", "<u4"), ("b_first", "<u4"), ("b_rows", "<u4"), ("out_first", "<u4"), ("reserved", "<u4")])
+PCM_LAG_DTYPE = np.dtype([("lag", "<i4"), ("n_best", "<u4"), ("err2_best", "<u8"), ("err2_at_0", "<u8"), ("search_first", "<u4"), ("search_rows", "<u4"),
+                          ("n_rows", "<u4"), ("n_chunks", "<u4")])
+PCM_MAX_LAG = 4608           # MP3S_PCM_MAX_LAG
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_frames", C.c_int64), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
                 ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("reserved", C.c_int32)]
@@ -231,7 +254,7 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps",
            "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages",
            "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes",
-           "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files"]
+           "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files", "mp3s_pcm_align_dev", "mp3s_pcm_alignment_files"]
 
 REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
 RV_BAD_REF = 1
@@ -351,6 +374,8 @@ def lib():
         L.mp3s_capacity_text_bytes.restype = i64
         L.mp3s_pcm_diff_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp]
         L.mp3s_pcm_distortion_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, pvp, vp, vp]
+        L.mp3s_pcm_align_dev.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.mp3s_pcm_alignment_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, pvp, vp, vp]
         L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
@@ -1032,6 +1057,84 @@ class Context:
         finally:
             for p in (d_pcm, d_pairs, d_frames, d_out):
                 self.free(p)
+
+    def pcm_alignments(self, mp3s_a, mp3s_b, max_lag=2304, search_rows=4608, lags=None, profile=False):
+        """mp3s_a[i] against mp3s_b[i] across a re-encode's delay (mp3s_pcm_alignment_files): both lists are decoded on the device, the
+        lag L in [-max_lag, +max_lag] that minimises the squared error of a[i + L] - b[i] over a window of search_rows rows in the middle
+        of the pair is found there by exhaustive search (lags = a list: taken as given, nothing is searched), and the pair is compared
+        at that lag over its whole overlap.  For a = stego and b = cover a positive lag means the stego audio comes later.  Returns one
+        entry per pair: the dict of pcm_distortions at the lag (n_frames = chunks of 1152 rows of the overlap) + "lag", "n_best" (lags
+        that reach the minimum; 0: not searched), "err2_best", "err2_at_0", "search_first", "search_rows", "scores"; with profile, "profile" is
+        a PCM_FRAME_DIFF_DTYPE record per chunk and "scores" the uint64 [2 max_lag + 1] scores of a searched pair (both None without); or
+        the pair's Mp3sError."""
+        if len(mp3s_a) != len(mp3s_b) or (lags is not None and len(lags) != len(mp3s_a)):
+            raise ValueError("one file of b (and one lag, when given) per file of a")
+        if len(mp3s_a) == 0:
+            return []
+        n, _keep_a, fa, la = _file_list([f if f is not None else b"" for f in mp3s_a])
+        _, _keep_b, fb, lb = _file_list([f if f is not None else b"" for f in mp3s_b])
+        for files, ptrs in ((mp3s_a, fa), (mp3s_b, fb)):             # a file that is None: a null pointer, which the pair answers for
+            for i, f in enumerate(files):
+                if f is None:
+                    ptrs[i] = None
+        given = None if lags is None else (C.c_int32 * n)(*[int(x) for x in lags])
+        out, status, owner = (PcmAlignment * n)(), (C.c_int32 * n)(), C.c_void_p()
+        check(lib().mp3s_pcm_alignment_files(self.handle, fa, la, fb, lb, n, int(max_lag), int(search_rows), given, 1 if profile else 0,
+                                             C.byref(owner), out, status))
+        own = _Owner(owner)
+
+        def entry(x):
+            d = self._distortion(x.at_lag, own)
+            g = x.lag
+            d.update(lag=g.lag, n_best=g.n_best, err2_best=g.err2_best, err2_at_0=g.err2_at_0, search_first=g.search_first, search_rows=g.search_rows)
+            d["scores"] = _view_owned(x.scores, np.uint64, (2 * int(max_lag) + 1,), own) if x.scores else None
+            return d
+        return [Mp3sError(status[i], f"pair {i}") if status[i] else entry(out[i]) for i in range(n)]
+
+    def stego_distortions(self, mp3s, messages, max_lag=2304, search_rows=4608, profile=False):
+        """how far the file handed on is from the file one started with: hide_messages, then pcm_alignments(stego, cover) over the files
+        the hide call took.  Returns one entry per file: the dict of pcm_alignments + "too_long" and "hide_offset" of the hide call, or
+        the exception either call gave for the file."""
+        if len(mp3s) != len(messages):
+            raise ValueError("one message (or None) per file")
+        hidden = self.hide_messages(mp3s, messages)
+        took = [i for i, h in enumerate(hidden) if not isinstance(h, Exception)]
+        diff = self.pcm_alignments([hidden[i]["data"] for i in took], [mp3s[i] for i in took], max_lag, search_rows, None, profile)
+        out = list(hidden)
+        for i, d in zip(took, diff):
+            if not isinstance(d, Exception):
+                d = dict(d, too_long=hidden[i]["too_long"], hide_offset=hidden[i]["hide_offset"])
+            out[i] = d
+        return out
+
+    def pcm_align_dev(self, pcm, runs, nch, max_lag, search_rows, lags=None):
+        """test aid: the three passes of k_pcmalign.hpp + k_pcm_diff_pairs alone (mp3s_pcm_align_dev) on the int16 buffer `pcm`
+        ([rows][nch]) and the PCM_RUN_PAIR_DTYPE records `runs` -> (scores uint64 [len(runs)][2 max_lag + 1] or None with given lags,
+        PCM_LAG_DTYPE [len(runs)], PCM_FRAME_DIFF_DTYPE [chunk records: max(out_first + bound)], PCM_PAIR_DIFF_DTYPE [len(runs)]);
+        what no pass writes (scores of a pair that is not searched, chunk records past an overlap) comes back as 0xFF bytes"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+        runs = np.ascontiguousarray(runs, dtype=PCM_RUN_PAIR_DTYPE)
+        n, n_lags = len(runs), 2 * int(max_lag) + 1
+        bound = (np.minimum(runs["a_rows"], runs["b_rows"]).astype(np.int64) + 1151) // 1152
+        n_rec = int((runs["out_first"].astype(np.int64) + bound).max()) if n else 0
+        given = None if lags is None else np.ascontiguousarray(lags, dtype=np.int32)
+        padded = np.zeros((pcm.size + 15) // 8 * 8 + 8, dtype=np.int16)   # (a whole dword behind the last row)
+        padded[:pcm.size] = pcm
+        d_pcm, d_runs = self.to_device(padded), self.to_device(runs)
+        d_scores, d_lags = (self.alloc(n * n_lags * 8) if given is None else None), self.alloc(n * 40)
+        d_frames, d_out = self.alloc(max(n_rec, 1) * 32), self.alloc(n * 40)
+        try:
+            check(lib().mp3s_dev_memset(self.handle, d_frames, 0xFF, max(n_rec, 1) * 32))
+            if d_scores is not None:
+                check(lib().mp3s_dev_memset(self.handle, d_scores, 0xFF, n * n_lags * 8))
+            check(lib().mp3s_pcm_align_dev(self.handle, d_pcm, int(nch), d_runs, runs.ctypes.data, n, int(max_lag), int(search_rows),
+                                           None if given is None else given.ctypes.data, d_scores, d_lags, d_frames, d_out))
+            return (None if d_scores is None else self.download(d_scores, np.uint64, (n, n_lags)), self.download(d_lags, PCM_LAG_DTYPE, (n,)),
+                    self.download(d_frames, PCM_FRAME_DIFF_DTYPE, (n_rec,)), self.download(d_out, PCM_PAIR_DIFF_DTYPE, (n,)))
+        finally:
+            for p in (d_pcm, d_runs, d_scores, d_lags, d_frames, d_out):
+                if p is not None:
+                    self.free(p)
 
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
