@@ -24,6 +24,47 @@ void file_from_seg(const EncSeg &seg, const uint8_t *mp3_base, int kbps, int rat
     out->too_long = hide_offset < (int64_t)seg.n_hide - 1 ? 1 : 0;
 }
 
+std::vector<int32_t> mp3_list_front(mp3s_ctx *c, mp3s_multi &m, int n_files, const std::function<std::pair<const uint8_t *, size_t>(int)> &file_of)
+{
+    m.parsed.resize(n_files); m.scanned.resize(n_files); m.pcm.assign(n_files, nullptr); m.files.resize(n_files);
+    std::vector<int32_t> st((size_t)n_files, MP3S_OK);
+    size_t total = 0;
+    for (int i = 0; i < n_files; i++) {
+        const std::pair<const uint8_t *, size_t> f = file_of(i);
+        if (!f.first) { st[(size_t)i] = MP3S_E_ARG; continue; }
+        m.files[i] = f;
+        total += f.second;
+    }
+    if (n_files == 1) m.scanned[0] = std::move(c->spare_scan);   // its capacity: no fresh pages for the blob of a long file
+    parallel_files(file_workers(n_files, total, host_threads16()), n_files, [&](int, int i) { if (!st[(size_t)i]) st[(size_t)i] = front_end(m, i); });
+    return st;
+}
+
+void mp3_list_done(mp3s_ctx *c, mp3s_multi &m)
+{
+    if (m.files.size() == 1) c->spare_scan = std::move(m.scanned[0]);
+    m.files.clear();   // borrowed pointers
+}
+
+void reencode_list_front(mp3s_ctx *c, mp3s_multi &m, const uint8_t *const *mp3s, const size_t *lens, int n_files, const uint8_t *const *msgs,
+                         const size_t *msg_lens, FileStatus &fs, std::vector<std::vector<uint8_t>> &bits, FileGroups &groups, double *t_scanned)
+{
+    const std::vector<int32_t> front = mp3_list_front(c, m, n_files, [&](int i) {
+        const bool bad = !mp3s[i] || (msgs && msgs[i] == nullptr && msg_lens[i]);
+        return std::pair<const uint8_t *, size_t>(bad ? nullptr : mp3s[i], lens[i]);
+    });
+    if (t_scanned) *t_scanned = now_ms();
+    bits.resize((size_t)n_files);
+    for (int i = 0; i < n_files; i++) {
+        int kbps = 0;
+        if (front[(size_t)i]) { fs.set(i, front_end_failed(front[(size_t)i], i)); continue; }
+        fs.set(i, reencode_check(m.parsed[i], &kbps));
+        if (fs.st[(size_t)i]) continue;
+        if (msgs && msgs[i]) message_frame(msgs[i], msg_lens[i], bits[(size_t)i]);
+        groups.add(m.parsed[i].sampling_rate, kbps, i);
+    }
+}
+
 int front_end_failed(int code, int i)
 {
     return fail(code, code == MP3S_E_ARG ? "file %d: null pointer" : "file %d: malformed or unsupported MP3 stream", i);
@@ -37,4 +78,12 @@ int finish_files(const FileStatus &fs, int32_t *status)
         if (fs.st[i] && !first_bad) first_bad = fail(fs.st[i], "%s", fs.why[i].c_str());
     }
     return first_bad;
+}
+
+int finish_list(const FileStatus &fs, int32_t *status, std::unique_ptr<mp3s_buf> &top, mp3s_buf **owner)
+{
+    const int first_bad = finish_files(fs, status);
+    if (!status && first_bad) return first_bad;
+    *owner = top.release();
+    return MP3S_OK;
 }

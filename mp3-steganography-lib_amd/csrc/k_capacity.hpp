@@ -12,7 +12,7 @@
 //                    frame, which is what a staged, coalesced copy of the tile into LDS would read as well -- with 72 KB of LDS and a
 //                    barrier more.  (Wider loads have nothing to take here: the records' other fields are not wanted.)
 //                  * the frame's bits (0 .. 12) and its active units (0 .. 4) travel as one dword, bits | units << 16 (a tile's sums are
-//                    at most 3 072 and 1 024): ONE inclusive scan -- DPP row shifts and row broadcasts inside the wave, the wave totals
+//                    at most 3 072 and 1 024): ONE inclusive scan -- wave_scan_u32 (k_wave.hpp) inside the wave, the wave totals
 //                    through LDS (two buffers, taken in turn: one barrier a tile) -- gives the running sum of the profile and the tile's
 //                    totals; the totals in front of the tile are carried in registers and restart with the workgroup = at every stream.
 //                Every word written has one writer: ordinary vector stores, no atomics, no scratch.
@@ -21,16 +21,6 @@
 namespace mp3s {
 
 constexpr int CAP_TILE = 256;               // frames of a tile = threads of the workgroup
-
-// inclusive prefix sum over the 64 lanes of a wave (lanes without a source add the 0 the DPP move leaves them)
-__device__ __forceinline__ uint32_t cap_wave_scan(uint32_t v)
-{
-#define MP3S_DPP_ADD(ctrl, rm) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rm, 0xf, false)
-    MP3S_DPP_ADD(0x111, 0xf); MP3S_DPP_ADD(0x112, 0xf); MP3S_DPP_ADD(0x114, 0xf); MP3S_DPP_ADD(0x118, 0xf);   // row_shr:1, 2, 4, 8: inside the rows of 16
-    MP3S_DPP_ADD(0x142, 0xa); MP3S_DPP_ADD(0x143, 0xc);                                                       // row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3
-#undef MP3S_DPP_ADD
-    return v;
-}
 
 __global__ __launch_bounds__(CAP_TILE) void k_capacity(
     const mp3s_gr_out *__restrict__ gr, const mp3s_chain_seg *__restrict__ segs, mp3s_capacity_seg *__restrict__ out,
@@ -56,7 +46,7 @@ __global__ __launch_bounds__(CAP_TILE) void k_capacity(
             for (int k = 0; k < 4; k++)
                 if (flags[k] & MP3S_RF_ACTIVE) v += (uint32_t)tables[k] + 0x10000u;
         }
-        v = cap_wave_scan(v);
+        v = wave_scan_u32(v);
         if (lane == 63) w_sum[row][wave] = v;
         __syncthreads();
         uint32_t tile = 0;

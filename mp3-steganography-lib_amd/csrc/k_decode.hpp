@@ -43,12 +43,7 @@ __device__ __forceinline__ double dpp_f64(double v)
 // on the way back.  Only for scales of guards.
 __device__ __forceinline__ double wave_max_bound_f64(double a)
 {
-    uint32_t v = (uint32_t)__double2hiint(a);
-#define MP3S_DPP_MAX(ctrl, rm) v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rm, 0xf, false))
-    MP3S_DPP_MAX(0x111, 0xf); MP3S_DPP_MAX(0x112, 0xf); MP3S_DPP_MAX(0x114, 0xf); MP3S_DPP_MAX(0x118, 0xf);   // row_shr:1, 2, 4, 8
-    MP3S_DPP_MAX(0x142, 0xa); MP3S_DPP_MAX(0x143, 0xc);                                                       // row_bcast:15, 31
-#undef MP3S_DPP_MAX
-    return __hiloint2double(__builtin_amdgcn_readlane((int)v, 63) + 1, 0);
+    return __hiloint2double((int)wave_max_u32((uint32_t)__double2hiint(a)) + 1, 0);
 }
 
 __device__ __forceinline__ double shfl_xor_f64(double v, int mask)

@@ -1,5 +1,5 @@
 // A cover file against its stego file: the lag that aligns two int16 PCM runs, and their exact difference at that lag, on the device
-// (gfx950).  Included by mp3s_device.hip only, behind k_pcmdiff.hpp (whose wave reductions and whose pass 2 are used here).
+// (gfx950).  Included by mp3s_device.hip only, behind k_pcmdiff.hpp (whose PcmDiffAcc and whose pass 2 are used here).
 //
 // A re-encode delays the audio, so two files that hold "the same" audio are not sample-aligned.  A run pair is rows
 // [a_first, a_first + a_rows) against rows [b_first, b_first + b_rows) of one PCM buffer, [row][nch] int16 interleaved, the runs anywhere
@@ -30,7 +30,7 @@
 //                same host-made PcmTile table as k_pcm_diff_frames -- sized by the bound ceil(min(rows_a, rows_b) / 1152), which holds
 //                for every lag; waves past the pair's real chunk count leave.  A lane takes one row a step (a dword load of A and of B,
 //                18 steps a chunk); rows past the overlap's end are masked and contribute nothing, sig2 included (zeros against zeros).
-//                A lane sums at most 36 samples in 64 bits, < 36 * 2^32 < 2^38: the wave reductions of k_pcmdiff.hpp hold.
+//                A lane sums at most 36 samples in 64 bits, < 36 * 2^32 < 2^38: PcmDiffAcc (k_pcmdiff.hpp) holds.
 //                The per-pair reduction is k_pcm_diff_pairs, unchanged, over the geometry's chunk count.
 #pragma once
 
@@ -215,29 +215,14 @@ __global__ __launch_bounds__(PCMDIFF_WAVES * 64) void k_pcm_diff_lagged(
         a[s] = in ? pcmalign_row<NCH>(pcm32, a0 + (uint64_t)i) : 0u;
         b[s] = in ? pcmalign_row<NCH>(pcm32, b0 + (uint64_t)i) : 0u;   // (zeros against zeros: no difference, nothing to the sums)
     }
-    uint64_t err2 = 0, sig2 = 0;
-    uint32_t max_abs = 0, n_diff = 0, not_first = 0;      // not_first = ~(first differing index), 0: none
+    PcmDiffAcc acc;
 #pragma unroll
     for (int s = 0; s < STEPS; s++) {
 #pragma unroll
-        for (int k = 0; k < NCH; k++) {
-            const int32_t x = k ? pcmalign_hi(a[s]) : pcmalign_lo(a[s]), y = k ? pcmalign_hi(b[s]) : pcmalign_lo(b[s]);
-            const int32_t d = x - y;
-            const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
-            err2 += ad * ad;                              // unsigned: 65 535^2 < 2^32
-            sig2 += (uint32_t)(x * x);
-            max_abs = max(max_abs, ad);
-            n_diff += d != 0;
-            not_first = max(not_first, d != 0 ? ~(uint32_t)((s * 64 + lane) * NCH + k) : 0u);
-        }
+        for (int k = 0; k < NCH; k++)
+            PCMDIFF_ADD(acc, k ? pcmalign_hi(a[s]) : pcmalign_lo(a[s]), k ? pcmalign_hi(b[s]) : pcmalign_lo(b[s]), (s * 64 + lane) * NCH + k)
     }
-    const uint64_t w_err2 = pcmdiff_wave_add64(err2), w_sig2 = pcmdiff_wave_add64(sig2);
-    const uint32_t w_max = pcmdiff_wave_max(max_abs), w_n = pcmdiff_wave_add(n_diff), w_nf = pcmdiff_wave_max(not_first);
-    mp3s_pcm_frame_diff r;
-    r.err2 = (uint64_t)pcmdiff_lane63((uint32_t)w_err2) | (uint64_t)pcmdiff_lane63((uint32_t)(w_err2 >> 32)) << 32;
-    r.sig2 = (uint64_t)pcmdiff_lane63((uint32_t)w_sig2) | (uint64_t)pcmdiff_lane63((uint32_t)(w_sig2 >> 32)) << 32;
-    r.max_abs = pcmdiff_lane63(w_max); r.n_diff = pcmdiff_lane63(w_n); r.first_diff = ~pcmdiff_lane63(w_nf); r.reserved = 0;
-    if (lane == 0) frames[(size_t)g.out_first + f] = r;
+    acc.reduce_and_store(lane, &frames[(size_t)g.out_first + f]);
 }
 
 }  // namespace mp3s

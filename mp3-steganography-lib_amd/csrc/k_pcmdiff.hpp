@@ -18,12 +18,11 @@
 //                frame in 4.5 steps and a mono frame in 2.25, the last step masked.  All loads of a frame (5 + 5 or 3 + 3) are issued
 //                before the first use.  Traffic: a frame of A and of B is read once, 9 216 bytes (4 608 mono) in, 32 bytes out.
 //                Per sample d = a - b:  |d| <= 65 535, d*d <= 65 535^2 < 2^32 (as an UNSIGNED product; it does not fit in int32),
-//                a*a <= 2^30.  A lane sums its at most 40 samples (5 steps of 8) in 64 bits: < 40 * 2^32 < 2^38.  For the wave's sum
-//                the lane's value is split at bit 26: low parts < 2^26, 64 of them < 2^32; high parts < 2^12, 64 of them < 2^18 --
-//                two 32-bit sums that cannot wrap, put together as lo + (hi << 26) < 2^44.  max |d|, the count of d != 0 (<= 2 304)
-//                and the first differing index take 32 bits; the index travels as its complement under a MAXIMUM, so that "none"
-//                (0xFFFFFFFF) is the 0 a lane without a source contributes.  The reduction is DPP (row shifts, row broadcasts), no
-//                LDS; lane 63 holds the totals, they are read from there and lane 0 writes the one 32-byte record.
+//                a*a <= 2^30.  A lane sums its at most 40 samples (5 steps of 8) in 64 bits: < 40 * 2^32 < 2^38, which is what
+//                wave_add64 (k_wave.hpp) takes.  max |d|, the count of d != 0 (<= 2 304) and the first differing index take 32 bits; the
+//                index travels as its complement under a MAXIMUM, so that "none" (0xFFFFFFFF) is the 0 a lane without a source
+//                contributes.  The reduction is DPP, no LDS; lane 63 holds the totals, they are read from there and lane 0 writes the
+//                one 32-byte record (PcmDiffAcc: k_pcm_diff_lagged of k_pcmalign.hpp sums and writes its chunks with it too).
 //   k_pcm_diff_pairs  : pass 2, one workgroup per pair over the pair's frame records in tiles of PCMDIFF_TILE, one record (two
 //                16-byte loads, lanes 32 bytes apart: every line of the tile once) per thread; per-thread sums in 64 bits, ONE reduction at
 //                the end -- shuffles inside the wave, the four wave totals through LDS.  Thread 0 writes the pair's 40-byte record.
@@ -37,31 +36,36 @@ namespace mp3s {
 constexpr int PCMDIFF_WAVES = kPcmDiffWaves;   // frames of a workgroup of pass 1 = its waves
 constexpr int PCMDIFF_TILE = 256;              // frame records of a tile of pass 2 = threads of its workgroup
 
-// sum / maximum over the 64 lanes of a wave, valid in lane 63 (cap_wave_scan's steps; lanes without a source contribute the 0 the DPP
-// move leaves them, which is neutral for both)
-__device__ __forceinline__ uint32_t pcmdiff_wave_add(uint32_t v)
-{
-#define MP3S_DPP_ADD(ctrl, rm) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rm, 0xf, false)
-    MP3S_DPP_ADD(0x111, 0xf); MP3S_DPP_ADD(0x112, 0xf); MP3S_DPP_ADD(0x114, 0xf); MP3S_DPP_ADD(0x118, 0xf);   // row_shr:1, 2, 4, 8
-    MP3S_DPP_ADD(0x142, 0xa); MP3S_DPP_ADD(0x143, 0xc);                                                       // row_bcast:15, row_bcast:31
-#undef MP3S_DPP_ADD
-    return v;
-}
-__device__ __forceinline__ uint32_t pcmdiff_wave_max(uint32_t v)
-{
-#define MP3S_DPP_MAX(ctrl, rm) v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rm, 0xf, false))
-    MP3S_DPP_MAX(0x111, 0xf); MP3S_DPP_MAX(0x112, 0xf); MP3S_DPP_MAX(0x114, 0xf); MP3S_DPP_MAX(0x118, 0xf);
-    MP3S_DPP_MAX(0x142, 0xa); MP3S_DPP_MAX(0x143, 0xc);
-#undef MP3S_DPP_MAX
-    return v;
-}
-// a lane's 64-bit sum (< 2^38) -> the wave's (< 2^44), valid in lane 63: see the header comment for the split
-__device__ __forceinline__ uint64_t pcmdiff_wave_add64(uint64_t v)
-{
-    const uint32_t lo = pcmdiff_wave_add((uint32_t)v & 0x3ffffffu), hi = pcmdiff_wave_add((uint32_t)(v >> 26));
-    return (uint64_t)lo + ((uint64_t)hi << 26);
-}
-__device__ __forceinline__ uint32_t pcmdiff_lane63(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
+// What a lane has seen of its frame (chunk), and the wave's record of it.  A lane may add up to 40 samples (wave_add64's bound).
+// PCMDIFF_ADD(acc, x, y, index): sample x of A against sample y of B, `index` its place in the frame.  A macro, not a member: as an
+// inlined call the compiler folds the chain of not_first maxima from its other end and the two kernels' instructions change
+// (docs/LOG.md); written out in the kernel they are the ones measured.
+#define PCMDIFF_ADD(acc, x, y, index)                                                                                                  \
+    {                                                                                                                                  \
+        const int32_t x_ = (x), y_ = (y);                                                                                              \
+        const int32_t d_ = x_ - y_;                                                                                                    \
+        const uint32_t ad_ = (uint32_t)(d_ < 0 ? -d_ : d_);                                                                            \
+        (acc).err2 += ad_ * ad_;                          /* unsigned: 65 535^2 < 2^32 */                                              \
+        (acc).sig2 += (uint32_t)(x_ * x_);                                                                                             \
+        (acc).max_abs = max((acc).max_abs, ad_);                                                                                       \
+        (acc).n_diff += d_ != 0;                                                                                                       \
+        (acc).not_first = max((acc).not_first, d_ != 0 ? ~(uint32_t)(index) : 0u);   /* the smallest index has the largest complement */ \
+    }
+struct PcmDiffAcc {
+    uint64_t err2 = 0, sig2 = 0;
+    uint32_t max_abs = 0, n_diff = 0, not_first = 0;      // not_first = ~(first differing index), 0: none
+    // the whole wave: the lanes' values to lane 63, from there into one record, written by lane 0
+    __device__ __forceinline__ void reduce_and_store(int lane, mp3s_pcm_frame_diff *dst) const
+    {
+        const uint64_t w_err2 = wave_add64(err2), w_sig2 = wave_add64(sig2);
+        const uint32_t w_max = wave_scan_max_u32(max_abs), w_n = wave_scan_u32(n_diff), w_nf = wave_scan_max_u32(not_first);
+        mp3s_pcm_frame_diff r;
+        r.err2 = (uint64_t)lane63((uint32_t)w_err2) | (uint64_t)lane63((uint32_t)(w_err2 >> 32)) << 32;
+        r.sig2 = (uint64_t)lane63((uint32_t)w_sig2) | (uint64_t)lane63((uint32_t)(w_sig2 >> 32)) << 32;
+        r.max_abs = lane63(w_max); r.n_diff = lane63(w_n); r.first_diff = ~lane63(w_nf); r.reserved = 0;
+        if (lane == 0) *dst = r;
+    }
+};
 
 template <int NCH>
 __global__ __launch_bounds__(PCMDIFF_WAVES * 64) void k_pcm_diff_frames(
@@ -85,8 +89,7 @@ __global__ __launch_bounds__(PCMDIFF_WAVES * 64) void k_pcm_diff_frames(
         a[s] = in ? A[i] : make_uint4(0, 0, 0, 0);
         b[s] = in ? B[i] : make_uint4(0, 0, 0, 0);      // (zeros against zeros: no difference, nothing to the sums)
     }
-    uint64_t err2 = 0, sig2 = 0;
-    uint32_t max_abs = 0, n_diff = 0, not_first = 0;      // not_first = ~(first differing index), 0: none
+    PcmDiffAcc acc;
 #pragma unroll
     for (int s = 0; s < STEPS; s++) {                     // in the order of the loads: the first step's sums run under the later loads
         const uint32_t wa[4] = {a[s].x, a[s].y, a[s].z, a[s].w}, wb[4] = {b[s].x, b[s].y, b[s].z, b[s].w};
@@ -94,22 +97,10 @@ __global__ __launch_bounds__(PCMDIFF_WAVES * 64) void k_pcm_diff_frames(
         for (int k = 0; k < 8; k++) {
             const int32_t x = (k & 1) ? (int32_t)wa[k >> 1] >> 16 : (int32_t)(wa[k >> 1] << 16) >> 16;
             const int32_t y = (k & 1) ? (int32_t)wb[k >> 1] >> 16 : (int32_t)(wb[k >> 1] << 16) >> 16;
-            const int32_t d = x - y;
-            const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
-            err2 += ad * ad;                              // unsigned: 65 535^2 < 2^32
-            sig2 += (uint32_t)(x * x);
-            max_abs = max(max_abs, ad);
-            n_diff += d != 0;
-            not_first = max(not_first, d != 0 ? ~(uint32_t)((s * 64 + lane) * 8 + k) : 0u);   // the smallest index has the largest complement
+            PCMDIFF_ADD(acc, x, y, (s * 64 + lane) * 8 + k)
         }
     }
-    const uint64_t w_err2 = pcmdiff_wave_add64(err2), w_sig2 = pcmdiff_wave_add64(sig2);
-    const uint32_t w_max = pcmdiff_wave_max(max_abs), w_n = pcmdiff_wave_add(n_diff), w_nf = pcmdiff_wave_max(not_first);
-    mp3s_pcm_frame_diff r;
-    r.err2 = (uint64_t)pcmdiff_lane63((uint32_t)w_err2) | (uint64_t)pcmdiff_lane63((uint32_t)(w_err2 >> 32)) << 32;
-    r.sig2 = (uint64_t)pcmdiff_lane63((uint32_t)w_sig2) | (uint64_t)pcmdiff_lane63((uint32_t)(w_sig2 >> 32)) << 32;
-    r.max_abs = pcmdiff_lane63(w_max); r.n_diff = pcmdiff_lane63(w_n); r.first_diff = ~pcmdiff_lane63(w_nf); r.reserved = 0;
-    if (lane == 0) frames[(size_t)pr.out_first + f] = r;
+    acc.reduce_and_store(lane, &frames[(size_t)pr.out_first + f]);
 }
 
 __global__ __launch_bounds__(PCMDIFF_TILE) void k_pcm_diff_pairs(

@@ -2,7 +2,7 @@
 //
 // One wavefront per granule*channel ("unit").  The 288 value pairs of the granule are spread over the
 // lanes (lane l holds the consecutive pairs 5l .. 5l+4); every step of the reference's loop body is a
-// lane-parallel map plus DPP wave reductions (independent ones written side by side), and all control
+// lane-parallel map plus DPP wave reductions (k_wave.hpp; independent ones written side by side), and all control
 // flow (binary search, inner loop, region split, table choice, hide swap) is wave-uniform scalar code.
 //   reference encoder/MP3_Encoder.py: __iteration_loop :760-815, __calc_scfsi energies :835-859,
 //   __bin_search_step_size :958-996, __inner_loop :1064-1095, quantize :373-415, calc_run_len :266-291,
@@ -34,71 +34,6 @@ extern "C" __attribute__((visibility("default"))) int mp3s_debug_rl_stats(unsign
 #endif
 
 namespace mp3s {
-
-// one DPP step of a wave reduction: lanes without a source read 0 (ctrl and row mask must be literals)
-#define RL_DPP(v, ctrl, rm) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, rm, 0xf, false))
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-    v = max(v, RL_DPP(v, 0x111, 0xf));  // row_shr:1
-    v = max(v, RL_DPP(v, 0x112, 0xf));  // row_shr:2
-    v = max(v, RL_DPP(v, 0x114, 0xf));  // row_shr:4
-    v = max(v, RL_DPP(v, 0x118, 0xf));  // row_shr:8
-    v = max(v, RL_DPP(v, 0x142, 0xa));  // row_bcast:15
-    v = max(v, RL_DPP(v, 0x143, 0xc));  // row_bcast:31
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t wave_add_u32(uint32_t v)
-{
-    v += RL_DPP(v, 0x111, 0xf);
-    v += RL_DPP(v, 0x112, 0xf);
-    v += RL_DPP(v, 0x114, 0xf);
-    v += RL_DPP(v, 0x118, 0xf);
-    v += RL_DPP(v, 0x142, 0xa);
-    v += RL_DPP(v, 0x143, 0xc);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// inclusive prefix sums over the lanes, the same six DPP steps: within the rows of 16 by shifts of 1, 2, 4, 8, then the last lane of
-// rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3 (six additions; through __shfl_up a step was an LDS permute, a compare,
-// a select and an addition with the address arithmetic of the permute on top)
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v)
-{
-    v += RL_DPP(v, 0x111, 0xf);
-    v += RL_DPP(v, 0x112, 0xf);
-    v += RL_DPP(v, 0x114, 0xf);
-    v += RL_DPP(v, 0x118, 0xf);
-    v += RL_DPP(v, 0x142, 0xa);
-    v += RL_DPP(v, 0x143, 0xc);
-    return v;
-}
-// Several reductions at once: a DPP step has to wait two issue slots for the VALU write in front of it, so independent
-// chains are written step by step side by side -- the second and third fill the slots the first would idle in.
-__device__ __forceinline__ void wave_add2(uint32_t &a, uint32_t &b)
-{
-#define RL_STEP(ctrl, rm) { const uint32_t ta = RL_DPP(a, ctrl, rm), tb = RL_DPP(b, ctrl, rm); a += ta; b += tb; }
-    RL_STEP(0x111, 0xf) RL_STEP(0x112, 0xf) RL_STEP(0x114, 0xf) RL_STEP(0x118, 0xf) RL_STEP(0x142, 0xa) RL_STEP(0x143, 0xc)
-#undef RL_STEP
-    a = (uint32_t)__builtin_amdgcn_readlane((int)a, 63);
-    b = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
-}
-__device__ __forceinline__ void wave_add3(uint32_t &a, uint32_t &b, uint32_t &c)
-{
-#define RL_STEP(ctrl, rm) { const uint32_t ta = RL_DPP(a, ctrl, rm), tb = RL_DPP(b, ctrl, rm), tc = RL_DPP(c, ctrl, rm); a += ta; b += tb; c += tc; }
-    RL_STEP(0x111, 0xf) RL_STEP(0x112, 0xf) RL_STEP(0x114, 0xf) RL_STEP(0x118, 0xf) RL_STEP(0x142, 0xa) RL_STEP(0x143, 0xc)
-#undef RL_STEP
-    a = (uint32_t)__builtin_amdgcn_readlane((int)a, 63);
-    b = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
-    c = (uint32_t)__builtin_amdgcn_readlane((int)c, 63);
-}
-__device__ __forceinline__ void wave_max3(uint32_t &a, uint32_t &b, uint32_t &c)
-{
-#define RL_STEP(ctrl, rm) { const uint32_t ta = RL_DPP(a, ctrl, rm), tb = RL_DPP(b, ctrl, rm), tc = RL_DPP(c, ctrl, rm); a = max(a, ta); b = max(b, tb); c = max(c, tc); }
-    RL_STEP(0x111, 0xf) RL_STEP(0x112, 0xf) RL_STEP(0x114, 0xf) RL_STEP(0x118, 0xf) RL_STEP(0x142, 0xa) RL_STEP(0x143, 0xc)
-#undef RL_STEP
-    a = (uint32_t)__builtin_amdgcn_readlane((int)a, 63);
-    b = (uint32_t)__builtin_amdgcn_readlane((int)b, 63);
-    c = (uint32_t)__builtin_amdgcn_readlane((int)c, 63);
-}
 
 // encoder/util.py:130-133 mulr for non-negative a: (a*b + 2^31) >> 32
 __device__ __forceinline__ uint32_t mulr_u(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b + 0x80000000ull) >> 32); }   // one v_mad_u64_u32

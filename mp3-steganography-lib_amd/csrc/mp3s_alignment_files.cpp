@@ -1,6 +1,5 @@
 // C-ABI of the library (include/mp3s.h), part 3f: a cover file against its stego file -- the lag that aligns the PCM of two MP3 files
-// and their exact difference at it, on the frame of mp3s_pcm_distortion_files (mp3s_distortion_files.cpp: the same front end, groups
-// and decode batch).  With the int16 PCM of a group's A and B streams in HBM, k_pcm_lag_scores, k_pcm_lag_pick and k_pcm_diff_lagged
+// and their exact difference at it, on the frame of the pair-list calls (pcm_pairs.cpp).  With the int16 PCM of a group's A and B streams in HBM, k_pcm_lag_scores, k_pcm_lag_pick and k_pcm_diff_lagged
 // (k_pcmalign.hpp) and k_pcm_diff_pairs run behind the decode; 80 bytes per pair come down, and with the profile 32 per chunk of 1152
 // rows and 8 per score; no PCM does.
 #include "mp3s_internal.h"
@@ -40,28 +39,22 @@ int align_inputs(const mp3s_pcm_run_pair *runs, int n_pairs, bool with_runs, con
     return MP3S_OK;
 }
 
-// The pairs `idx` (file idx[k] against file n_pairs + idx[k] of m, all of `nch` channels, every stream with a frame) as one batch: one
-// decode of all their streams into pool slot 7, the passes behind it, one copy down.  What the results point into (profile, scores) is
-// kept in a new part of `top`.
+// The pairs `idx` as one batch (PcmPairBatch): the passes behind the decode, the pair and lag records down and with the profile the
+// chunk records and the scores, which the results then point into.
 int align_group(mp3s_ctx *c, mp3s_multi &m, int n_pairs, const std::vector<int> &idx, int nch, int max_lag, int search_rows, const int32_t *lags,
                 bool want_profile, mp3s_buf *top, mp3s_pcm_alignment *out)
 {
     const size_t n = idx.size(), n_lags = (size_t)2 * (size_t)max_lag + 1;
-    std::vector<int> streams;
+    PcmPairBatch b;
+    if (const int rc = b.lay(m, n_pairs, idx, 0x7fffffff / 1152 / 8)) return rc;
     std::vector<mp3s_pcm_run_pair> runs(n);
     std::vector<int32_t> given(lags ? n : 0);
-    std::vector<int64_t> frames_a(n), frames_b(n);
-    int64_t rows_frames = 0, chunks = 0;
     for (size_t k = 0; k < n; k++) {
-        const int fa = idx[k], fb = n_pairs + idx[k];
-        const int64_t na = pcm_frames(m.parsed[fa]), nb = pcm_frames(m.parsed[fb]);
-        if (rows_frames + na + nb > 0x7fffffff / 1152 / 8) return fail(MP3S_E_ARG, "batch of more than %d frames is too large", 0x7fffffff / 1152 / 8);
-        runs[k] = {(uint32_t)(rows_frames * 1152), (uint32_t)(na * 1152), (uint32_t)((rows_frames + na) * 1152), (uint32_t)(nb * 1152), (uint32_t)chunks, 0};
+        runs[k] = {(uint32_t)(b.first[k] * 1152), (uint32_t)(b.frames_a[k] * 1152), (uint32_t)((b.first[k] + b.frames_a[k]) * 1152), (uint32_t)(b.frames_b[k] * 1152),
+                   (uint32_t)b.out_first[k], 0};   // (chunk records in whole frames: the bound of a pair is its smaller frame count)
         if (lags) given[k] = lags[idx[k]];
-        streams.push_back(fa); streams.push_back(fb);
-        frames_a[k] = na; frames_b[k] = nb;
-        rows_frames += na + nb; chunks += std::min(na, nb);   // (whole frames: the bound of a pair is its smaller frame count)
     }
+    const int64_t chunks = b.cmp_frames;
     AlignIn L;
     std::vector<uint8_t> &in = c->h_in;
     if (const int rc = align_inputs(runs.data(), (int)n, true, lags ? given.data() : nullptr, in, &L)) return rc;
@@ -69,29 +62,18 @@ int align_group(mp3s_ctx *c, mp3s_multi &m, int n_pairs, const std::vector<int> 
     const size_t o_lag = up16(n * sizeof(mp3s_pcm_pair_diff)), o_frames = o_lag + up16(n * sizeof(mp3s_pcm_lag)),
                  o_scores = o_frames + up16((size_t)chunks * sizeof(mp3s_pcm_frame_diff)), o_geo = o_scores + (lags ? 0 : up16(n * n_lags * sizeof(uint64_t))),
                  res_bytes = o_geo + n * sizeof(mp3s_pcm_pair), down_bytes = want_profile ? o_geo : o_frames;
-    if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
-    void *d_keep = c->grab(7, (size_t)rows_frames * 1152 * nch * 2);
-    uint8_t *d_in = (uint8_t *)c->grab(9, L.bytes), *d_res = (uint8_t *)c->grab(18, res_bytes);
-    if (!d_keep || !d_in || !d_res) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
-    std::unique_ptr<mp3s_buf> part(new mp3s_buf());
-    if (!part->big[2].reserve(down_bytes)) return fail(MP3S_E_NOMEM, "host memory for %zu bytes of records", down_bytes);
-    uint8_t *const res = part->big[2].data();
-    int rc = decode_group(c, m, streams, nch, MP3S_PCM_I16, d_keep);
-    if (!rc) rc = pcm_pairs_same_frames(m, n_pairs, idx, frames_a, frames_b);
-    if (!rc && hipMemcpyAsync(d_in, in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
-    if (!rc) {
-        const int e = launch_pcm_align(c->stream, (const int16_t *)d_keep, nch, (const mp3s_pcm_run_pair *)d_in, (int)n, max_lag, search_rows,
+    const int rc = b.run(c, m, nch, in.data(), L.bytes, res_bytes, down_bytes, [&](const int16_t *d_pcm, const uint8_t *d_in, uint8_t *d_res) {
+        const int e = launch_pcm_align(c->stream, d_pcm, nch, (const mp3s_pcm_run_pair *)d_in, (int)n, max_lag, search_rows,
                                        lags ? (const int32_t *)(d_in + L.o_lags) : nullptr, (const PcmTile *)(d_in + L.o_tiles), L.n_tiles,
                                        lags ? nullptr : (uint64_t *)(d_res + o_scores), (mp3s_pcm_lag *)(d_res + o_lag), (mp3s_pcm_pair *)(d_res + o_geo),
                                        (mp3s_pcm_frame_diff *)(d_res + o_frames), (mp3s_pcm_pair_diff *)d_res);
-        if (e) rc = fail(MP3S_E_HIP, "pcm align launch: %s", hipGetErrorString((hipError_t)e));
-    }
-    if (!rc && hipMemcpyAsync(res, d_res, down_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail(MP3S_E_HIP, "sync failed");   // (also on failure: `in` is the source of a copy)
+        return e ? fail(MP3S_E_HIP, "pcm align launch: %s", hipGetErrorString((hipError_t)e)) : MP3S_OK;
+    });
     if (rc) return rc;
     if (trace_on())
         fprintf(stderr, "mp3s:   pcm alignment: %zu pair(s) of %d channel(s), %lld frames decoded, %zu lag(s) %s, %lld chunk record(s), %zu bytes down\n", n, nch,
-                (long long)rows_frames, n_lags, lags ? "given" : "searched", (long long)chunks, down_bytes);
+                (long long)b.rows_frames, n_lags, lags ? "given" : "searched", (long long)chunks, down_bytes);
+    const uint8_t *const res = b.res;
     const mp3s_pcm_pair_diff *rec = (const mp3s_pcm_pair_diff *)res;
     const mp3s_pcm_lag *lag = (const mp3s_pcm_lag *)(res + o_lag);
     for (size_t k = 0; k < n; k++) {
@@ -101,7 +83,7 @@ int align_group(mp3s_ctx *c, mp3s_multi &m, int n_pairs, const std::vector<int> 
         o.lag = lag[k];
         o.scores = want_profile && !lags && lag[k].n_best ? (const uint64_t *)(res + o_scores) + k * n_lags : nullptr;
     }
-    top->parts.push_back(std::move(part));
+    top->parts.push_back(std::move(b.part));
     return MP3S_OK;
 }
 
@@ -117,16 +99,18 @@ int mp3s_pcm_align_dev(mp3s_ctx *c, const int16_t *d_pcm, int nch, const mp3s_pc
     if (const int rc = check_search(n_pairs, nch, max_lag, search_rows, h_lags)) return rc;
     if ((uintptr_t)d_pcm & 15) return fail(MP3S_E_ARG, "d_pcm is not 16-byte aligned");
     HIPCHK(hipSetDevice(c->device));
-    // the block of the call before may still be on its way: its copy reads the vector that is written next
-    if (c->ev_pcm_tiles) HIPCHK(hipEventSynchronize(c->ev_pcm_tiles));
-    else HIPCHK(hipEventCreateWithFlags(&c->ev_pcm_tiles, hipEventDisableTiming));
     AlignIn L;
-    if (const int rc = align_inputs(h_runs, n_pairs, false, h_lags, c->h_pcm_align, &L)) return rc;
-    const size_t o_geo = up16(L.bytes);
-    uint8_t *d_in = (uint8_t *)c->grab(9, o_geo + (size_t)n_pairs * sizeof(mp3s_pcm_pair));   // [tiles | given lags | geometry]
-    if (!d_in) return fail(MP3S_E_NOMEM, "hipMalloc failed for %d workgroup entries", L.n_tiles);
-    if (L.bytes) HIPCHK(hipMemcpyAsync(d_in, c->h_pcm_align.data(), L.bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_pcm_tiles, c->stream));
+    size_t o_geo = 0;
+    uint8_t *d_in = nullptr;
+    const int rc = pcm_dev_host_block(c, [&]() {
+        if (const int rc = align_inputs(h_runs, n_pairs, false, h_lags, c->h_pcm_align, &L)) return rc;
+        o_geo = up16(L.bytes);
+        d_in = (uint8_t *)c->grab(9, o_geo + (size_t)n_pairs * sizeof(mp3s_pcm_pair));   // [tiles | given lags | geometry]
+        if (!d_in) return fail(MP3S_E_NOMEM, "hipMalloc failed for %d workgroup entries", L.n_tiles);
+        if (L.bytes) HIPCHK(hipMemcpyAsync(d_in, c->h_pcm_align.data(), L.bytes, hipMemcpyHostToDevice, c->stream));
+        return (int)MP3S_OK;
+    });
+    if (rc) return rc;
     const int e = launch_pcm_align(c->stream, d_pcm, nch, d_runs, n_pairs, max_lag, search_rows, h_lags ? (const int32_t *)(d_in + L.o_lags) : nullptr,
                                    (const PcmTile *)(d_in + L.o_tiles), L.n_tiles, d_scores, d_lags, (mp3s_pcm_pair *)(d_in + o_geo), d_frames, d_out);
     if (e) return fail(MP3S_E_HIP, "pcm align launch: %s", hipGetErrorString((hipError_t)e));
@@ -139,41 +123,24 @@ int mp3s_pcm_alignment_files(mp3s_ctx *c, const uint8_t *const *a, const size_t 
     if (!c || !a || !a_lens || !b || !b_lens || !owner || !out || n_pairs <= 0) return fail(MP3S_E_ARG, "bad argument");
     if (n_pairs > 0x3fffffff) return fail(MP3S_E_ARG, "n_pairs=%d", n_pairs);
     if (const int rc = check_search(n_pairs, 2, max_lag, search_rows, lags)) return rc;
-    std::unique_ptr<mp3s_buf> top(new mp3s_buf());
-    top->multi.reset(new mp3s_multi());
-    mp3s_multi &m = *top->multi;
-    FileStatus fs(n_pairs);                               // per pair
-    FileGroups groups;                                    // by channel count
-    for (int i = 0; i < n_pairs; i++) std::memset(&out[i], 0, sizeof out[i]);
     const mp3s_pcm_pair_diff nothing = {0, 0, 0, -1, 0, 0};
-    // a pair too short for the search is refused; the others are unaffected
-    auto too_short = [&](int i) {
-        const int64_t ra = 1152 * pcm_frames(m.parsed[i]), rb = 1152 * pcm_frames(m.parsed[n_pairs + i]);
-        if (lags || search_room(ra, rb, max_lag) >= 1) return false;
-        fs.set(i, fail(MP3S_E_UNSUPPORTED, "pair %d: %lld rows against %lld are too few to search lags up to max_lag = %d (more than %d rows are needed)", i,
-                       (long long)ra, (long long)rb, max_lag, 2 * max_lag));
-        return true;
-    };
-    pcm_pairs_front_end(a, a_lens, b, b_lens, n_pairs, m, fs,
-                        // a stream without a frame: nothing to search; with a given lag the record of an empty overlap
-                        [&](int i) {
-                            if (too_short(i)) return;
-                            distortion_from_record(nothing, m.parsed[i], m.parsed[n_pairs + i], 0, 0, nullptr, &out[i].at_lag);
-                            out[i].lag.lag = lags[i];
-                        },
-                        [&](int i) { if (!too_short(i)) groups.add(m.parsed[i].nch, 0, i); });
-    // ---- per channel count: decode into HBM, search and compare there
-    run_groups(groups, [&](int nch, int, const std::vector<int> &idx) {
-        const int rc = align_group(c, m, n_pairs, idx, nch, max_lag, search_rows, lags, want_profile != 0, top.get(), out);
-        if (rc) for (int i : idx) std::memset(&out[i], 0, sizeof out[i]);
-        return rc;
-    }, fs, [] {});
-    m.files.clear();   // borrowed pointers
-    m.parsed.clear(); m.scanned.clear();   // (the results point into the parts only)
-    const int first_bad = finish_files(fs, status);
-    if (!status && first_bad) return first_bad;
-    *owner = top.release();
-    return MP3S_OK;
+    return pcm_pairs_call(c, a, a_lens, b, b_lens, n_pairs, out, sizeof *out, owner, status,
+                          // a stream without a frame: nothing to search; with a given lag the record of an empty overlap
+                          [&](const mp3s_multi &m, int i) {
+                              distortion_from_record(nothing, m.parsed[i], m.parsed[n_pairs + i], 0, 0, nullptr, &out[i].at_lag);
+                              out[i].lag.lag = lags[i];
+                          },
+                          // a pair too short for the search is refused; the others are unaffected
+                          [&](const mp3s_multi &m, FileStatus &fs, int i) {
+                              const int64_t ra = 1152 * pcm_frames(m.parsed[i]), rb = 1152 * pcm_frames(m.parsed[n_pairs + i]);
+                              if (lags || search_room(ra, rb, max_lag) >= 1) return false;
+                              fs.set(i, fail(MP3S_E_UNSUPPORTED, "pair %d: %lld rows against %lld are too few to search lags up to max_lag = %d (more than %d rows are needed)", i,
+                                             (long long)ra, (long long)rb, max_lag, 2 * max_lag));
+                              return true;
+                          },
+                          [&](mp3s_multi &m, const std::vector<int> &idx, int nch, mp3s_buf *top) {
+                              return align_group(c, m, n_pairs, idx, nch, max_lag, search_rows, lags, want_profile != 0, top, out);
+                          });
 }
 
 }  // extern "C"

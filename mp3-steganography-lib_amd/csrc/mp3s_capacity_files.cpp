@@ -87,32 +87,15 @@ int mp3s_capacity_files(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *l
                         const size_t *msg_lens, int want_profile, mp3s_buf **owner, mp3s_capacity *out, int32_t *status)
 {
     if (!c || !mp3s || !lens || !owner || !out || n_files <= 0 || (msgs && !msg_lens)) return fail(MP3S_E_ARG, "bad argument");
-    // ---- the front of mp3s_hide_messages: scan, the reference's checks, messages, groups
+    // ---- the front of the re-encoding calls (file_lists.cpp): scan, the reference's checks, messages, groups
     std::unique_ptr<mp3s_buf> top(new mp3s_buf());
     top->multi.reset(new mp3s_multi());
     mp3s_multi &m = *top->multi;
-    m.parsed.resize(n_files); m.scanned.resize(n_files); m.pcm.assign(n_files, nullptr); m.files.resize(n_files);
-    std::vector<std::vector<uint8_t>> bits(n_files);
+    std::vector<std::vector<uint8_t>> bits;
     FileStatus fs(n_files);
-    std::vector<int32_t> &st = fs.st;
     FileGroups groups;                       // by (sampling rate, kbps)
-    size_t total = 0;
-    for (int i = 0; i < n_files; i++) {
-        std::memset(&out[i], 0, sizeof out[i]);
-        if (!mp3s[i] || (msgs && msgs[i] == nullptr && msg_lens[i])) { st[i] = MP3S_E_ARG; continue; }
-        m.files[i] = {mp3s[i], lens[i]};
-        total += lens[i];
-    }
-    if (n_files == 1) m.scanned[0] = std::move(c->spare_scan);
-    parallel_files(file_workers(n_files, total, host_threads16()), n_files, [&](int, int i) { if (!st[i]) st[i] = front_end(m, i); });
-    for (int i = 0; i < n_files; i++) {
-        int kbps = 0;
-        if (st[i]) { fs.set(i, front_end_failed(st[i], i)); continue; }
-        fs.set(i, reencode_check(m.parsed[i], &kbps));
-        if (st[i]) continue;
-        if (msgs && msgs[i]) message_frame(msgs[i], msg_lens[i], bits[i]);
-        groups.add(m.parsed[i].sampling_rate, kbps, i);
-    }
+    for (int i = 0; i < n_files; i++) std::memset(&out[i], 0, sizeof out[i]);
+    reencode_list_front(c, m, mp3s, lens, n_files, msgs, msg_lens, fs, bits, groups);
     // ---- per group: decode into HBM as reencode_group does, then the encode without its tail
     run_groups(groups, [&](int rate, int kbps, const std::vector<int> &idx) {
         std::vector<EncSeg> segs;
@@ -124,12 +107,8 @@ int mp3s_capacity_files(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *l
         if (rc) for (int i : idx) std::memset(&out[i], 0, sizeof out[i]);
         return rc;
     }, fs, [] {});
-    m.files.clear();   // borrowed pointers
-    if (n_files == 1) c->spare_scan = std::move(m.scanned[0]);
-    const int first_bad = finish_files(fs, status);
-    if (!status && first_bad) return first_bad;
-    *owner = top.release();
-    return MP3S_OK;
+    mp3_list_done(c, m);
+    return finish_list(fs, status, top, owner);
 }
 
 int mp3s_capacity_wavs(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
@@ -162,10 +141,7 @@ int mp3s_capacity_wavs(mp3s_ctx *c, const uint8_t *const *wavs, const size_t *le
         }
         return rc;
     }, fs, [&] { (void)hipStreamSynchronize(c->stream); });
-    const int first_bad = finish_files(fs, status);
-    if (!status && first_bad) return first_bad;
-    *owner = top.release();
-    return MP3S_OK;
+    return finish_list(fs, status, top, owner);
 }
 
 }  // extern "C"

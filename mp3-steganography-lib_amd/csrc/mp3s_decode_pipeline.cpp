@@ -267,26 +267,16 @@ static int decode_streams_impl(mp3s_ctx *c, const uint8_t *const *files, const s
     b->multi.reset(new mp3s_multi());
     mp3s_multi &m = *b->multi;
     m.head_room = head_room;
-    m.parsed.resize(n_files); m.scanned.resize(n_files); m.pcm.assign(n_files, nullptr); m.files.resize(n_files);
     std::vector<int> group[3];
-    size_t total = 0;
     FileStatus fs(n_files);
     std::vector<int32_t> &frc = fs.st;
-    // (with status == NULL a file the front end refuses fails the call here, before any device work)
-    for (int i = 0; i < n_files; i++) {
-        if (!files[i]) {
-            fs.set(i, fail(MP3S_E_ARG, "file %d is null", i));
-            if (!status) { delete b; return frc[i]; }
-            continue;
-        }
-        m.files[i] = {files[i], lens[i]};
-        total += lens[i];
-    }
-    if (n_files == 1) m.scanned[0] = std::move(c->spare_scan);   // its capacity: no fresh pages for the blob of a long file
-    parallel_files(file_workers(n_files, total, host_threads16()), n_files, [&](int, int i) { if (!frc[i]) frc[i] = front_end(m, i); });
+    // (with status == NULL a file the front end refuses fails the call here, before any device work -- a null file before any work at all)
+    for (int i = 0; i < n_files && !status; i++)
+        if (!files[i]) { delete b; return fail(MP3S_E_ARG, "file %d is null", i); }
+    frc = mp3_list_front(c, m, n_files, [&](int i) { return std::pair<const uint8_t *, size_t>(files[i], lens[i]); });
     for (int i = 0; i < n_files; i++) {
         if (frc[i]) {
-            if (files[i]) fs.set(i, fail(frc[i], "file %d: malformed or unsupported MP3 stream", i));   // (a null file has its text)
+            fs.set(i, files[i] ? fail(frc[i], "file %d: malformed or unsupported MP3 stream", i) : fail(MP3S_E_ARG, "file %d is null", i));
             if (!status) { delete b; return frc[i]; }
             m.parsed[i] = ParsedStream();        // nothing of it goes into a batch
             continue;
@@ -321,8 +311,7 @@ static int decode_streams_impl(mp3s_ctx *c, const uint8_t *const *files, const s
         out[i].n_bits = (int32_t)p.bits.size(); out[i].n_rows = (int64_t)1152 * (p.n_frames + p.dup_last_frame);
         out[i].pcm = m.pcm[i]; out[i].bits = p.bits.data();
     }
-    if (n_files == 1) c->spare_scan = std::move(m.scanned[0]);   // (the result refers to the parse and the PCM only)
-    m.files.clear();   // borrowed
+    mp3_list_done(c, m);   // (the result refers to the parse and the PCM only)
     finish_files(fs, status);   // (with status == NULL every failure has failed the call above)
     *owner = b;
     return MP3S_OK;

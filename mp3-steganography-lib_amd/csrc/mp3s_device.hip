@@ -15,6 +15,7 @@ namespace mp3s {
 __constant__ DevTables c_tab;
 }
 
+#include "k_wave.hpp"
 #include "k_sync.hpp"
 #include "k_decode.hpp"
 #include "k_decode_stream.hpp"

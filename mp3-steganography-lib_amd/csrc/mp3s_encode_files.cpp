@@ -164,10 +164,7 @@ int encode_files_as(mp3s_ctx *c, WavRead how, const uint8_t *const *wavs, const 
         if (rc) for (int i : idx) std::memset(&out[i], 0, sizeof out[i]);
         return rc;
     }, fs, [&] { (void)hipStreamSynchronize(c->stream); });   // (copies of the failed batch may still read the callers' bytes and the staging)
-    const int first_bad = finish_files(fs, status);
-    if (!status && first_bad) return first_bad;
-    *owner = top.release();
-    return MP3S_OK;
+    return finish_list(fs, status, top, owner);
 }
 
 extern "C" {

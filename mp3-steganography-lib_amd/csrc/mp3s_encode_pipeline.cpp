@@ -809,42 +809,21 @@ int mp3s_hide_messages(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *le
     std::unique_ptr<mp3s_buf> top(new mp3s_buf());
     top->multi.reset(new mp3s_multi());
     mp3s_multi &m = *top->multi;
-    m.parsed.resize(n_files); m.scanned.resize(n_files); m.pcm.assign(n_files, nullptr); m.files.resize(n_files);
-    std::vector<std::vector<uint8_t>> bits(n_files);
+    std::vector<std::vector<uint8_t>> bits;
     FileStatus fs(n_files);
-    std::vector<int32_t> &st = fs.st;
     FileGroups groups;                       // by (sampling rate, kbps)
-    size_t total = 0;
+    double t1 = 0;
     const double t0 = trace_on() ? now_ms() : 0;
-    for (int i = 0; i < n_files; i++) {
-        std::memset(&out[i], 0, sizeof out[i]);
-        if (!mp3s[i] || (msgs && msgs[i] == nullptr && msg_lens[i])) { st[i] = MP3S_E_ARG; continue; }
-        m.files[i] = {mp3s[i], lens[i]};
-        total += lens[i];
-    }
-    if (n_files == 1) m.scanned[0] = std::move(c->spare_scan);   // its capacity: no fresh pages for the blob of a long file
-    parallel_files(file_workers(n_files, total, host_threads16()), n_files, [&](int, int i) { if (!st[i]) st[i] = front_end(m, i); });
-    const double t1 = trace_on() ? now_ms() : 0;
-    for (int i = 0; i < n_files; i++) {
-        int kbps = 0;
-        if (st[i]) { fs.set(i, front_end_failed(st[i], i)); continue; }
-        fs.set(i, reencode_check(m.parsed[i], &kbps));
-        if (st[i]) continue;
-        if (msgs && msgs[i]) message_frame(msgs[i], msg_lens[i], bits[i]);
-        groups.add(m.parsed[i].sampling_rate, kbps, i);
-    }
+    for (int i = 0; i < n_files; i++) std::memset(&out[i], 0, sizeof out[i]);
+    reencode_list_front(c, m, mp3s, lens, n_files, msgs, msg_lens, fs, bits, groups, trace_on() ? &t1 : nullptr);
     const double t2 = trace_on() ? now_ms() : 0;
     run_groups(groups, [&](int rate, int kbps, const std::vector<int> &idx) { return reencode_group(c, m, idx, bits, rate, kbps, top.get(), out); },
                fs, [] {});
     if (trace_on())
         fprintf(stderr, "mp3s: hide_messages, %d file(s): scan %.3f ms, messages + grouping %.3f ms, device batches %.3f ms\n", n_files,
                 t1 - t0, t2 - t1, now_ms() - t2);
-    m.files.clear();   // borrowed pointers
-    if (n_files == 1) c->spare_scan = std::move(m.scanned[0]);
-    const int first_bad = finish_files(fs, status);
-    if (!status && first_bad) return first_bad;
-    *owner = top.release();
-    return MP3S_OK;
+    mp3_list_done(c, m);
+    return finish_list(fs, status, top, owner);
 }
 
 int mp3s_reencode_block(mp3s_ctx *c, const uint8_t *mp3, size_t len, const uint8_t *utf8, size_t n_msg, int rank, int world,

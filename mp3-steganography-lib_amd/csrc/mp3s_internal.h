@@ -317,6 +317,21 @@ int front_end_failed(int code, int i);   // fail(code, "file %d: null pointer" f
 // The tail of every list call: the codes into status[] (when given) and the FIRST failing file's text into mp3s_last_error().
 // Returns that file's code (MP3S_OK: none failed), which fails the call when status == NULL.
 int finish_files(const FileStatus &fs, int32_t *status);
+// ... and the call's end behind it: the first failing file's code when there is no status[], else the results' owner to the caller
+int finish_list(const FileStatus &fs, int32_t *status, std::unique_ptr<mp3s_buf> &top, mp3s_buf **owner);
+
+// The front of the calls that take a list of MP3 files: m sized for n_files, file i = file_of(i) borrowed into m.files (a null pointer:
+// MP3S_E_ARG, the file is not looked at), the context's spare scan lent to a list of one, front_end(m, i) of every file on the host
+// threads.  Returns the per-file codes; their texts are the caller's.  mp3_list_done, after the last use of m.files and m.scanned:
+// the borrowed pointers dropped, the spare scan handed back.
+struct mp3s_multi;
+std::vector<int32_t> mp3_list_front(mp3s_ctx *c, mp3s_multi &m, int n_files, const std::function<std::pair<const uint8_t *, size_t>(int)> &file_of);
+void mp3_list_done(mp3s_ctx *c, mp3s_multi &m);
+// ... of the re-encoding calls (mp3s_hide_messages, mp3s_capacity_files), where a message without bytes but with a length is a null
+// file too: then per file the front end's text or the reference's checks (reencode_check), its framed message into bits[i], its
+// (sampling rate, kbps) group.  *t_scanned (when given): now_ms() between the front ends and the rest
+void reencode_list_front(mp3s_ctx *c, mp3s_multi &m, const uint8_t *const *mp3s, const size_t *lens, int n_files, const uint8_t *const *msgs,
+                         const size_t *msg_lens, FileStatus &fs, std::vector<std::vector<uint8_t>> &bits, FileGroups &groups, double *t_scanned = nullptr);
 
 // run(a, b, idx) -> code, for every group in order.  One file spoils its batch (main data the host parser rejects, a quantizer
 // step that leaves the table ...): a failed group of one fails its file, a larger one is run again file by file, run(a, b, {i}),
@@ -349,19 +364,46 @@ int decode_transform_chunk(mp3s_ctx *c, const int16_t *d_is, const mp3s_granule_
 // decode the streams `idx` of m (one channel count) as one batch; d_keep: int16 PCM stays on the device there
 int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, int out_format, void *d_keep = nullptr);
 
-// ---------------------------------------------------------------- pairs of MP3 files (mp3s_distortion_files.cpp, mp3s_alignment_files.cpp)
+// ---------------------------------------------------------------- pairs of MP3 files compared on the device (pcm_pairs.cpp)
 // frames of a stream's PCM, the frame the decoder repeats after a bad header (D12) included: what mp3s_decoded.n_rows counts, / 1152
 inline int64_t pcm_frames(const ParsedStream &p) { return (int64_t)p.n_frames + (p.dup_last_frame ? 1 : 0); }
 // out = a pair's record and what the host knows of its two streams: the ONE place a mp3s_pcm_pair_diff becomes an mp3s_pcm_distortion
+// (n_frames records of n_samples compared samples in all)
 void distortion_from_record(const mp3s_pcm_pair_diff &r, const ParsedStream &a, const ParsedStream &b, int64_t n_frames, int64_t n_samples,
                             const mp3s_pcm_frame_diff *profile, mp3s_pcm_distortion *out);
-// the front of the pair-list calls: all 2 n files as one list (file i = a[i], file n + i = b[i]) into m, per pair its code in fs, or
-// empty(i) (a stream without a frame: nothing for a decode batch), or valid(i) (same channel count and sampling rate: to be grouped)
-void pcm_pairs_front_end(const uint8_t *const *a, const size_t *a_lens, const uint8_t *const *b, const size_t *b_lens, int n_pairs, mp3s_multi &m,
-                         FileStatus &fs, const std::function<void(int)> &empty, const std::function<void(int)> &valid);
-// after decode_group of the streams (A, B of pair idx[0], A, B of pair idx[1], ...): a host re-parse inside it must have left the frame
-// counts the batch's layout was built on: na[k] / nb[k] = the frames of pair idx[k]'s streams as the layout took them
-int pcm_pairs_same_frames(const mp3s_multi &m, int n_pairs, const std::vector<int> &idx, const std::vector<int64_t> &na, const std::vector<int64_t> &nb);
+// The pairs `idx` (file idx[k] against file n_pairs + idx[k] of m, one channel count, every stream with a frame) as one batch.
+//   lay : the streams A, B of pair idx[0], A, B of pair idx[1], ... and where each lies in the PCM buffer (decode_group: frames back to
+//         back, a repeated last frame behind its stream); max_frames: what the caller's kernels can address.
+//   run : pool slots 7 (the PCM), 9 (in_bytes of `in`, made by the caller from the layout: the context's h_in) and 18 (res_bytes), the
+//         decode, a check that it left the layout's frame counts, the upload, launch(d_pcm, d_in, d_res) -> code (its own text),
+//         down_bytes of the results into part->big[2] = res, and the stream synchronised whatever happened.
+struct PcmPairBatch {
+    std::vector<int> streams;
+    std::vector<int64_t> first, frames_a, frames_b;   // per pair: the first frame of A in the buffer (B follows), the frames of A and of B
+    std::vector<int64_t> out_first;                   // ... and the whole frames both have (min) of the pairs in front: where its records begin
+    int64_t rows_frames = 0, cmp_frames = 0;          // the sums: frames of the PCM buffer, frame records
+    std::unique_ptr<mp3s_buf> part;
+    const uint8_t *res = nullptr;
+    int lay(const mp3s_multi &m, int n_pairs, const std::vector<int> &idx, int64_t max_frames);
+    int run(mp3s_ctx *c, mp3s_multi &m, int nch, const uint8_t *in, size_t in_bytes, size_t res_bytes, size_t down_bytes,
+            const std::function<int(const int16_t *d_pcm, const uint8_t *d_in, uint8_t *d_res)> &launch);
+private:
+    int n_pairs = 0;
+    const std::vector<int> *idx = nullptr;
+};
+// The shell of the pair-list calls behind their own argument checks: all 2 n files as one list (file i = a[i], file n + i = b[i])
+// through the MP3 list front, out[0 .. n_pairs) (elements of out_size bytes) zeroed, per pair its code and text ("pair %d: ..."), or
+// empty(m, i) (a stream without a frame: nothing for a decode batch; it fills out[i]), or its channel count's group; refuse(m, fs, i)
+// (may be empty) is asked first in both cases and sets the pair's code when it says true.  group(m, idx, nch, top) -> code runs a
+// batch and keeps what its results point into in a part of top; the out[] of a failed batch is zeroed again.
+int pcm_pairs_call(mp3s_ctx *c, const uint8_t *const *a, const size_t *a_lens, const uint8_t *const *b, const size_t *b_lens, int n_pairs, void *out,
+                   size_t out_size, mp3s_buf **owner, int32_t *status, const std::function<void(const mp3s_multi &m, int i)> &empty,
+                   const std::function<bool(const mp3s_multi &m, FileStatus &fs, int i)> &refuse,
+                   const std::function<int(mp3s_multi &m, const std::vector<int> &idx, int nch, mp3s_buf *top)> &group);
+// The host block of a _dev test aid (the context's h_pcm_tiles / h_pcm_align) travels on the stream behind the call: the block of the
+// call before may still be on its way, and its copy reads the vector that is written next.  Waits for ev_pcm_tiles (made on first
+// use), runs fill_and_copy() -> code, records the event behind its copy.
+int pcm_dev_host_block(mp3s_ctx *c, const std::function<int()> &fill_and_copy);
 
 // ---------------------------------------------------------------- encode pipeline (mp3s_encode_pipeline.cpp)
 constexpr int kLongMessageBits = 1024;    // above: the first pass does not guess cursors at all

@@ -176,10 +176,7 @@ static int reveal_files(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *l
         o.kbps = r.bit_rate / 1000; o.sampling_rate = r.sampling_rate; o.channels = r.nch; o.n_frames = r.n_frames;
         o.n_bits = (int32_t)bits.size(); o.bits = bits.data();
     }
-    const int first_bad = finish_files(fs, status);
-    if (!status && first_bad) return first_bad;
-    *owner = top.release();
-    return MP3S_OK;
+    return finish_list(fs, status, top, owner);
 }
 
 extern "C" {

@@ -423,9 +423,31 @@ def _file_list(files):
     return n, (files, bufs), ptrs, lens
 
 
-def _per_file(out, status, make, n=None):
-    """the answer of a list-of-files call, one entry per file: make(out[i]), or the Mp3sError status[i] names"""
-    return [Mp3sError(status[i], f"file {i}") if status[i] else make(out[i]) for i in range(len(status) if n is None else n)]
+def _per_file(out, status, make, n=None, what="file"):
+    """the answer of a list-of-files call, one entry per file (per pair: what="pair"): make(out[i]), or the Mp3sError status[i] names"""
+    return [Mp3sError(status[i], f"{what} {i}") if status[i] else make(out[i]) for i in range(len(status) if n is None else n)]
+
+
+def _pair_lists(mp3s_a, mp3s_b, none_is_null=False):
+    """two lists of byte strings as the arrays of a pair-list call -> (n, what has to stay alive beside them, a's pointers and lengths,
+    b's).  none_is_null: a file that is None travels as a null pointer, which the pair answers for"""
+    r = []
+    for files in (mp3s_a, mp3s_b):
+        n, keep, ptrs, lens = _file_list([b"" if none_is_null and f is None else f for f in files])
+        for i, f in enumerate(files):
+            if none_is_null and f is None:
+                ptrs[i] = None
+        r += [keep, ptrs, lens]
+    return n, (r[0], r[3]), r[1], r[2], r[4], r[5]
+
+
+def _with_hide_fields(out, took, diff, hidden):
+    """out[i] = diff[k] + "too_long" and "hide_offset" of hidden[i] for i = took[k] (an exception in diff[k] as it is) -> out"""
+    for i, d in zip(took, diff):
+        if not isinstance(d, Exception):
+            d = dict(d, too_long=hidden[i]["too_long"], hide_offset=hidden[i]["hide_offset"])
+        out[i] = d
+    return out
 
 
 class _Owner:
@@ -1016,12 +1038,11 @@ class Context:
             raise ValueError("one file of b per file of a")
         if len(mp3s_a) == 0:
             return []
-        n, _keep_a, fa, la = _file_list(mp3s_a)
-        _, _keep_b, fb, lb = _file_list(mp3s_b)
+        n, _keep, fa, la, fb, lb = _pair_lists(mp3s_a, mp3s_b)
         out, status, owner = (PcmDistortion * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_pcm_distortion_files(self.handle, fa, la, fb, lb, n, 1 if profile else 0, C.byref(owner), out, status))
         own = _Owner(owner)
-        return [Mp3sError(status[i], f"pair {i}") if status[i] else self._distortion(out[i], own) for i in range(n)]
+        return _per_file(out, status, lambda x: self._distortion(x, own), what="pair")
 
     def hide_distortions(self, mp3s, messages, profile=False):
         """what hiding `messages` in `mp3s` changes in the audio: hide_messages without any message (the clear re-encode) and with the
@@ -1033,12 +1054,7 @@ class Context:
         hidden = self.hide_messages(mp3s, messages)
         took = [i for i, (c, h) in enumerate(zip(clear, hidden)) if not isinstance(c, Exception) and not isinstance(h, Exception)]
         diff = self.pcm_distortions([clear[i]["data"] for i in took], [hidden[i]["data"] for i in took], profile)
-        out = [c if isinstance(c, Exception) else h for c, h in zip(clear, hidden)]
-        for i, d in zip(took, diff):
-            if not isinstance(d, Exception):
-                d = dict(d, too_long=hidden[i]["too_long"], hide_offset=hidden[i]["hide_offset"])
-            out[i] = d
-        return out
+        return _with_hide_fields([c if isinstance(c, Exception) else h for c, h in zip(clear, hidden)], took, diff, hidden)
 
     def pcm_diff_dev(self, pcm, pairs, nch):
         """test aid: k_pcm_diff_frames + k_pcm_diff_pairs alone (mp3s_pcm_diff_dev) on the int16 buffer `pcm` ([frames][1152][nch]) and
@@ -1071,12 +1087,7 @@ class Context:
             raise ValueError("one file of b (and one lag, when given) per file of a")
         if len(mp3s_a) == 0:
             return []
-        n, _keep_a, fa, la = _file_list([f if f is not None else b"" for f in mp3s_a])
-        _, _keep_b, fb, lb = _file_list([f if f is not None else b"" for f in mp3s_b])
-        for files, ptrs in ((mp3s_a, fa), (mp3s_b, fb)):             # a file that is None: a null pointer, which the pair answers for
-            for i, f in enumerate(files):
-                if f is None:
-                    ptrs[i] = None
+        n, _keep, fa, la, fb, lb = _pair_lists(mp3s_a, mp3s_b, none_is_null=True)
         given = None if lags is None else (C.c_int32 * n)(*[int(x) for x in lags])
         out, status, owner = (PcmAlignment * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_pcm_alignment_files(self.handle, fa, la, fb, lb, n, int(max_lag), int(search_rows), given, 1 if profile else 0,
@@ -1089,7 +1100,7 @@ class Context:
             d.update(lag=g.lag, n_best=g.n_best, err2_best=g.err2_best, err2_at_0=g.err2_at_0, search_first=g.search_first, search_rows=g.search_rows)
             d["scores"] = _view_owned(x.scores, np.uint64, (2 * int(max_lag) + 1,), own) if x.scores else None
             return d
-        return [Mp3sError(status[i], f"pair {i}") if status[i] else entry(out[i]) for i in range(n)]
+        return _per_file(out, status, entry, what="pair")
 
     def stego_distortions(self, mp3s, messages, max_lag=2304, search_rows=4608, profile=False):
         """how far the file handed on is from the file one started with: hide_messages, then pcm_alignments(stego, cover) over the files
@@ -1100,12 +1111,7 @@ class Context:
         hidden = self.hide_messages(mp3s, messages)
         took = [i for i, h in enumerate(hidden) if not isinstance(h, Exception)]
         diff = self.pcm_alignments([hidden[i]["data"] for i in took], [mp3s[i] for i in took], max_lag, search_rows, None, profile)
-        out = list(hidden)
-        for i, d in zip(took, diff):
-            if not isinstance(d, Exception):
-                d = dict(d, too_long=hidden[i]["too_long"], hide_offset=hidden[i]["hide_offset"])
-            out[i] = d
-        return out
+        return _with_hide_fields(list(hidden), took, diff, hidden)
 
     def pcm_align_dev(self, pcm, runs, nch, max_lag, search_rows, lags=None):
         """test aid: the three passes of k_pcmalign.hpp + k_pcm_diff_pairs alone (mp3s_pcm_align_dev) on the int16 buffer `pcm`
