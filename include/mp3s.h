@@ -1024,6 +1024,71 @@ int mp3s_pcm_alignment_files(mp3s_ctx *ctx, const uint8_t *const *a, const size_
                              int n_pairs, int max_lag, int search_rows, const int32_t *lags /* NULL = search */, int want_profile,
                              mp3s_buf **owner, mp3s_pcm_alignment *out, int32_t *status);
 
+/* ---------------------------------------------------------------- (vi-e) table audit: does a file carry a payload, and how much
+ * replaces: nothing in the reference -- its reveal reads the table indices as bits whether or not anything was hidden, so it cannot tell
+ *           a clean file from a stego file, finds no payload hidden as raw bits and none behind a damaged "<n>#" frame.
+ * The reference's encoder picks a region's code book in two steps (__new_choose_table, reference encoder/MP3_Encoder.py:1170-1264):
+ * a NATURAL choice from the region's quantised values alone, then IDX_TO_TRANSFORM_HUF[(choice, bit)] (:419-449) when a message bit
+ * is left.  A decoder sees the values exactly, so the natural choice is recomputed here from the Huffman-decoded spectrum, and every
+ * region is classified.  Units are visited as the stego bits walk them: frame, channel, granule, region.
+ *   a window-switching unit (this encoder writes none): every non-zero one of table_select[0..1] is one FOREIGN region; table_select[2]
+ *     is not in the side info and is not counted (the carry of SURVEY D10 is not followed); window_units counts the unit.
+ *   any other unit: with bv = big_values (taken as at most 288) and the frame's long-block band table,
+ *     a1 = min(sfb_long[min(region0_count + 1, 22)], 2 bv), a2 = min(sfb_long[min(region0_count + region1_count + 2, 22)], 2 bv),
+ *     a3 = 2 bv; the regions are the lines [0, a1), [a1, a2), [a2, a3).  A region with t = table_select[r] == 0 is not counted.
+ *   m = max |is| over the region's lines, 0 without lines.  m == 0: EMPTY -- the region names a book and holds no value.
+ *   m < 15:  nat = 15 if bits(15) <= bits(13), else 13.
+ *   m >= 15: c0 = the first i in 15..23, c1 = the first i in 24..31 with linmax[i] >= m - 15; nat = c1 if bits(c1) < bits(c0), else c0.
+ *     (|is| <= 8206 is what a stream can hold; above it c0 = 23 and c1 = 31.)
+ *   bits(t) = the reference's count_bit (:234-261): per pair of absolute values (x, y), for t > 15 a value above 14 adds linbits[t] and
+ *     becomes 15; then hlen_t[x * 16 + y] + (x != 0) + (y != 0).
+ *   t == nat: NATURAL.  Otherwise t == transform[nat][b] (b = 0 looked at first): FORCED with bit b, bits(t) - bits(nat) excess bits.
+ *   Anything else, every t outside {13, 15..31} included: FOREIGN -- no encoder of this family wrote the region.
+ * `regions` counts every classified region, and its running value in front of a region is the region's index; first_forced and
+ * last_forced are such indices.  Two quirks of the reference make that index differ from a position among the bits reveal returns:
+ * EMPTY regions count as stego bits for reveal (and carry nothing: the encoder writes table 0 there, so it meets none of its own), and a
+ * window-switching unit contributes its carried third index to reveal's bits but not to `regions`.  For a stream of this encoder
+ * neither happens and the index IS the position among the bits of mp3s_reveal_messages.
+ * A file this encoder wrote without a message has no FORCED region, and behind a message's end there is none; a random message forces
+ * about every second region, so last_forced + 1 is a lower bound on the payload's bits.  Exact integer arithmetic throughout. */
+#define MP3S_TA_NONE 0     /* table 0: not counted */
+#define MP3S_TA_NATURAL 1
+#define MP3S_TA_FORCED 2
+#define MP3S_TA_FOREIGN 3
+#define MP3S_TA_EMPTY 4
+typedef struct {
+    uint8_t cls[3];        /* MP3S_TA_* per region */
+    uint8_t forced_bits;   /* bit r: the message bit region r was forced with */
+    uint8_t nat[3];        /* the natural book per region (0 where none was computed: NONE, EMPTY, window switching) */
+    uint8_t window;        /* 1: a window-switching unit */
+    int16_t excess[3];     /* bits(t) - bits(nat) of a FORCED region (negative where the bit made the region cheaper: 15 -> 13), else 0 */
+    uint16_t reserved;     /* 0 */
+} mp3s_table_audit_unit; /* 16 bytes */
+typedef struct { int32_t first_frame, n_frames; } mp3s_table_audit_seg; /* 8 bytes: a stream's frames in the batch */
+typedef struct {
+    int64_t regions, natural, forced, forced_ones, foreign, empty, excess_bits;
+    int64_t first_forced, last_forced;   /* region indices, -1 when nothing is forced */
+    int32_t n_frames, channels, sampling_rate, kbps, window_units, reserved;
+    const uint32_t *profile;             /* [n_frames]: natural | forced << 4 | foreign << 8 | empty << 12 of each frame (each <= 12), or NULL */
+} mp3s_table_audit; /* 9 * 8 + 6 * 4 + 8 = 104 bytes */
+/* the two kernels alone (k_table_audit.hpp), asynchronous on the context's stream: d_is = int16 [n_frames][2 gr][2 ch][576] and d_side
+ * [n_frames] as mp3s_huffman_decode_dev takes and leaves them (of a side record big_values, table_select, the region counts and
+ * window_switching of every unit and sr_idx are read; ch 1 is ignored when nch == 1), d_segs [n_segs] the streams.  k_table_audit_units
+ * writes d_units [n_frames][4], unit ch * 2 + gr (zeros for ch 1 of a mono batch) -- optional: NULL takes a buffer the context keeps;
+ * k_table_audit_streams writes d_out [n_segs] (n_frames and channels filled in, sampling_rate, kbps and profile 0) and, with d_profile
+ * (optional, uint32 [n_frames], indexed by batch frame), the frames' words.  A stream of 0 frames gets zeros and -1 / -1.  Null
+ * pointers, n_frames <= 0, n_segs <= 0 or another nch: MP3S_E_ARG (checked without a device); the segments must lie inside the batch. */
+int mp3s_table_audit_dev(mp3s_ctx *ctx, const int16_t *d_is, const mp3s_frame_side *d_side, int n_frames, int nch,
+                         const mp3s_table_audit_seg *d_segs, int n_segs, mp3s_table_audit_unit *d_units /* optional */,
+                         mp3s_table_audit *d_out, uint32_t *d_profile /* optional */);
+/* The audit of a list of MP3 files on the frame of the list-of-files calls: the files are scanned on the host threads and grouped by
+ * channel count; per group ONE batch goes through the front half of the decode (upload, Huffman decode, the host's repair of frames the
+ * kernel flags, host-parsed streams placed) and the two kernels behind it.  No transform runs, no PCM exists; 104 bytes per file come
+ * down, and 4 a frame with want_profile != 0 (out[i].profile, owned by *owner).  kbps is the first frame's bitrate.  A file without a
+ * frame gets zeros and -1 / -1.  status[i] / mp3s_last_error() by the rule of every list call (MP3S_E_ARG for a null file). */
+int mp3s_table_audit_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int want_profile, mp3s_buf **owner,
+                           mp3s_table_audit *out, int32_t *status);
+
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference
  *           steganography.py:133-182, whose two serial frame loops (decoder/MP3_Parser.py:68-80, encoder/MP3_Encoder.py:

@@ -80,14 +80,12 @@ int decode_transform_chunk(mp3s_ctx *c, const int16_t *d_is, const mp3s_granule_
     return MP3S_OK;
 }
 
-// Decode the streams listed in `idx` (all with the same channel count) as ONE batch.
-// d_keep != nullptr: the PCM of the group stays on the device there (frames back to back, a duplicated last frame
-// included) and nothing is downloaded -- the re-encode path of mp3s_hide_message / mp3s_clear_file.
-int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, int out_format, void *d_keep)
+// The front half of a decode batch (mp3s_internal.h): layout, upload, Huffman decode, the host's repair, host-parsed streams placed.
+int decode_front(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, size_t frame_bytes, DecodeFront &F)
 {
-    const size_t esz = pcm_elem(out_format), frame_bytes = (size_t)1152 * nch * esz;
     long n = 0;
     for (int i : idx) n += m.parsed[i].n_frames;
+    F.n = n;
     if (n <= 0) return MP3S_OK;
     if (n > 0x7fffffff / 8) return fail(MP3S_E_ARG, "batch of %ld frames is too large", n);
     const double t_cat0 = trace_on() ? now_ms() : 0;
@@ -96,7 +94,8 @@ int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
     //      (tens of MB of fresh vectors per call cost more in page faults than the copy itself).
     std::vector<mp3s_frame_hdr> &hdr = c->h_hdr;
     hdr.resize((size_t)n);
-    std::vector<long> first_of(idx.size());
+    std::vector<long> &first_of = F.first_of;
+    first_of.assign(idx.size(), 0);
     bool any_dev = false, any_host = false;
     const bool in_place = idx.size() == 1 && !m.scanned[idx[0]].host_parsed;
     if (!in_place) { c->h_side.resize((size_t)n); c->h_blob.clear(); }
@@ -132,6 +131,7 @@ int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
          *d_blob = grab(blob_bytes), *d_side = grab((size_t)n * sizeof(mp3s_frame_side));
     if (!d_is || !d_si || !d_hdr || !d_pcm || !d_st || !d_blob || !d_side)
         return fail(MP3S_E_NOMEM, "hipMalloc failed for a %ld-frame decode", n);
+    F.d_is = d_is; F.d_si = d_si; F.d_hdr = d_hdr; F.d_pcm = d_pcm; F.d_st = d_st; F.d_blob = d_blob; F.d_side = d_side;
     int rc = MP3S_OK;
     const double t_up0 = trace_on() ? now_ms() : 0;
     if (any_dev) {
@@ -201,6 +201,24 @@ int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
             if (!rc) rc = mp3s_dev_upload(c, (mp3s_granule_si *)d_si + (size_t)first_of[k] * 4, p.si.data(),
                                           (size_t)p.n_frames * 4 * sizeof(mp3s_granule_si));
         }
+    return rc;
+}
+
+// Decode the streams listed in `idx` (all with the same channel count) as ONE batch.
+// d_keep != nullptr: the PCM of the group stays on the device there (frames back to back, a duplicated last frame
+// included) and nothing is downloaded -- the re-encode path of mp3s_hide_message / mp3s_clear_file.
+int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, int out_format, void *d_keep)
+{
+    const size_t esz = pcm_elem(out_format), frame_bytes = (size_t)1152 * nch * esz;
+    DecodeFront F;
+    int rc = decode_front(c, m, idx, nch, frame_bytes, F);
+    const long n = F.n;
+    if (n <= 0) return rc;
+    // (a front that failed behind its allocations goes on as it always did: the arena is reserved, nothing more is issued)
+    if (!F.d_is) return rc;
+    const std::vector<mp3s_frame_hdr> &hdr = c->h_hdr;
+    const std::vector<long> &first_of = F.first_of;
+    void *const d_is = F.d_is, *const d_si = F.d_si, *const d_hdr = F.d_hdr, *const d_pcm = F.d_pcm;
     // ---- transforms in chunks of kDecodeChunk frames; a chunk that starts inside a stream re-runs one halo frame.
     //      Host layout = device layout plus one extra frame after every stream that ends in a bad header (D12): the
     //      reference appends that stream's last PCM frame once more.

@@ -123,6 +123,11 @@ int launch_reveal(hipStream_t stream, const uint8_t *d_image, uint32_t image_bas
 // record, and with d_profile (optional, [frames of the batch]) per frame the running sum of the stream's bits up to and including it
 int launch_capacity(hipStream_t stream, const mp3s_gr_out *d_gr, const mp3s_chain_seg *d_segs, int n_segs, mp3s_capacity_seg *d_out, uint32_t *d_profile);
 
+// the table audit of a batch of Huffman-decoded streams (k_table_audit.hpp; the rule: include/mp3s.h, vi-e): a record per unit into
+// d_units [n_frames][4] (16-byte aligned), then per stream of d_segs its record and, with d_profile (optional, [n_frames]), a word per frame
+int launch_table_audit(hipStream_t stream, const int16_t *d_is, const mp3s_frame_side *d_side, int n_frames, int nch, const mp3s_table_audit_seg *d_segs,
+                       int n_segs, mp3s_table_audit_unit *d_units, mp3s_table_audit *d_out, uint32_t *d_profile);
+
 // the exact difference of pairs of frame runs of one int16 PCM buffer [frame][1152][nch] (k_pcmdiff.hpp): pass 1 writes a record per
 // compared frame (pair p's at d_frames[out_first ..]), pass 2 a record per pair.  Pass 1 takes kPcmDiffWaves frames to a workgroup and
 // finds them in d_tiles, which the host makes from the pairs' frame counts (pcm_diff_tiles; n_tiles = the grid): a pair of 0 frames has

@@ -25,6 +25,7 @@ __constant__ DevTables c_tab;
 #include "k_parse.hpp"
 #include "k_reveal.hpp"
 #include "k_capacity.hpp"
+#include "k_table_audit.hpp"
 #include "k_pcmdiff.hpp"
 #include "k_pcmalign.hpp"
 #include "k_pack.hpp"
@@ -406,6 +407,18 @@ int launch_capacity(hipStream_t stream, const mp3s_gr_out *d_gr, const mp3s_chai
 {
     if (n_segs <= 0) return 0;
     hipLaunchKernelGGL(k_capacity, dim3((unsigned)n_segs), dim3(CAP_TILE), 0, stream, d_gr, d_segs, d_out, d_profile);
+    return (int)hipGetLastError();
+}
+
+// k_table_audit_units: one workgroup per frame (a wave per unit); k_table_audit_streams behind it: one workgroup per stream
+int launch_table_audit(hipStream_t stream, const int16_t *d_is, const mp3s_frame_side *d_side, int n_frames, int nch, const mp3s_table_audit_seg *d_segs,
+                       int n_segs, mp3s_table_audit_unit *d_units, mp3s_table_audit *d_out, uint32_t *d_profile)
+{
+    if (n_frames <= 0 || n_segs <= 0) return 0;
+    if ((nch != 1 && nch != 2) || ((uintptr_t)d_is & 3) || ((uintptr_t)d_units & 15)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_table_audit_units, dim3((unsigned)n_frames), dim3(256), 0, stream, d_is, d_side, nch, d_units);
+    if (const hipError_t e = hipGetLastError()) return (int)e;
+    hipLaunchKernelGGL(k_table_audit_streams, dim3((unsigned)n_segs), dim3(TA_TILE), 0, stream, d_units, d_segs, nch, d_out, d_profile);
     return (int)hipGetLastError();
 }
 

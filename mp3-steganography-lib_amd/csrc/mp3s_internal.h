@@ -361,6 +361,18 @@ int front_end(mp3s_multi &m, int i);
 int decode_transform_chunk(mp3s_ctx *c, const int16_t *d_is, const mp3s_granule_si *d_si, const mp3s_frame_hdr *d_hdr, long first, int cnt,
                            int nch, int halo, int out_format, void *d_pcm, hipStream_t stream = nullptr /* null: the context's */,
                            hipEvent_t done = nullptr /* recorded behind the chunk's transforms (launch_decode) */);
+// The front half of a decode batch, for decode_group and the table audit (mp3s_table_audit_files.cpp) alike: the streams `idx` of m (one
+// channel count) laid end to end -- frame headers into the context's h_hdr, side records, main data --, uploaded, launch_huffman, the
+// frames the kernel flags decided by the host parser, host-parsed streams placed.  Afterwards d_is / d_si hold every frame's samples
+// and granule records; d_side holds the side records of the device-decoded streams and zeros for streams that were host-parsed when
+// the call began.  Pool slots 0 .. 6; d_pcm gets room for a chunk of frames of frame_bytes each (0: none is wanted).  n == 0: nothing
+// was done.  d_is == nullptr behind a failure: it happened in front of the allocations.
+struct DecodeFront {
+    long n = 0;                       // frames of the batch
+    std::vector<long> first_of;       // per stream of idx: its first frame in the batch
+    void *d_is = nullptr, *d_si = nullptr, *d_hdr = nullptr, *d_pcm = nullptr, *d_st = nullptr, *d_blob = nullptr, *d_side = nullptr;
+};
+int decode_front(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, size_t frame_bytes, DecodeFront &F);
 // decode the streams `idx` of m (one channel count) as one batch; d_keep: int16 PCM stays on the device there
 int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch, int out_format, void *d_keep = nullptr);
 

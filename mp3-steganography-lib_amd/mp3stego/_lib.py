@@ -150,6 +150,26 @@ class Capacity(C.Structure):
 CAPACITY_SEG_DTYPE = np.dtype([("bits", "<i8"), ("active_units", "<i4"), ("reserved", "<i4")])
 
 
+class TableAudit(C.Structure):
+    """mp3s_table_audit: what mp3s_table_audit_files answers per file and k_table_audit_streams writes per stream"""
+    _fields_ = [("regions", C.c_int64), ("natural", C.c_int64), ("forced", C.c_int64), ("forced_ones", C.c_int64), ("foreign", C.c_int64),
+                ("empty", C.c_int64), ("excess_bits", C.c_int64), ("first_forced", C.c_int64), ("last_forced", C.c_int64),
+                ("n_frames", C.c_int32), ("channels", C.c_int32), ("sampling_rate", C.c_int32), ("kbps", C.c_int32),
+                ("window_units", C.c_int32), ("reserved", C.c_int32), ("profile", C.c_void_p)]
+
+
+TABLE_AUDIT_DTYPE = np.dtype([("regions", "<i8"), ("natural", "<i8"), ("forced", "<i8"), ("forced_ones", "<i8"), ("foreign", "<i8"), ("empty", "<i8"),
+                              ("excess_bits", "<i8"), ("first_forced", "<i8"), ("last_forced", "<i8"), ("n_frames", "<i4"), ("channels", "<i4"),
+                              ("sampling_rate", "<i4"), ("kbps", "<i4"), ("window_units", "<i4"), ("reserved", "<i4"), ("profile", "<u8")])
+TABLE_AUDIT_UNIT_DTYPE = np.dtype([("cls", "u1", (3,)), ("forced_bits", "u1"), ("nat", "u1", (3,)), ("window", "u1"), ("excess", "<i2", (3,)),
+                                   ("reserved", "<u2")])
+TABLE_AUDIT_SEG_DTYPE = np.dtype([("first_frame", "<i4"), ("n_frames", "<i4")])
+assert TABLE_AUDIT_DTYPE.itemsize == 104 and TABLE_AUDIT_UNIT_DTYPE.itemsize == 16 and TABLE_AUDIT_SEG_DTYPE.itemsize == 8
+TA_NONE, TA_NATURAL, TA_FORCED, TA_FOREIGN, TA_EMPTY = 0, 1, 2, 3, 4     # MP3S_TA_*
+TABLE_AUDIT_FIELDS = ("regions", "natural", "forced", "forced_ones", "foreign", "empty", "excess_bits", "first_forced", "last_forced",
+                      "n_frames", "channels", "sampling_rate", "kbps", "window_units")
+
+
 class PcmDistortion(C.Structure):
     """mp3s_pcm_distortion: what mp3s_pcm_distortion_files answers per pair"""
     _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("n_samples", C.c_int64), ("n_diff", C.c_int64), ("first_diff", C.c_int64),
@@ -254,7 +274,8 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps",
            "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages",
            "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes",
-           "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files", "mp3s_pcm_align_dev", "mp3s_pcm_alignment_files"]
+           "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files", "mp3s_pcm_align_dev", "mp3s_pcm_alignment_files",
+           "mp3s_table_audit_dev", "mp3s_table_audit_files"]
 
 REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
 RV_BAD_REF = 1
@@ -372,6 +393,8 @@ def lib():
         L.mp3s_capacity_wavs.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, pvp, vp, vp]
         L.mp3s_capacity_text_bytes.argtypes = [i64]
         L.mp3s_capacity_text_bytes.restype = i64
+        L.mp3s_table_audit_dev.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]
+        L.mp3s_table_audit_files.argtypes = [vp, vp, vp, i32, i32, pvp, vp, vp]
         L.mp3s_pcm_diff_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp]
         L.mp3s_pcm_distortion_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, pvp, vp, vp]
         L.mp3s_pcm_align_dev.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
@@ -1020,6 +1043,59 @@ class Context:
                 if p is not None:
                     self.free(p)
         return out, prof
+
+    @staticmethod
+    def _table_audit(x, own):
+        r = {k: getattr(x, k) for k in TABLE_AUDIT_FIELDS}
+        r["payload_bits"] = x.last_forced + 1
+        r["verdict"] = "foreign" if x.foreign > 0 else ("carries" if x.forced > 0 else "clean")
+        r["profile"] = _view_owned(x.profile, np.uint32, (x.n_frames,), own) if x.profile else None
+        return r
+
+    def table_audits(self, mp3s, profile=False):
+        """does each of a list of MP3 files carry a payload, and how much (mp3s_table_audit_files): the code book the reference's
+        encoder would choose for every region from its values alone is computed again on the device from the Huffman-decoded
+        spectrum; a region whose book is that choice transformed by a bit was forced by a message bit.  No transform runs, no PCM
+        exists.  mp3s: byte strings (None: a null file, which gets its code).  Returns one entry per file: a dict with the fields of
+        mp3s_table_audit (include/mp3s.h, vi-e) plus "payload_bits" = last_forced + 1, a lower bound on the bits hidden (about half the
+        bits of a random message force nothing), and "verdict": "foreign" when some region is FOREIGN (the file was not written by
+        this encoder and the audit does not speak for it), else "carries" when some region is FORCED, else "clean"; or the Mp3sError
+        that file's front end raises.  profile: "profile" = uint32 [n_frames], natural | forced << 4 | foreign << 8 | empty << 12."""
+        if len(mp3s) == 0:
+            return []
+        n, _keep, files, lens = _file_list([b"" if f is None else f for f in mp3s])
+        for i, f in enumerate(mp3s):
+            if f is None:
+                files[i] = None
+        out, status, owner = (TableAudit * n)(), (C.c_int32 * n)(), C.c_void_p()
+        check(lib().mp3s_table_audit_files(self.handle, files, lens, n, 1 if profile else 0, C.byref(owner), out, status))
+        own = _Owner(owner)
+        return _per_file(out, status, lambda x: self._table_audit(x, own))
+
+    def table_audit_dev(self, is_, side, segs, nch, units=True, profile=True):
+        """test aid: the two audit kernels alone (mp3s_table_audit_dev) on int16 [n_frames][2][2][576] samples, FRAME_SIDE_DTYPE
+        [n_frames] side records and TABLE_AUDIT_SEG_DTYPE streams -> (TABLE_AUDIT_DTYPE [len(segs)], TABLE_AUDIT_UNIT_DTYPE
+        [n_frames][4] (unit ch * 2 + gr) or None, uint32 [n_frames] or None)"""
+        is_ = np.ascontiguousarray(is_, dtype=np.int16)
+        side = np.ascontiguousarray(side, dtype=FRAME_SIDE_DTYPE)
+        segs = np.ascontiguousarray(segs, dtype=TABLE_AUDIT_SEG_DTYPE)
+        n_frames = len(side)
+        if is_.size != n_frames * 2304:
+            raise ValueError("is_ must hold 2304 samples per side record")
+        d_is, d_side, d_segs = self.to_device(is_), self.to_device(side), self.to_device(segs)
+        d_out = self.alloc(len(segs) * TABLE_AUDIT_DTYPE.itemsize)
+        d_units = self.alloc(n_frames * 4 * TABLE_AUDIT_UNIT_DTYPE.itemsize) if units else None
+        d_prof = self.alloc(n_frames * 4) if profile else None
+        try:
+            check(lib().mp3s_table_audit_dev(self.handle, d_is, d_side, n_frames, int(nch), d_segs, len(segs), d_units, d_out, d_prof))
+            out = self.download(d_out, TABLE_AUDIT_DTYPE, (len(segs),))
+            un = self.download(d_units, TABLE_AUDIT_UNIT_DTYPE, (n_frames, 4)) if units else None
+            prof = self.download(d_prof, np.uint32, (n_frames,)) if profile else None
+        finally:
+            for p in (d_is, d_side, d_segs, d_out, d_units, d_prof):
+                if p is not None:
+                    self.free(p)
+        return out, un, prof
 
     @staticmethod
     def _distortion(x, own):
