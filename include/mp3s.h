@@ -1033,9 +1033,15 @@ int mp3s_pcm_alignment_files(mp3s_ctx *ctx, const uint8_t *const *a, const size_
  * region is classified.  Units are visited as the stego bits walk them: frame, channel, granule, region.
  *   a window-switching unit (this encoder writes none): every non-zero one of table_select[0..1] is one FOREIGN region; table_select[2]
  *     is not in the side info and is not counted (the carry of SURVEY D10 is not followed); window_units counts the unit.
- *   any other unit: with bv = big_values (taken as at most 288) and the frame's long-block band table,
- *     a1 = min(sfb_long[min(region0_count + 1, 22)], 2 bv), a2 = min(sfb_long[min(region0_count + region1_count + 2, 22)], 2 bv),
- *     a3 = 2 bv; the regions are the lines [0, a1), [a1, a2), [a2, a3).  A region with t = table_select[r] == 0 is not counted.
+ *   any other unit: with bv = big_values (taken as at most 288) and the frame's long-block band table (of the rate the frame runs at: a
+ *     frame with the reserved rate bits keeps the rate of the frame before),
+ *     e1 = sfb_long[min(region0_count + 1, 22)], e2 = sfb_long[min(region0_count + region1_count + 2, 22)], a3 = 2 bv,
+ *     a1 = min(e1, a3), a2 = min(e2, a3); the regions are the lines [0, a1), [a1, a2), [a2, a3).  A region with t = table_select[r] == 0
+ *     is not counted.
+ *   Region 0 with e1 > a3 and region 1 with e2 > a3 reach behind the big values: EMPTY, whatever they hold.  The encoder chose their book
+ *     from every line up to e1 / e2 (__subdivide, :998-1036, does not cut the two at 2 bv, and with bv == 0 leaves the bounds of an earlier
+ *     call standing), and the lines behind the big values do not reach a decoder as the encoder held them (the reference's decoder reads a
+ *     count1 quadruple in the opposite order), so the natural choice cannot be computed again there.
  *   m = max |is| over the region's lines, 0 without lines.  m == 0: EMPTY -- the region names a book and holds no value.
  *   m < 15:  nat = 15 if bits(15) <= bits(13), else 13.
  *   m >= 15: c0 = the first i in 15..23, c1 = the first i in 24..31 with linmax[i] >= m - 15; nat = c1 if bits(c1) < bits(c0), else c0.
@@ -1046,11 +1052,13 @@ int mp3s_pcm_alignment_files(mp3s_ctx *ctx, const uint8_t *const *a, const size_
  *   Anything else, every t outside {13, 15..31} included: FOREIGN -- no encoder of this family wrote the region.
  * `regions` counts every classified region, and its running value in front of a region is the region's index; first_forced and
  * last_forced are such indices.  Two quirks of the reference make that index differ from a position among the bits reveal returns:
- * EMPTY regions count as stego bits for reveal (and carry nothing: the encoder writes table 0 there, so it meets none of its own), and a
- * window-switching unit contributes its carried third index to reveal's bits but not to `regions`.  For a stream of this encoder
- * neither happens and the index IS the position among the bits of mp3s_reveal_messages.
+ * EMPTY regions count as stego bits for reveal (one that reaches behind the big values may carry a message bit, which the audit does
+ * not see; this encoder writes such regions where a unit has fewer big values than its first bands have lines, in quiet passages and at
+ * low bit rates), and a window-switching unit contributes its carried third index to reveal's bits but not to `regions`.  For a stream
+ * of this encoder the second does not happen and the index IS the position among the bits of mp3s_reveal_messages.
  * A file this encoder wrote without a message has no FORCED region, and behind a message's end there is none; a random message forces
- * about every second region, so last_forced + 1 is a lower bound on the payload's bits.  Exact integer arithmetic throughout. */
+ * about every second region it is judged in, so last_forced + 1 is a lower bound on the payload's bits.  Exact integer arithmetic
+ * throughout. */
 #define MP3S_TA_NONE 0     /* table 0: not counted */
 #define MP3S_TA_NATURAL 1
 #define MP3S_TA_FORCED 2
@@ -1084,7 +1092,7 @@ int mp3s_table_audit_dev(mp3s_ctx *ctx, const int16_t *d_is, const mp3s_frame_si
 /* The audit of a list of MP3 files on the frame of the list-of-files calls: the files are scanned on the host threads and grouped by
  * channel count; per group ONE batch goes through the front half of the decode (upload, Huffman decode, the host's repair of frames the
  * kernel flags, host-parsed streams placed) and the two kernels behind it.  No transform runs, no PCM exists; 104 bytes per file come
- * down, and 4 a frame with want_profile != 0 (out[i].profile, owned by *owner).  kbps is the first frame's bitrate.  A file without a
+ * down, and 4 a frame with want_profile != 0 (out[i].profile, owned by *owner).  sampling_rate and kbps are the last frame's, as in every list call.  A file without a
  * frame gets zeros and -1 / -1.  status[i] / mp3s_last_error() by the rule of every list call (MP3S_E_ARG for a null file). */
 int mp3s_table_audit_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int want_profile, mp3s_buf **owner,
                            mp3s_table_audit *out, int32_t *status);

@@ -76,7 +76,11 @@ __global__ __launch_bounds__(256) void k_table_audit_units(
     const int sr = min((int)fs->sr_idx, 2);
     const int bv = min((int)us->big_values, 288);
     const int i0 = min((int)us->region0_count + 1, 22), i1 = min((int)us->region0_count + (int)us->region1_count + 2, 22);
-    const int a3 = 2 * bv, a1 = min(c_tab.sfb_long[sr][i0], a3), a2 = min(c_tab.sfb_long[sr][i1], a3);   // (all even: a pair lies in one region)
+    const int a3 = 2 * bv, e1 = c_tab.sfb_long[sr][i0], e2 = c_tab.sfb_long[sr][i1];
+    const int a1 = min(e1, a3), a2 = min(e2, a3);         // (all even: a pair lies in one region)
+    // The encoder chose a book for regions 0 and 1 from every line up to e1 and e2 (__subdivide does not cut them at 2 bv), and the
+    // lines behind the big values do not reach a decoder as the encoder held them: such a region is not judged
+    const bool unseen[3] = {e1 > a3, e2 > a3, false};
     // ---- the lane's pairs: |x| | |y| << 16, their region (3: behind the big values), their packed length word
     const uint32_t *row = reinterpret_cast<const uint32_t *>(is + (f * 4 + (size_t)(gr * 2 + ch)) * 576);
     uint32_t mx[3] = {0, 0, 0}, h[TA_NP];
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(256) void k_table_audit_units(
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         if (!t[q]) continue;
-        if (!mx[q]) { rec.cls[q] = MP3S_TA_EMPTY; continue; }
+        if (unseen[q] || !mx[q]) { rec.cls[q] = MP3S_TA_EMPTY; continue; }
         const bool second = mx[q] < 15 ? s[q][1] <= s[q][0] : s[q][1] < s[q][0];
         const int nat = second ? cand[q][1] : cand[q][0];
         const uint32_t nat_bits = second ? s[q][1] : s[q][0];

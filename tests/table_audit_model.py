@@ -62,12 +62,16 @@ def audit_unit(spec, u, sr_idx):
     sfb = T["sfb_long"][min(int(sr_idx), 2)]
     r0, r1 = int(u["region0_count"]), int(u["region1_count"])
     a3 = 2 * bv
-    a1 = min(int(sfb[min(r0 + 1, 22)]), a3)
-    a2 = min(int(sfb[min(r0 + r1 + 2, 22)]), a3)
+    e1, e2 = int(sfb[min(r0 + 1, 22)]), int(sfb[min(r0 + r1 + 2, 22)])   # where the encoder's regions 0 and 1 end: not cut at a3
+    a1, a2 = min(e1, a3), min(e2, a3)
     bounds = [(0, a1), (a1, a2), (a2, a3)]
+    unseen = [e1 > a3, e2 > a3, False]                             # the region reaches behind the big values
     v_all = np.abs(spec.astype(np.int64))
     for r, (lo, hi) in enumerate(bounds):
         if t[r] == 0:
+            continue
+        if unseen[r]:
+            rec["cls"][r] = EMPTY
             continue
         v = v_all[lo:hi] if hi > lo else v_all[:0]
         m = int(v.max()) if len(v) else 0
@@ -101,15 +105,18 @@ def audit_unit(spec, u, sr_idx):
     return rec
 
 
-def audit_units(is_, side, nch):
-    """int16 [n][2 gr][2 ch][576], FRAME_SIDE records [n] -> UNIT_DTYPE [n][4], unit ch * 2 + gr (zeros for ch 1 of a mono batch)"""
+def audit_units(is_, side, nch, sr_idx=None):
+    """int16 [n][2 gr][2 ch][576], FRAME_SIDE records [n] -> UNIT_DTYPE [n][4], unit ch * 2 + gr (zeros for ch 1 of a mono batch);
+    sr_idx: each frame's rate index from somewhere else than the side records (None: theirs)"""
     n = len(side)
+    rates = side["sr_idx"] if sr_idx is None else sr_idx
+    assert len(rates) == n
     is_ = np.asarray(is_).reshape(n, 2, 2, 576)
     out = np.zeros((n, 4), dtype=UNIT_DTYPE)
     for f in range(n):
         for ch in range(nch):
             for gr in range(2):
-                out[f, ch * 2 + gr] = audit_unit(is_[f, gr, ch], side[f]["unit"][gr][ch], side[f]["sr_idx"])
+                out[f, ch * 2 + gr] = audit_unit(is_[f, gr, ch], side[f]["unit"][gr][ch], rates[f])
     return out
 
 
@@ -140,15 +147,16 @@ def audit_stream(units):
     return r, profile
 
 
-def audit_file(mlib, data):
-    """the whole answer for one MP3 file: the counters, n_frames, channels, sampling_rate, kbps, payload_bits, verdict, profile"""
+def audit_file(mlib, data, sr_idx=None):
+    """the whole answer for one MP3 file: the counters, n_frames, channels, sampling_rate, kbps, payload_bits, verdict, profile;
+    sr_idx: each frame's rate index where the caller knows it from the way the stream was built (None: the scan's)"""
     p, s = mlib.parse_stream(data), mlib.scan_stream(data)
     assert p["n_frames"] == s["n_frames"]
     n = p["n_frames"]
     if n == 0:
         r, profile = audit_stream(np.zeros((0, 4), dtype=UNIT_DTYPE))
     else:
-        r, profile = audit_stream(audit_units(p["is"], s["side"], p["channels"]))
+        r, profile = audit_stream(audit_units(p["is"], s["side"], p["channels"], sr_idx))
     r.update(n_frames=n, channels=p["channels"], sampling_rate=p["sampling_rate"], kbps=p["bit_rate"] // 1000)
     r["payload_bits"] = r["last_forced"] + 1
     r["verdict"] = "foreign" if r["foreign"] > 0 else ("carries" if r["forced"] > 0 else "clean")

@@ -114,6 +114,19 @@ def family_f():
             "f_to_stereo_late": concat(*[_seg(343, 100, bitrate_idx=9, mode=3)] * 30, _seg(344, 4, bitrate_idx=9))}
 
 
+G_RESERVED = (5, 6, 14, 23, 31, 39)                   # frames of family_g that carry the reserved rate bits; 39 is the last
+G_SR_IDX = {name: [3 if f in G_RESERVED else sr for f in range(40)] for name, sr in (("g_reserved_48_long", 1), ("g_reserved_44_long", 0))}
+
+
+@functools.lru_cache(maxsize=None)
+def family_g():
+    """reserved rate bits inside long-block streams at 48 and at 44.1 kHz: every reserved frame has regions whose bounds are those of
+    the rate it inherits (neither is the 32 kHz row that clamping the header's two bits to 2 would pick).  The streams of the list
+    calls' tests only (tests/test_list_calls_foreign.py): not part of all_good()"""
+    return {name: make_stream(351 + k, 40, sr_idx=sr, bitrate_idx=_vbr(40, 4 + k), block_types=(0,))
+            for k, (name, sr) in enumerate(G_SR_IDX.items())}
+
+
 def all_good():
     """every family of streams the library decodes"""
     out = {}
