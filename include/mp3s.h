@@ -41,7 +41,7 @@ extern "C" {
 #define MP3S_E_EXIT (-8)        /* the reference calls sys.exit(text) here; the text is in mp3s_last_error() */
 #define MP3S_E_BUSY (-9)        /* mp3s_pipe_submit: every slot is taken, collect a result first; mp3s_pipe_collect: nothing pending */
 #define MP3S_E_TABLES (-10)     /* a constant table built with this host's libm is not the one a kernel was compiled for (the encoder's analysis
-                                 * filter: csrc/analysis_plan.h); the encode entry points refuse, decoding works */
+                                 * filter: csrc/analysis_plan.h, csrc/analysis_sign_plan.h); the encode entry points refuse, decoding works */
 
 #define MP3S_PCM_I16 0 /* (pcm*32767) truncated toward zero, low 16 bits: reference decoder/MP3_Parser.py:91 */
 #define MP3S_PCM_F32 1
@@ -160,7 +160,12 @@ int mp3s_ctx_wait_last(mp3s_ctx *ctx, mp3s_ctx *other);
                                     * no encode scratch, 221 MB less traffic per 10 000 frames); 0 (default): two kernels with the samples in device memory --
                                     * measured faster: the one kernel's workgroup barriers and its 67 KB of LDS per workgroup cost more than the round trip
                                     * through memory [MP3S_FUSED_ENCODE=1 -> 1] */
-#define MP3S_OPT_PIPE_DEC 17       /* 1: a pipe created on this context runs the decode transform of job k + 1 on a stream of its own, under the encode
+#define MP3S_OPT_ANALYSIS_SHARED 0 /* 1 (default): the analysis filter bank (k_enc_analysis, k_enc_fused) computes a product once for coefficients that are equal
+                                    * up to SIGN (csrc/analysis_sign_plan.h: 1 030 products per slot; the negated product follows exactly from the positive
+                                    * one), wave by wave wherever no window sum it would negate is zero -- bit-identical; 0: every wave of a launch takes the
+                                    * matrixing that shares equal coefficients only (1 516 products), which waves of silence and stream starts take either
+                                    * way.  (Number 0: the slot the numbering had left free.) [MP3S_ANALYSIS_SHARED=0 -> 0] */
+#define MP3S_OPT_PIPE_DEC 17      /* 1: a pipe created on this context runs the decode transform of job k + 1 on a stream of its own, under the encode
                                     * transforms and the rate loop of job k [MP3S_PIPE_DEC=0|1] */
 #define MP3S_OPT_RATE_SIGNALS 18   /* 1: the dispatch of the rate loop (mp3s_rate_variants_dev, mp3s_rate_loop_dev) carries the context's order event as its
                                     * completion signal: another context's mp3s_ctx_wait_last(other, this) then waits for the rate loop without a

@@ -4,7 +4,11 @@
 //                    321-370, 751-758) + the odd-slot/odd-band sign flip (:676-679).
 //                    lane = time slot (32 new PCM samples); its 512-sample window is read from an
 //                    LDS tile (rows padded to 80 B so 16-byte reads are conflict free), enwindow and
-//                    the 32x64 matrix fl are scalar operands.
+//                    the 32x64 matrix fl are scalar operands.  The matrixing computes a product once
+//                    for coefficients that are equal up to sign (analysis_sign_plan.h, 1 030 products
+//                    per slot) in every wave that holds no zero window sum, and once for equal
+//                    coefficients (analysis_plan.h, 1 516) in the others and with
+//                    MP3S_OPT_ANALYSIS_SHARED 0 -- both bit for bit the reference's sums.
 //   k_enc_mdct     : 36->18 MDCT with the fused sine window + alias butterflies (:681-744).
 //                    lane = (channel, band); cos_l is a scalar operand, the butterfly partner comes
 //                    from the neighbouring lane.
@@ -15,6 +19,7 @@
 #pragma once
 #include <type_traits>
 #include "analysis_plan.h"
+#include "analysis_sign_plan.h"
 
 namespace mp3s {
 
@@ -43,6 +48,21 @@ constexpr int ENC_ROW = 34;   // int16 per LDS row: 32 samples + 2 pad: 17 dword
 constexpr int ENC_LDS_DW = 79 * 17 + 1;   // per-wave LDS in dwords: the PCM tile (79 rows of 17 dwords), then -- twice -- a 64 x 16 half of the output tile (rows of 17):
                                       // 5.4 KB per wave, 21.5 per workgroup: five workgroups = five waves per SIMD fit a CU's LDS (8.4 KB per wave and four until round 4)
 
+// analysis_sign_plan.h at compile time: the pass of product n, and its place within the run of products of its pass that feed the same set
+constexpr int sign_plan_pass(int n)
+{
+    int p = 0;
+    while (p < 7 && n >= ANALYSIS_SIGN_FIRST[p + 1]) p++;
+    return p;
+}
+constexpr int sign_plan_pos(int n)
+{
+    int pos = 0;
+    if (n >= ANALYSIS_SIGN_PRODUCTS) return 0;
+    while (n - pos > ANALYSIS_SIGN_FIRST[sign_plan_pass(n)] && ANALYSIS_SIGN_SET[n - pos - 1] == ANALYSIS_SIGN_SET[n]) pos++;
+    return pos;
+}
+
 // The analysis of 64 consecutive slots t0 .. t0 + 63 of channel ch by one wave (lane = slot).  `lds`: ENC_LDS_DW dwords of the wave's own.
 // TILE == false (k_enc_analysis): the subband samples go to SB in device memory, int32 [ch][Ts][32] (a 128-byte row per slot, bands at sb_pos), staged
 // through `lds` so that they leave as 16-byte pieces of the rows.  TILE == true (k_enc_fused): they go to `rows` in LDS, row r of the
@@ -51,7 +71,7 @@ constexpr int ENC_LDS_DW = 79 * 17 + 1;   // per-wave LDS in dwords: the PCM til
 constexpr int ENC_TROW = 33;  // dwords per row of the fused kernel's tile (32 bands + 1: the slot lanes' writes and the band lanes' reads are conflict free)
 template <bool TILE, class Between>
 __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pcm, const mp3s_frame_hdr *__restrict__ hdr, long Ts, int ch, long t0, int lane,
-                                                  uint32_t *lds, int32_t *__restrict__ SB, uint32_t *rows, long tile_t0, long lo, long hi, Between between)
+                                                  uint32_t *lds, int32_t *__restrict__ SB, uint32_t *rows, long tile_t0, long lo, long hi, bool shared, Between between)
 {
     int16_t *tw = reinterpret_cast<int16_t *>(lds);
     // stage rows t0-15 .. t0+63 of channel ch (zeros outside the batch): the tile is one contiguous piece of the interleaved PCM,
@@ -175,6 +195,7 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
 #pragma unroll
         for (int o = 0; o < 4; o++) c[o] = *(const i32x8 __attribute__((address_space(4))) *)(flp + O[o] * 64 + 8 * B);
     };
+    auto matrix_equal = [&](auto &&finish_pass) {
     load_block(std::integral_constant<int, 0>{}, cur);
     static_for<0, 64>([&](auto nc) {
         constexpr int N = decltype(nc)::value, P = N >> 3, B = N & 7;
@@ -207,6 +228,17 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
             if (j == 2) __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (B == 7) {
+            finish_pass(std::integral_constant<int, P>{});
+            a[0] = a[1] = a[2] = a[3] = 0;
+        }
+        if constexpr (N < 63) {
+#pragma unroll
+            for (int o = 0; o < 4; o++) cur[o] = nxt[o];
+        }
+    });
+    };
+    auto finish_pass = [&](auto pc) {
+            constexpr int P = decltype(pc)::value;
             // ---- the pass's four bands are complete.  Odd bands of odd slots change sign (:365-368): bands P and 16 + P are odd with P, 15 - P and 31 - P with P even
             if (odd_slot) {
                 if (P & 1) { a[0] = (int32_t)(0u - (uint32_t)a[0]); a[2] = (int32_t)(0u - (uint32_t)a[2]); }
@@ -221,7 +253,6 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
             ot[lane * 17 + 8 + q] = (uint32_t)a[2];           // piece 2: bands 16 + 4g ..
             ot[lane * 17 + 12 + 3 - q] = (uint32_t)a[3];      // piece 3: bands 28 - 4g ..
             }
-            a[0] = a[1] = a[2] = a[3] = 0;
             if constexpr (q == 3 && !TILE) {
                 // ---- sixteen bands of the 64 slots are complete: out 16 bytes per lane, four lanes (= four pieces) per row, sixteen rows per trip
                 constexpr int g = P >> 2;
@@ -239,12 +270,103 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 __builtin_amdgcn_wave_barrier();         // (the tile is free for the other sixteen bands)
             }
-        }
-        if constexpr (N < 63) {
+    };
+    // ---- The same sums with a product computed once wherever coefficients of a pass's column are equal in ABSOLUTE value (analysis_sign_plan.h,
+    // generated from the table's values: 1 030 products per slot).  The cosine's second symmetry is negation, and the negated product follows
+    // exactly from the positive one: mulhi(y, -c) = -mulhi(y, c) - [low32(y c) != 0].  For y != 0 the low word is never zero (the generator
+    // proves it from the window's values), so the correction of an output is a constant, the number of negated products that feed it: its sum
+    // starts there.  A pass's products come ordered by the set of (output, sign) they feed: those of one output go straight into its sum, the
+    // shared ones into ONE partial sum S that is folded into its outputs where the set changes -- two products per v_add3_u32 either way.
+    // The coefficients are a stream of their own in consumption order (c_fl_sign, built by the host from fl), 32 per block, a block ahead as above.
+    fl_ptr fsp = (fl_ptr)&c_fl_sign[0];
+    auto load_sign_block = [&](auto bc, i32x8 (&c)[4]) {
+        constexpr int Bk = decltype(bc)::value;
+#pragma unroll
+        for (int o = 0; o < 4; o++) c[o] = *(const i32x8 __attribute__((address_space(4))) *)(fsp + Bk * ANALYSIS_SIGN_BLOCK + 8 * o);
+    };
+    auto matrix_signed = [&]() {
+    static_assert(ANALYSIS_SIGN_BLOCK == 32 && ANALYSIS_SIGN_STREAM % ANALYSIS_SIGN_BLOCK == 0, "four s_load_dwordx8 per block");
+    constexpr int NBLK = ANALYSIS_SIGN_STREAM / ANALYSIS_SIGN_BLOCK;
+    uint32_t S = 0, pend = 0;
+    asm volatile("" : "+s"(fsp));            // (the stream's address once, as the table's above -- taken here, where only this path keeps it)
+#pragma unroll
+    for (int o = 0; o < 4; o++) a[o] = -ANALYSIS_SIGN_NEG[0][o];
+    load_sign_block(std::integral_constant<int, 0>{}, cur);
+    static_for<0, NBLK>([&](auto bc) {
+        constexpr int Bk = decltype(bc)::value;
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xc07f);      // this block's coefficients are here; nothing else is outstanding
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (Bk + 1 < NBLK) load_sign_block(std::integral_constant<int, Bk + 1>{}, nxt);
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<0, ANALYSIS_SIGN_BLOCK / 8>([&](auto qc) {
+            // eight products, then their sums: the multiplies stand side by side (the compiler puts a wait state between a product and a sum
+            // that follows it directly), and the barrier behind the sums bounds the scheduler's hoisting
+            constexpr int Q = decltype(qc)::value;
+            uint32_t m[8];
+            static_for<0, 8>([&](auto ic) {
+                constexpr int I = Q * 8 + decltype(ic)::value, n = Bk * ANALYSIS_SIGN_BLOCK + I;
+                if constexpr (n < ANALYSIS_SIGN_PRODUCTS) m[I & 7] = (uint32_t)mulhi_vs(y[ANALYSIS_SIGN_COL[n]], cur[I >> 3][I & 7]);
+            });
+            static_for<0, 8>([&](auto ic) {
+                constexpr int I = Q * 8 + decltype(ic)::value, n = Bk * ANALYSIS_SIGN_BLOCK + I;
+                if constexpr (n < ANALYSIS_SIGN_PRODUCTS) {
+                    constexpr int P = sign_plan_pass(n), pos = sign_plan_pos(n);
+                    constexpr unsigned set = ANALYSIS_SIGN_SET[n];
+                    constexpr bool last = sign_plan_pos(n + 1) == 0;                      // of its set within the pass
+                    constexpr bool multi = ((set & 0x55u) & ((set & 0x55u) - 1u)) != 0;   // feeds more than one output
+                    if constexpr ((pos & 1) == 0 && !last) pend = m[I & 7];               // leaves with its successor, in one v_add3_u32
+                    else {
+                        const uint32_t two = (pos & 1) ? pend + m[I & 7] : m[I & 7];
+                        if constexpr (!multi) {
+#pragma unroll
+                            for (int o = 0; o < 4; o++)
+                                if ((set >> (2 * o)) & 1u) a[o] = (int32_t)((uint32_t)a[o] + two);
+                        } else {
+                            if constexpr (pos < 2) S = two; else S += two;
+                            if constexpr (last) {
+#pragma unroll
+                                for (int o = 0; o < 4; o++) {
+                                    const unsigned f = (set >> (2 * o)) & 3u;
+                                    if (f == 1u) a[o] = (int32_t)((uint32_t)a[o] + S);
+                                    if (f == 3u) a[o] = (int32_t)((uint32_t)a[o] - S);
+                                }
+                            }
+                        }
+                    }
+                    if constexpr (n + 1 == ANALYSIS_SIGN_FIRST[P + 1]) {
+                        finish_pass(std::integral_constant<int, P>{});
+                        if constexpr (P < 7) {
+#pragma unroll
+                            for (int o = 0; o < 4; o++) a[o] = -ANALYSIS_SIGN_NEG[P + 1][o];
+                        }
+                    }
+                }
+            });
+            // (sums are not re-associated across the groups of eight; within one the empty statement would cost a wait state in front of the next sum)
+            asm("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(S), "+v"(pend));
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        if constexpr (Bk + 1 < NBLK) {
 #pragma unroll
             for (int o = 0; o < 4; o++) cur[o] = nxt[o];
         }
     });
+    };
+    // Which way: one wave-uniform test.  The constant correction holds for a wave none of whose lanes that count (slots of the batch; of the tile)
+    // holds a zero y in a column that takes part in a negated share; any other wave -- silence, a stream's first slots -- takes the matrixing
+    // above, exact for every input.  (Unsigned minimum over those columns: zero iff one of them is.)
+    bool use_signed = shared;
+    if (shared) {
+        uint32_t ymin = 0xffffffffu;
+        static_for<0, 64>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            if constexpr ((ANALYSIS_SIGN_ZERO_COLS >> k) & 1u) ymin = ymin < (uint32_t)y[k] ? ymin : (uint32_t)y[k];
+        });
+        const bool counts = valid && (!TILE || (t >= lo && t < hi));
+        use_signed = __ballot(counts && ymin == 0u) == 0;
+    }
+    if (use_signed) matrix_signed(); else matrix_equal(finish_pass);
 }
 
 // SB layout: int32 [ch][Ts][32] with Ts = n_frames * 36 slots (a 128-byte row per slot); band b of a slot sits at sb_pos(b) of its row -- the order in
@@ -254,7 +376,7 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
 __device__ __forceinline__ int sb_pos(int band) { return (int)((0x37621540u >> (4 * (band >> 2))) & 7u) * 4 + (band & 3); }
 __global__ __launch_bounds__(256, 5) void k_enc_analysis(
     const int16_t *__restrict__ pcm, const mp3s_frame_hdr *__restrict__ hdr, int n_frames,
-    int32_t *__restrict__ SB, long Ts)
+    int32_t *__restrict__ SB, long Ts, int shared)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[4][ENC_LDS_DW];
     static_assert(79 * ENC_ROW * 2 <= ENC_LDS_DW * 4, "PCM tile must fit");
@@ -263,7 +385,7 @@ __global__ __launch_bounds__(256, 5) void k_enc_analysis(
     const int ch = (int)(wid & 1);
     const long t0 = (wid >> 1) * 64;          // first slot of this wave
     if (t0 >= Ts) return;
-    enc_analysis_wave<false>(pcm, hdr, Ts, ch, t0, lane, lds_all[wave], SB, nullptr, 0, 0, 0, [] {});
+    enc_analysis_wave<false>(pcm, hdr, Ts, ch, t0, lane, lds_all[wave], SB, nullptr, 0, 0, 0, shared != 0, [] {});
 }
 
 // mdct layout: int32 [frame][ch][gr][576]  (reference __mdct_freq)
@@ -388,7 +510,7 @@ static_assert(EF_WAVES * ENC_LDS_DW <= EF_TILE_DW, "the waves' PCM staging fits 
 static_assert(((EF_GR + 1) / 2) * 4 * MD_BLK <= EF_TILE_DW, "the MDCT waves' butterfly tiles fit the tile");
 
 __global__ __launch_bounds__(EF_WAVES * 64, 4) void k_enc_fused(
-    const int16_t *__restrict__ pcm, const mp3s_frame_hdr *__restrict__ hdr, int n_frames, int32_t *__restrict__ mdct)
+    const int16_t *__restrict__ pcm, const mp3s_frame_hdr *__restrict__ hdr, int n_frames, int32_t *__restrict__ mdct, int shared)
 {
     __shared__ __attribute__((aligned(16))) uint32_t tile[EF_TILE_DW];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -400,7 +522,7 @@ __global__ __launch_bounds__(EF_WAVES * 64, 4) void k_enc_fused(
         const int ch = wave >> 2;
         const long t0 = t_first + 64 * (wave & 3);
         uint32_t *rows = tile + ((long)ch * (EF_SLOTS + 1) + 1) * ENC_TROW;
-        enc_analysis_wave<true>(pcm, hdr, Ts, ch, t0, lane, tile + wave * ENC_LDS_DW, nullptr, rows, t_first, t_first, t_first + EF_SLOTS,
+        enc_analysis_wave<true>(pcm, hdr, Ts, ch, t0, lane, tile + wave * ENC_LDS_DW, nullptr, rows, t_first, t_first, t_first + EF_SLOTS, shared != 0,
                                 [] { __syncthreads(); });
     }
     __syncthreads();                                               // every row of the tile is written

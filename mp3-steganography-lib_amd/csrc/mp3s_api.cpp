@@ -128,6 +128,7 @@ int mp3s_ctx_create(int device, mp3s_ctx **out)
         c->opt[MP3S_OPT_FAIL_CHUNK] = 0;
         c->opt[MP3S_OPT_FUSED_DECODE] = env("MP3S_FUSED_DECODE", 1) != 0;
         c->opt[MP3S_OPT_FUSED_ENCODE] = env("MP3S_FUSED_ENCODE", 0) != 0;
+        c->opt[MP3S_OPT_ANALYSIS_SHARED] = env("MP3S_ANALYSIS_SHARED", 1) != 0;
         c->opt[MP3S_OPT_PIPE_DEC] = env("MP3S_PIPE_DEC", 0) != 0;
         c->opt[MP3S_OPT_RATE_SIGNALS] = env("MP3S_RATE_SIGNALS", 0) != 0;
         c->opt[MP3S_OPT_PIPE_SIGNALS] = env("MP3S_PIPE_SIGNALS", 0) & 3;
@@ -191,7 +192,7 @@ int mp3s_ctx_host_share(mp3s_ctx *c, mp3s_host_share *out)
 
 int mp3s_ctx_set_option(mp3s_ctx *c, int option, int64_t value)
 {
-    if (!c || option <= 0 || option >= MP3S_OPT_COUNT) return fail(MP3S_E_ARG, "unknown option %d", option);
+    if (!c || option < 0 || option >= MP3S_OPT_COUNT) return fail(MP3S_E_ARG, "unknown option %d", option);
     if (value < 0 || ((option == MP3S_OPT_CHUNK_FRAMES || option == MP3S_OPT_FIRST_CHUNK_FRAMES) && value != 0 && value < 4) || (option == MP3S_OPT_SCAN_THREADS && value > 64))
         return fail(MP3S_E_ARG, "option %d: value %lld out of range", option, (long long)value);
     if (option == MP3S_OPT_WAV_RESAMPLE && value != 0 && value != 1 && value != 32000 && value != 44100 && value != 48000)
@@ -212,7 +213,7 @@ int mp3s_ctx_run_stats(mp3s_ctx *c, mp3s_run_stats *out)
 
 int mp3s_ctx_get_option(mp3s_ctx *c, int option, int64_t *value)
 {
-    if (!c || !value || option <= 0 || option >= MP3S_OPT_COUNT) return fail(MP3S_E_ARG, "unknown option %d", option);
+    if (!c || !value || option < 0 || option >= MP3S_OPT_COUNT) return fail(MP3S_E_ARG, "unknown option %d", option);
     *value = c->opt[option];
     return MP3S_OK;
 }
@@ -467,15 +468,15 @@ int mp3s_encode_transform_dev(mp3s_ctx *c, const int16_t *d_pcm, const mp3s_fram
 {
     if (!c || !d_pcm || !d_hdr || !d_mdct) return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0) return fail(MP3S_E_ARG, "n_frames=%d", n_frames);
-    // k_enc_analysis computes a product once where the filter table repeats itself (analysis_plan.h, generated from the table's values): a
+    // k_enc_analysis computes a product once where the filter table repeats itself, exactly or up to sign (analysis_plan.h, analysis_sign_plan.h, generated from the table's values): a
     // host whose libm rounds the table differently gets no wrong subband samples -- the encode entry points refuse, decoding is not affected
     if (!host_tables().analysis_plan_ok)
         return fail(MP3S_E_TABLES, "the analysis filter table built on this host does not repeat itself where the kernel shares products "
-                                   "(csrc/analysis_plan.h: run tools/gen_analysis_plan.py here and rebuild)");
+                                   "(csrc/analysis_plan.h, csrc/analysis_sign_plan.h: run tools/gen_analysis_plan.py and tools/gen_analysis_sign_plan.py here and rebuild)");
     const bool fused = c->opt[MP3S_OPT_FUSED_ENCODE] != 0;
     int rc = fused ? MP3S_OK : c->ensure_scratch_enc(enc_scratch_bytes(n_frames));   // (the fused kernel keeps the subband samples in LDS)
     if (rc) return rc;
-    const int e = launch_encode(c->stream, d_pcm, d_hdr, n_frames, d_mdct, c->scratch_enc, &c->prof, fused);
+    const int e = launch_encode(c->stream, d_pcm, d_hdr, n_frames, d_mdct, c->scratch_enc, &c->prof, fused, c->opt[MP3S_OPT_ANALYSIS_SHARED] != 0);
     if (e) return fail(MP3S_E_HIP, "encode launch: %s", hipGetErrorString((hipError_t)e));
     return MP3S_OK;
 }

@@ -10,9 +10,13 @@
 #include "mp3s_device.h"
 #include "mp3s_host.h"
 #include "mp3s_tables.h"
+#include "analysis_sign_plan.h"
 
 namespace mp3s {
 __constant__ DevTables c_tab;
+// the analysis filter's coefficients in the order k_enc_analysis consumes them when it shares products up to sign (analysis_sign_plan.h;
+// HostTables::fl_sign).  A symbol of its own: DevTables' layout is mirrored by the Python package and the rate loop copies from it by offset
+__constant__ __attribute__((aligned(64))) int32_t c_fl_sign[ANALYSIS_SIGN_STREAM];
 }
 
 #include "k_wave.hpp"
@@ -69,6 +73,9 @@ int dev_upload_tables(hipStream_t stream)
 {
     const HostTables &h = host_tables();
     hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(c_tab), &h.dev, sizeof(DevTables), 0, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return (int)e;
+    static_assert(sizeof h.fl_sign == sizeof(int32_t) * ANALYSIS_SIGN_STREAM, "the coefficient stream and its symbol");
+    e = hipMemcpyToSymbolAsync(HIP_SYMBOL(c_fl_sign), h.fl_sign, sizeof h.fl_sign, 0, hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) return (int)e;
     return (int)hipStreamSynchronize(stream);
 }
@@ -191,13 +198,13 @@ size_t enc_scratch_bytes(int n_frames)
 }
 
 int launch_encode(hipStream_t stream, const int16_t *d_pcm, const mp3s_frame_hdr *d_hdr, int n_frames, int32_t *d_mdct,
-                  void *d_scratch, Profiler *prof, bool fused)
+                  void *d_scratch, Profiler *prof, bool fused, bool analysis_shared)
 {
     if (fused) {
         // analysis and MDCT as one kernel, the subband samples in LDS (k_enc_fused); timed as the analysis
         const long n_gran = (long)n_frames * 2;
         const int pf = prof ? prof->begin(stream, K_ENC_ANALYSIS) : -1;
-        hipLaunchKernelGGL(k_enc_fused, dim3((unsigned)((n_gran + EF_GR - 1) / EF_GR)), dim3(EF_WAVES * 64), 0, stream, d_pcm, d_hdr, n_frames, d_mdct);
+        hipLaunchKernelGGL(k_enc_fused, dim3((unsigned)((n_gran + EF_GR - 1) / EF_GR)), dim3(EF_WAVES * 64), 0, stream, d_pcm, d_hdr, n_frames, d_mdct, (int)analysis_shared);
         if (prof) prof->end(stream, pf);
         return (int)hipGetLastError();
     }
@@ -206,7 +213,7 @@ int launch_encode(hipStream_t stream, const int16_t *d_pcm, const mp3s_frame_hdr
     const long waves = 2 * ((Ts + 63) / 64);
     int pp = prof ? prof->begin(stream, K_ENC_ANALYSIS) : -1;
     hipLaunchKernelGGL(k_enc_analysis, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, d_pcm, d_hdr, n_frames, SB,
-                       Ts);
+                       Ts, (int)analysis_shared);
     if (prof) prof->end(stream, pp);
     pp = prof ? prof->begin(stream, K_ENC_MDCT) : -1;
     hipLaunchKernelGGL(k_enc_mdct, dim3((n_frames + 3) / 4), dim3(256), 0, stream, (const int32_t *)SB, Ts, d_hdr, n_frames,

@@ -4,6 +4,7 @@
 #include "mp3s_tables.h"
 #include "iso_tables.h"
 #include "analysis_plan.h"
+#include "analysis_sign_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -323,6 +324,35 @@ void build()
             }
             if (word != ANALYSIS_PLAN[p][k]) H.analysis_plan_ok = false;
         }
+    // ... and its other matrixing once where they are equal up to SIGN (analysis_sign_plan.h, tools/gen_analysis_sign_plan.py): every product
+    // of that plan must feed outputs whose coefficients HERE are the representative's with the recorded signs, and the products must cover
+    // every coefficient of the table that is not zero exactly once.  The kernel's coefficient stream is the representatives in plan order.
+    {
+        static_assert(sizeof H.fl_sign == sizeof(int32_t) * ANALYSIS_SIGN_STREAM, "HostTables::fl_sign holds the plan's stream");
+        uint8_t fed[32][64] = {};
+        for (int p = 0; p < 8; p++) {
+            const int o[4] = {p, 15 - p, 16 + p, 31 - p};
+            for (int n = ANALYSIS_SIGN_FIRST[p]; n < ANALYSIS_SIGN_FIRST[p + 1]; n++) {
+                const int k = ANALYSIS_SIGN_COL[n];
+                const unsigned set = ANALYSIS_SIGN_SET[n];
+                int32_t rep = 0;
+                bool have = false;
+                for (int j = 0; j < 4; j++) {
+                    const unsigned f = (set >> (2 * j)) & 3u;
+                    if (!f) continue;
+                    const int32_t c = T.fl[o[j]][k];
+                    if (!have) { rep = c; have = true; if (f != 1u) H.analysis_plan_ok = false; }
+                    if (c == 0 || c == INT32_MIN || (int64_t)c != (f == 1u ? (int64_t)rep : -(int64_t)rep)) H.analysis_plan_ok = false;
+                    fed[o[j]][k]++;
+                }
+                if (!have || rep != ANALYSIS_SIGN_COEF[n]) H.analysis_plan_ok = false;
+                H.fl_sign[n] = rep;
+            }
+        }
+        for (int i = 0; i < 32; i++)
+            for (int k = 0; k < 64; k++)
+                if (fed[i][k] != (T.fl[i][k] != 0 ? 1 : 0)) H.analysis_plan_ok = false;
+    }
     for (int m = 0; m < 18; m++)
         for (int k = 0; k < 36; k++)
             T.cos_l[m][k] = (int32_t)(std::sin(0.087266462599717 * (k + 0.5)) *

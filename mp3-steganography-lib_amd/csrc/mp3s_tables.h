@@ -137,7 +137,9 @@ struct HostTables {
     int sfb_short_width[3][12];
     int slen[16][2];
     uint8_t in_h0[32];
-    bool analysis_plan_ok;   // the filter table built here repeats itself exactly where k_enc_analysis was compiled to share products (analysis_plan.h)
+    bool analysis_plan_ok;   // the filter table built here repeats itself exactly where k_enc_analysis was compiled to share products (analysis_plan.h),
+                             // and up to sign where its other matrixing shares them (analysis_sign_plan.h)
+    int32_t fl_sign[1056];   // dev.fl's coefficients in the order that matrixing consumes them (ANALYSIS_SIGN_STREAM; the device's c_fl_sign)
 };
 
 const HostTables &host_tables();   // built on first use, thread-safe
