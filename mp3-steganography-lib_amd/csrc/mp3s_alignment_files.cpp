@@ -105,7 +105,7 @@ int mp3s_pcm_align_dev(mp3s_ctx *c, const int16_t *d_pcm, int nch, const mp3s_pc
     const int rc = pcm_dev_host_block(c, [&]() {
         if (const int rc = align_inputs(h_runs, n_pairs, false, h_lags, c->h_pcm_align, &L)) return rc;
         o_geo = up16(L.bytes);
-        d_in = (uint8_t *)c->grab(9, o_geo + (size_t)n_pairs * sizeof(mp3s_pcm_pair));   // [tiles | given lags | geometry]
+        d_in = (uint8_t *)c->grab(kPoolInputs, o_geo + (size_t)n_pairs * sizeof(mp3s_pcm_pair));   // [tiles | given lags | geometry]
         if (!d_in) return fail(MP3S_E_NOMEM, "hipMalloc failed for %d workgroup entries", L.n_tiles);
         if (L.bytes) HIPCHK(hipMemcpyAsync(d_in, c->h_pcm_align.data(), L.bytes, hipMemcpyHostToDevice, c->stream));
         return (int)MP3S_OK;

@@ -581,7 +581,7 @@ int mp3s_select_dev(mp3s_ctx *c, const uint8_t *d_hide_bits, int32_t *d_cursor, 
         return fail(MP3S_E_ARG, "null pointer");
     if (n_segs <= 0 || n_entries <= 0 || max_reach <= 0 || max_reach > MP3S_SELECT_MAX_REACH) return fail(MP3S_E_ARG, "bad sizes");
     const RateVariantArgs va = {d_ent_unit, d_ent_cursor, n_entries, d_ixv, d_outv, d_env, (uint8_t *)(d_outv + n_entries)};
-    void *d_pairs = c->grab(29, (size_t)n_segs * max_reach * 8);
+    void *d_pairs = c->grab(kPoolSelectDev, (size_t)n_segs * max_reach * 8);
     if (!d_pairs) return fail(MP3S_E_NOMEM, "hipMalloc failed for the selection scratch");
     const int e = launch_select(c->stream, d_segs, d_spans, n_segs, max_reach, d_hide_bits, va, d_ix, d_en, d_out, d_cursor, d_pairs, &c->prof);
     if (e) return fail(MP3S_E_HIP, "select launch: %s", hipGetErrorString((hipError_t)e));
@@ -608,7 +608,7 @@ int mp3s_chain_resolve_dev(mp3s_ctx *c, mp3s_gr_out *d_gr, const mp3s_rate_frame
 {
     if (!c || !d_gr || !d_frames || !d_segs || !d_verdict || !d_seg_out) return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0 || n_segs <= 0) return fail(MP3S_E_ARG, "bad sizes");
-    void *d_agg = c->grab(30, chain_agg_bytes(n_frames));
+    void *d_agg = c->grab(kPoolChainDev, chain_agg_bytes(n_frames));
     if (!d_agg) return fail(MP3S_E_NOMEM, "hipMalloc failed for the chain scratch");
     const int e = launch_chain(c->stream, d_gr, d_frames, n_frames, d_segs, d_cursor_in, d_state_in, d_agg, d_verdict, d_seg_out, &c->prof);
     if (e) return fail(MP3S_E_HIP, "chain launch: %s", hipGetErrorString((hipError_t)e));
@@ -621,7 +621,7 @@ int mp3s_chain_redo_dev(mp3s_ctx *c, const int32_t *d_mdct, const mp3s_rate_fram
 {
     if (!c || !d_mdct || !d_gr || !d_frames || !d_segs || !d_verdict || !d_seg_out || !d_ix || !d_en) return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0 || n_segs <= 0 || n_hide < 0 || (n_hide > 0 && (!d_hide_bits || !d_cursor))) return fail(MP3S_E_ARG, "bad sizes");
-    void *d_agg = c->grab(30, chain_agg_bytes(n_frames));
+    void *d_agg = c->grab(kPoolChainDev, chain_agg_bytes(n_frames));
     if (!d_agg) return fail(MP3S_E_NOMEM, "hipMalloc failed for the chain scratch");
     const ChainRedoArgs redo = {d_mdct, d_hide_bits, n_hide, d_ix, d_en};
     const int e = launch_chain(c->stream, d_gr, d_frames, n_frames, d_segs, d_cursor, nullptr, d_agg, d_verdict, d_seg_out, &c->prof, &redo);

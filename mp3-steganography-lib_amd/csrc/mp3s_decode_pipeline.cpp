@@ -124,11 +124,10 @@ int decode_front(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
     const size_t blob_bytes = in_place ? m.scanned[idx[0]].blob.size() : c->h_blob.size();
     if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
     const int chunk = (int)std::min<long>(n, kDecodeChunk) + 1;
-    int slot = 0;
-    auto grab = [&](size_t bytes) { return c->grab(slot++, bytes); };
-    void *d_is = grab((size_t)n * 2304 * 2), *d_si = grab((size_t)n * 4 * sizeof(mp3s_granule_si)),
-         *d_hdr = grab((size_t)n * sizeof(mp3s_frame_hdr)), *d_pcm = grab((size_t)chunk * frame_bytes), *d_st = grab(((size_t)n + 1) * 4),
-         *d_blob = grab(blob_bytes), *d_side = grab((size_t)n * sizeof(mp3s_frame_side));
+    void *d_is = c->grab(kPoolIs0, (size_t)n * 2304 * 2), *d_si = c->grab(kPoolSi0, (size_t)n * 4 * sizeof(mp3s_granule_si)),
+         *d_hdr = c->grab(kPoolFrameHdr, (size_t)n * sizeof(mp3s_frame_hdr)), *d_pcm = c->grab(kPoolPcmChunk, (size_t)chunk * frame_bytes),
+         *d_st = c->grab(kPoolHufStatus, ((size_t)n + 1) * 4), *d_blob = c->grab(kPoolMainData, blob_bytes),
+         *d_side = c->grab(kPoolSideInfo, (size_t)n * sizeof(mp3s_frame_side));
     if (!d_is || !d_si || !d_hdr || !d_pcm || !d_st || !d_blob || !d_side)
         return fail(MP3S_E_NOMEM, "hipMalloc failed for a %ld-frame decode", n);
     F.d_is = d_is; F.d_si = d_si; F.d_hdr = d_hdr; F.d_pcm = d_pcm; F.d_st = d_st; F.d_blob = d_blob; F.d_side = d_side;

@@ -59,7 +59,7 @@ int mp3s_pcm_diff_dev(mp3s_ctx *c, const int16_t *d_pcm, int nch, const mp3s_pcm
     const int rc = pcm_dev_host_block(c, [&]() {
         tiles.clear();
         if (!pcm_diff_tiles(h_pairs, n_pairs, tiles)) return fail(MP3S_E_ARG, "too many frames to compare");
-        d_tiles = c->grab(9, tiles.size() * sizeof(PcmTile));
+        d_tiles = c->grab(kPoolInputs, tiles.size() * sizeof(PcmTile));
         if (!d_tiles) return fail(MP3S_E_NOMEM, "hipMalloc failed for %zu workgroup entries", tiles.size());
         if (!tiles.empty()) HIPCHK(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(PcmTile), hipMemcpyHostToDevice, c->stream));
         return (int)MP3S_OK;

@@ -83,8 +83,8 @@ static int resample_taps_dev(mp3s_ctx *c, int L, int M, const uint32_t **d_out)
 // the files `idx` to the device: their images up, the batch's kernels (launch_wav_batch) queued on the context's stream -> *d_pcm_out =
 // [b.n_all][1152][2] int16 in the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is
 // waited for; the batch's records and the callers' bytes are read by copies in flight until the stream is synchronised.
-// Buffers: image and records in pool slot 27 (the records behind the image and its slack), PCM in 7, the resampler's scratch in 28,
-// the short files' staging in h_blob.
+// Buffers: image and records in kPoolWavImage (the records behind the image and its slack), PCM in kPoolPcm0, the resampler's scratch in
+// kPoolResampleRows, the short files' staging in h_blob.
 int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, WavBatch &b, void **d_pcm_out)
 {
     segs.assign(idx.size(), EncSeg());
@@ -99,9 +99,9 @@ int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<i
         if (rc) return rc;
     }
     b.place_records(b.img + kWavSlack);
-    uint8_t *d_image = (uint8_t *)c->grab(27, b.rec_end);
-    void *d_pcm = c->grab(7, (size_t)b.n_all * 4608);
-    void *d_rows = b.rruns.empty() ? nullptr : c->grab(28, (size_t)b.s_all * 4608);
+    uint8_t *d_image = (uint8_t *)c->grab(kPoolWavImage, b.rec_end);
+    void *d_pcm = c->grab(kPoolPcm0, (size_t)b.n_all * 4608);
+    void *d_rows = b.rruns.empty() ? nullptr : c->grab(kPoolResampleRows, (size_t)b.s_all * 4608);
     if (!d_image || !d_pcm || (!b.rruns.empty() && !d_rows)) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of WAV input", (long long)b.n_all);
     std::vector<Upload> ups;
     plan_uploads(b.files, [&](size_t extent) { if (c->h_blob.size() < extent) c->h_blob.resize(extent); return c->h_blob.data(); }, ups);

@@ -93,10 +93,24 @@ int enc_layout(std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncL
 bool enc_variant_buffers(mp3s_ctx *c, const EncLayout &L, EncDev &d)
 {
     if (L.n_entries <= 0) { d.d_ixv = nullptr; d.d_outv = nullptr; d.d_env = nullptr; return true; }
-    d.d_ixv = (int16_t *)c->grab(kSlotVariants + 1, (size_t)L.n_entries * 1152);
-    d.d_outv = (mp3s_gr_out *)c->grab(kSlotVariants + 2, variant_out_bytes(L.n_entries));
-    d.d_env = (int32_t *)c->grab(kSlotVariants + 3, (size_t)L.n_entries * 88);
+    d.d_ixv = (int16_t *)c->grab(kPoolVarIx, (size_t)L.n_entries * 1152);
+    d.d_outv = (mp3s_gr_out *)c->grab(kPoolVarOut, variant_out_bytes(L.n_entries));
+    d.d_env = (int32_t *)c->grab(kPoolVarEnergy, (size_t)L.n_entries * 88);
     return d.d_ixv && d.d_outv && d.d_env;
+}
+
+// d = the buffers of encode_batch and capacity_batch from the context's pool, asked for in this order up to the first that fails (false): with
+// want_pcm room for the host's PCM (without: d_pcm is the caller's), with want_mp3 the packed bytes and the scalefactor selection, small_room
+// bytes of small results.  The variant buffers are the caller's to ask for, behind its uploads (enc_variant_buffers).
+static bool enc_pool_buffers(mp3s_ctx *c, const EncLayout &L, bool want_pcm, bool want_mp3, size_t small_room, EncDev &d)
+{
+    const size_t n = (size_t)L.n, n_all = (size_t)L.n_all, units = (size_t)L.units;
+    d = EncDev();
+    return (!want_pcm || (d.d_pcm = (const int16_t *)c->grab(kPoolPcmUp, n_all * 2304 * 2))) && (d.d_in = (const uint8_t *)c->grab(kPoolInputs, L.bytes)) && (d.d_mdct_all = (int32_t *)c->grab(kPoolMdct, n_all * 2304 * 4)) &&
+           (d.d_ix = (int16_t *)c->grab(kPoolIx, n * 2304 * 2)) && (d.d_out = (mp3s_gr_out *)c->grab(kPoolGrOut, units * sizeof(mp3s_gr_out))) &&
+           (d.d_en = (int32_t *)c->grab(kPoolEnergy, units * 22 * 4)) && (d.d_agg = c->grab(kPoolChainAgg, chain_agg_bytes(L.n))) &&
+           (!want_mp3 || ((d.d_mp3 = (uint8_t *)c->grab(kPoolMp3, L.mp3_bytes + 16)) && (d.d_sc = (int32_t *)c->grab(kPoolScfsi, n * 8 * 4)))) &&
+           (d.d_small = (int32_t *)c->grab(kPoolSmall, small_room));
 }
 
 int enc_fill(std::vector<EncSeg> &segs, EncLayout &L, uint8_t *dst)
@@ -276,7 +290,7 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     const mp3s_rate_frame *d_rf = (const mp3s_rate_frame *)(d_in + L.o_rf);
     const uint8_t *d_hide = d_in + L.o_hide;
     const size_t total = segs.back().mp3_off + segs.back().mp3_len;
-    void *d_redo = c->grab(kSlotRedo, (size_t)units * 24);
+    void *d_redo = c->grab(kPoolRedo, (size_t)units * 24);
     if (!d_redo || !b->big[0].reserve(L.mp3_bytes)) return fail(MP3S_E_NOMEM, "memory for resolving %d units", units);
     b->mp3 = b->big[0].data();
     int rc = MP3S_OK;
@@ -415,10 +429,8 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
             }
             if (spans.empty()) break;
             const size_t ne = ent_unit.size();
-            int slot = kSlotVariants;
-            auto alloc = [&](void **p, size_t bytes) { *p = c->grab(slot++, bytes); return *p != nullptr; };
-            if (!alloc(&d_ent, ne * 24) || !alloc(&d_ixv, ne * 1152) || !alloc(&d_outv, ne * sizeof(mp3s_gr_out)) ||
-                !alloc(&d_env, ne * 88) || !alloc(&d_pairs, ne))   // at most one pair per unit = ne / 8 pairs of 8 bytes
+            if (!(d_ent = c->grab(kPoolVarEntries, ne * 24)) || !(d_ixv = c->grab(kPoolVarIx, ne * 1152)) || !(d_outv = c->grab(kPoolVarOut, ne * sizeof(mp3s_gr_out))) ||
+                !(d_env = c->grab(kPoolVarEnergy, ne * 88)) || !(d_pairs = c->grab(kPoolVarPairs, ne)))   // at most one pair per unit = ne / 8 pairs of 8 bytes
                 rc = fail(MP3S_E_NOMEM, "hipMalloc failed for the message variants");
             mark("variant entries listed");
             // (d_pairs holds the table counts first, the chosen pairs afterwards: ne bytes either way)
@@ -517,20 +529,13 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     in.resize(L.bytes);
     rc = enc_fill(segs, L, in.data());
     if (rc) return rc;
-    void *d_pcm = nullptr, *d_in = nullptr, *d_mdct_all = nullptr, *d_ix = nullptr, *d_out = nullptr, *d_en = nullptr,
-         *d_agg = nullptr, *d_mp3 = nullptr, *d_sc = nullptr, *d_small = nullptr;
     auto cleanup = [&]() { hipStreamSynchronize(c->stream); };   // the buffers stay in the context's pool
-    int slot = 8;
-    auto alloc = [&](void **p, size_t bytes) { *p = c->grab(slot++, bytes); return *p != nullptr; };
-    if (pcm_dev) { d_pcm = const_cast<int16_t *>(pcm_dev); slot++; }
-    else if (!alloc(&d_pcm, (size_t)n_all * 2304 * 2)) d_pcm = nullptr;
-    if (!d_pcm || !alloc(&d_in, L.bytes) || !alloc(&d_mdct_all, (size_t)n_all * 2304 * 4) || (slot++ /* kSlotRedo */, false) ||
-        !alloc(&d_ix, (size_t)n * 2304 * 2) || !alloc(&d_out, (size_t)units * sizeof(mp3s_gr_out)) || !alloc(&d_en, (size_t)units * 22 * 4) ||
-        !alloc(&d_agg, chain_agg_bytes(n)) || !alloc(&d_mp3, L.mp3_bytes + 16) || !alloc(&d_sc, (size_t)n * 8 * 4) ||
-        !alloc(&d_small, small_bytes(L.n_segs))) {
+    EncDev dev;
+    if (!enc_pool_buffers(c, L, !pcm_dev, true, small_bytes(L.n_segs), dev)) {
         cleanup();
         return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame encode", n);
     }
+    if (pcm_dev) dev.d_pcm = pcm_dev;
     const size_t total = segs.back().mp3_off + segs.back().mp3_len;
     if (!b->big[0].reserve(L.mp3_bytes) || !b->big[2].reserve(small_bytes(L.n_segs)) ||
         (want_gr && !b->big[1].reserve((size_t)units * sizeof(mp3s_gr_out)))) {
@@ -543,22 +548,18 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     if (want_gr) b->scfsi.assign((size_t)n * 8, 0);
     // ---- one pass, nothing waited for in between: inputs up, transforms, rate loop on the guessed cursors, the chain
     //      check on the device, bit packing, results down.  The verdict says whether the guesses held.
-    if (!pcm_dev && hipMemcpyAsync(d_pcm, pcm, (size_t)n_all * 2304 * 2, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "PCM upload failed");
-    if (!rc && hipMemcpyAsync(d_in, in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
-    EncDev dev;
-    dev.d_pcm = (const int16_t *)d_pcm; dev.d_in = (const uint8_t *)d_in; dev.d_mdct_all = (int32_t *)d_mdct_all; dev.d_ix = (int16_t *)d_ix;
-    dev.d_out = (mp3s_gr_out *)d_out; dev.d_en = (int32_t *)d_en; dev.d_agg = d_agg; dev.d_mp3 = (uint8_t *)d_mp3; dev.d_sc = (int32_t *)d_sc;
-    dev.d_small = (int32_t *)d_small;
+    if (!pcm_dev && hipMemcpyAsync(const_cast<int16_t *>(dev.d_pcm), pcm, (size_t)n_all * 2304 * 2, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "PCM upload failed");
+    if (!rc && hipMemcpyAsync(const_cast<uint8_t *>(dev.d_in), in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
     if (!rc && !enc_variant_buffers(c, L, dev)) rc = fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
     if (!rc) rc = enc_issue(c, L, dev);
     auto down = [&](void *dst, const void *src, size_t bytes) {
         if (!rc && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
     };
-    down(small, d_small, small_bytes(L.n_segs));
-    down(b->mp3, d_mp3, total);
+    down(small, dev.d_small, small_bytes(L.n_segs));
+    down(b->mp3, dev.d_mp3, total);
     if (want_gr) {
-        down(b->big[1].data(), d_out, (size_t)units * sizeof(mp3s_gr_out));
-        down(b->scfsi.data(), d_sc, (size_t)n * 8 * 4);
+        down(b->big[1].data(), dev.d_out, (size_t)units * sizeof(mp3s_gr_out));
+        down(b->scfsi.data(), dev.d_sc, (size_t)n * 8 * 4);
     }
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "sync failed");
     if (rc) { cleanup(); return rc; }
@@ -577,14 +578,13 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     }
     // ---- the guesses did not hold: resolve the chains on the host, as round 1 did
     if (trace_on()) fprintf(stderr, "mp3s: encode of %d frames: %d units still to redo behind the device's re-runs (step range %d), %d variant entries, redo launches %d -> the host resolves\n", n, small[0], small[1], L.n_entries, (int)L.redo);
-    EncDev devr = dev;
-    rc = enc_resolve(c, L, segs, in.data(), devr, b, want_gr, passes_out);
+    rc = enc_resolve(c, L, segs, in.data(), dev, b, want_gr, passes_out);
     cleanup();
     return rc;
 }
 
-// encode_batch without its tail (mp3s_internal.h): same pool slots, minus the MP3 bytes and the scalefactor selection (16, 17); the small
-// block (18) holds [verdict, chain ends | capacity records | profile] so that one copy brings all of it down.
+// encode_batch without its tail (mp3s_internal.h): the same pool buffers, minus kPoolMp3 and kPoolScfsi; the small block (kPoolSmall)
+// holds [verdict, chain ends | capacity records | profile] so that one copy brings all of it down.
 int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, bool want_profile,
                    mp3s_buf *b, CapacityBatch *out)
 {
@@ -592,7 +592,7 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
     EncLayout L;
     int rc = enc_layout(segs, samplerate, bitrate_kbps, L, c->opt[MP3S_OPT_SELECT] != 0);
     if (rc) return rc;
-    const int n = L.n, units = L.units, n_all = L.n_all;
+    const int n = L.n;
     HIPCHK(hipSetDevice(c->device));
     std::vector<uint8_t> &in = c->h_in;
     in.resize(L.bytes);
@@ -600,11 +600,9 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
     if (rc) return rc;
     const size_t o_cap = up16(small_bytes(L.n_segs)), o_prof = o_cap + (size_t)L.n_segs * sizeof(mp3s_capacity_seg),
                  down_bytes = o_prof + (want_profile ? (size_t)n * 4 : 0);
-    void *d_in = c->grab(9, L.bytes), *d_mdct_all = c->grab(10, (size_t)n_all * 2304 * 4), *d_ix = c->grab(12, (size_t)n * 2304 * 2),
-         *d_out = c->grab(13, (size_t)units * sizeof(mp3s_gr_out)), *d_en = c->grab(14, (size_t)units * 22 * 4),
-         *d_agg = c->grab(15, chain_agg_bytes(n)), *d_small = c->grab(18, down_bytes);
     auto cleanup = [&]() { hipStreamSynchronize(c->stream); };   // the buffers stay in the context's pool
-    if (!d_in || !d_mdct_all || !d_ix || !d_out || !d_en || !d_agg || !d_small) {
+    EncDev dev;
+    if (!enc_pool_buffers(c, L, false, false, down_bytes, dev)) {
         cleanup();
         return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame encode", n);
     }
@@ -615,15 +613,13 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
     uint8_t *const small8 = b->big[2].data();
     const int32_t *const small = (const int32_t *)small8;
     const mp3s_chain_seg_out *const seg_out = (const mp3s_chain_seg_out *)(small8 + kSmallHead);
-    if (hipMemcpyAsync(d_in, in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
-    EncDev dev;
-    dev.d_pcm = pcm_dev; dev.d_in = (const uint8_t *)d_in; dev.d_mdct_all = (int32_t *)d_mdct_all; dev.d_ix = (int16_t *)d_ix;
-    dev.d_out = (mp3s_gr_out *)d_out; dev.d_en = (int32_t *)d_en; dev.d_agg = d_agg; dev.d_small = (int32_t *)d_small;
-    dev.d_cap = (mp3s_capacity_seg *)((uint8_t *)d_small + o_cap);
-    dev.d_profile = want_profile ? (uint32_t *)((uint8_t *)d_small + o_prof) : nullptr;
+    if (hipMemcpyAsync(const_cast<uint8_t *>(dev.d_in), in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
+    dev.d_pcm = pcm_dev;
+    dev.d_cap = (mp3s_capacity_seg *)((uint8_t *)dev.d_small + o_cap);
+    dev.d_profile = want_profile ? (uint32_t *)((uint8_t *)dev.d_small + o_prof) : nullptr;
     if (!rc && !enc_variant_buffers(c, L, dev)) rc = fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
     if (!rc) rc = enc_issue(c, L, dev);
-    if (!rc && hipMemcpyAsync(small8, d_small, down_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
+    if (!rc && hipMemcpyAsync(small8, dev.d_small, down_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "sync failed");
     if (rc) { cleanup(); return rc; }
     out->down_bytes = down_bytes;
@@ -767,7 +763,7 @@ extern "C++" int reencode_decode(mp3s_ctx *c, mp3s_multi &m, const std::vector<i
         rows_frames += segs[k].n_frames;
     }
     if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
-    void *d_keep = c->grab(7, (size_t)rows_frames * 2304 * 2);
+    void *d_keep = c->grab(kPoolPcm0, (size_t)rows_frames * 2304 * 2);
     if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
     const int rc = decode_group(c, m, idx, 2, MP3S_PCM_I16, d_keep);
     if (rc) return rc;
@@ -888,7 +884,7 @@ int mp3s_reencode_block_indexed(mp3s_ctx *c, const uint8_t *mp3, size_t len, con
     if (!with_dup) p.dup_last_frame = 0;
     const int64_t rows_frames = (w1 - w0) + (with_dup ? 1 : 0);
     if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
-    void *d_keep = c->grab(7, (size_t)rows_frames * 2304 * 2);
+    void *d_keep = c->grab(kPoolPcm0, (size_t)rows_frames * 2304 * 2);
     if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
     rc = decode_group(c, m, std::vector<int>{0}, 2, MP3S_PCM_I16, d_keep);
     if (rc) return rc;

@@ -36,6 +36,38 @@ using namespace mp3s;
         if (e_ != hipSuccess) return fail(MP3S_E_HIP, "%s: %s", #call, hipGetErrorString(e_));       \
     } while (0)
 
+// The device buffers a context keeps between calls (mp3s_ctx::grab), one name per buffer.  A buffer with several users is shared on purpose;
+// what keeps them apart is said here, and a new user says it here too.
+//   One call at a time per context covers most of it: a list call, a one-file call or an encode has synchronised the context's stream when
+//   it returns, and within a call the users below follow each other on that stream.
+//   A pipe owns its context while it exists (mp3s.h): no other call runs beside its jobs.  They alternate between two sets of {Is, Si, Pcm}
+//   -- job k + 1 fills the other set while job k's is read -- and a set is written again only behind the events of the job that had it
+//   (e_dec, e_enc, e_down: pipe_jobs.cpp).  ChainAgg and the Var* buffers are one per context: the jobs' rate loops, selections and chain
+//   checks follow each other on the compute and tail streams (tail_from, rate_after, ev_sel).
+//   The _dev calls (test aids on the caller's device arrays, nothing waited for) queue on the context's stream: what a later call writes
+//   to a buffer they share lies behind their reads, and a regrow synchronises that stream first.  SelectDev and ChainDev are theirs alone.
+enum PoolSlot : int {
+    kPoolIs0, kPoolSi0,     // Huffman output of a decode batch (decode_front) or of set 0 of a pipe: samples [frames][2][2][576] int16, granule records
+    kPoolFrameHdr, kPoolPcmChunk, kPoolHufStatus, kPoolMainData, kPoolSideInfo,   // decode_front: headers, a chunk of PCM on its way down, Huffman status, main data, side records
+    kPoolPcm0,              // int16 PCM that stays on the device: reencode_decode, the pair calls, wav_to_device, set 0 of a pipe; the table audit, which decodes no PCM, keeps its unit records here
+    kPoolPcmUp,             // the PCM an encode brings from the host (encode_batch without pcm_dev)
+    kPoolInputs,            // the host-made input block of the call: the encoder's (EncLayout), the pair calls', the audit's stream table, the workgroup tables of mp3s_pcm_diff_dev / mp3s_pcm_align_dev
+    kPoolMdct,              // encode_batch, capacity_batch: MDCT lines [n_all][2][2][576]
+    kPoolRedo,              // enc_resolve: entries of the exact re-runs
+    kPoolIx, kPoolGrOut, kPoolEnergy,   // encode_batch, capacity_batch: quantised lines, GrInfo records, band energies
+    kPoolChainAgg,          // chain_agg_bytes(n) of the chain check: encode_batch, capacity_batch, every job of a pipe
+    kPoolMp3, kPoolScfsi,   // encode_batch: the packed bytes, the scalefactor selection (capacity_batch packs nothing and takes neither)
+    kPoolSmall,             // the small results one copy brings down: of an encode (small_bytes; capacity_batch: + capacity records and profile), of the pair calls, of the audit
+    kPoolVarEntries, kPoolVarIx, kPoolVarOut, kPoolVarEnergy, kPoolVarPairs,   // message variants: enc_resolve's launches take all five, the entries inside the first rate-loop launch
+                            // (enc_variant_buffers) Ix, Out and Energy -- their selection is through before a resolve begins
+    kPoolIs1, kPoolSi1, kPoolPcm1,      // set 1 of a pipe
+    kPoolWavImage, kPoolResampleRows,   // wav_to_device: the files' bytes with the kernels' records behind them; PCM at the source rate for the resampler
+    kPoolSelectDev, kPoolChainDev,      // scratch of mp3s_select_dev; of mp3s_chain_resolve_dev and mp3s_chain_redo_dev
+    kPoolReveal,            // mp3s_reveal_messages: a batch's [files | records | packed bits out]
+    kPoolSlotCount
+};
+constexpr PoolSlot kPoolIs[2] = {kPoolIs0, kPoolIs1}, kPoolSi[2] = {kPoolSi0, kPoolSi1}, kPoolPcm[2] = {kPoolPcm0, kPoolPcm1};   // by Job::set
+
 struct mp3s_pipe;
 struct mp3s_ctx {
     int device = 0;
@@ -62,8 +94,9 @@ struct mp3s_ctx {
     std::vector<ResampleTaps> res_taps;
     void *pool[kPoolSlots] = {nullptr};
     size_t pool_bytes[kPoolSlots] = {0};
-    void *grab(int slot, size_t bytes)
+    void *grab(PoolSlot slot, size_t bytes)
     {
+        if (slot < 0 || slot >= kPoolSlots) return nullptr;   // (callers answer MP3S_E_NOMEM)
         if (bytes < 16) bytes = 16;
         if (pool_bytes[slot] >= bytes) return pool[slot];
         if (pool[slot]) { hipStreamSynchronize(stream); hipFree(pool[slot]); pool[slot] = nullptr; pool_bytes[slot] = 0; }
@@ -113,6 +146,7 @@ struct mp3s_ctx {
         return 0;
     }
 };
+static_assert(kPoolSlotCount <= mp3s_ctx::kPoolSlots, "every PoolSlot needs a place in mp3s_ctx::pool");
 
 // Page-locked host memory for large results (decoded PCM): the device writes it at PCIe speed, no bounce buffer, no
 // page faults.  Pinning costs more than the copy it saves, so blocks are kept and reused: process-wide, because a
@@ -365,7 +399,7 @@ int decode_transform_chunk(mp3s_ctx *c, const int16_t *d_is, const mp3s_granule_
 // channel count) laid end to end -- frame headers into the context's h_hdr, side records, main data --, uploaded, launch_huffman, the
 // frames the kernel flags decided by the host parser, host-parsed streams placed.  Afterwards d_is / d_si hold every frame's samples
 // and granule records; d_side holds the side records of the device-decoded streams and zeros for streams that were host-parsed when
-// the call began.  Pool slots 0 .. 6; d_pcm gets room for a chunk of frames of frame_bytes each (0: none is wanted).  n == 0: nothing
+// the call began.  Pool buffers kPoolIs0 .. kPoolSideInfo; d_pcm gets room for a chunk of frames of frame_bytes each (0: none is wanted).  n == 0: nothing
 // was done.  d_is == nullptr behind a failure: it happened in front of the allocations.
 struct DecodeFront {
     long n = 0;                       // frames of the batch
@@ -386,7 +420,7 @@ void distortion_from_record(const mp3s_pcm_pair_diff &r, const ParsedStream &a, 
 // The pairs `idx` (file idx[k] against file n_pairs + idx[k] of m, one channel count, every stream with a frame) as one batch.
 //   lay : the streams A, B of pair idx[0], A, B of pair idx[1], ... and where each lies in the PCM buffer (decode_group: frames back to
 //         back, a repeated last frame behind its stream); max_frames: what the caller's kernels can address.
-//   run : pool slots 7 (the PCM), 9 (in_bytes of `in`, made by the caller from the layout: the context's h_in) and 18 (res_bytes), the
+//   run : kPoolPcm0 (the PCM), kPoolInputs (in_bytes of `in`, made by the caller from the layout: the context's h_in) and kPoolSmall (res_bytes), the
 //         decode, a check that it left the layout's frame counts, the upload, launch(d_pcm, d_in, d_res) -> code (its own text),
 //         down_bytes of the results into part->big[2] = res, and the stream synchronised whatever happened.
 struct PcmPairBatch {
@@ -485,9 +519,17 @@ struct EncDev {
     // there (and the per-frame profile, when d_profile is given) and the bit packer is not launched: d_mp3, d_sc and the pack fields are unused
     mp3s_capacity_seg *d_cap = nullptr; uint32_t *d_profile = nullptr;
 };
+// d_mdct_all | d_ix | d_out | d_en (a multiple of 256 bytes) | d_sc of a batch in ONE allocation (a slot of a pipe): where each begins, the end
+struct EncScratch { size_t o_mdct, o_ix, o_out, o_en, o_sc, bytes; };
+inline EncScratch enc_scratch_layout(const EncLayout &L)
+{
+    const size_t o_ix = (size_t)L.n_all * 2304 * 4, o_out = o_ix + (size_t)L.n * 2304 * 2, o_en = o_out + (size_t)L.units * sizeof(mp3s_gr_out),
+                 o_sc = o_en + (((size_t)L.units * 22 * 4 + 255) & ~(size_t)255);
+    return {0, o_ix, o_out, o_en, o_sc, o_sc + (size_t)L.n * 8 * 4};
+}
 // the entries of a stream's first `reach` units (variant-major, the two "bits left" rows from MP3S_SELECT_TAIL_FIRST on: mp3s.h)
 void select_entries(int first_unit, int reach, int first_entry, int hide_end, int64_t bits_left, int32_t *ent_unit, int32_t *ent_cursor);
-// device buffers for L.n_entries variant entries from the context's pool (slots of the host's variants, free at that point)
+// device buffers for L.n_entries variant entries from the context's pool (kPoolVarIx, kPoolVarOut, kPoolVarEnergy: the host's variants', free at that point)
 bool enc_variant_buffers(mp3s_ctx *c, const EncLayout &L, EncDev &d);
 // transforms -> rate loop on the guessed cursors -> chain check -> bit packing (with d.d_cap: k_capacity in its place), all on c->stream,
 // nothing waited for.  The packed bytes (the capacity records) are final iff verdict[0] == 0 and verdict[1] == 0 (d_small[0], d_small[1]).
@@ -495,8 +537,7 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
               hipEvent_t tail_from = nullptr, hipEvent_t rate_after = nullptr /* the rate loop waits for this event (the previous job's tail) */,
               hipEvent_t pcm_read = nullptr /* recorded behind the encode transforms: the PCM they read may be overwritten */);
 // verdict != 0: the host resolves the chains on the first pass's device buffers (walk, message variants, exact re-runs,
-// packing again); `in` = the host copy of the block.  Pool slots of its own: the entries of the exact re-runs, the variants.
-constexpr int kSlotRedo = 11, kSlotVariants = 19;
+// packing again); `in` = the host copy of the block.  Pool buffers of its own: kPoolRedo, kPoolVarEntries .. kPoolVarPairs.
 int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, const uint8_t *in, const EncDev &d, mp3s_buf *b, bool have_gr,
                 int *passes_out);
 int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps,
@@ -515,7 +556,7 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
 int reencode_check(const ParsedStream &p, int *kbps_out);
 // the front half of a re-encode batch: the streams `idx` of m (stereo, one sampling rate and bitrate) become segs (bits[i] = framed
 // message of file i, empty: nothing hidden; guess keeps the table counts segs point into) and are decoded on the device into
-// *d_keep_out, int16 PCM that stays in HBM (pool slot 7), *rows_frames frames back to back
+// *d_keep_out, int16 PCM that stays in HBM (kPoolPcm0), *rows_frames frames back to back
 int reencode_decode(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, const std::vector<std::vector<uint8_t>> &bits,
                     std::vector<EncSeg> &segs, std::vector<std::vector<uint8_t>> &guess, void **d_keep_out, int64_t *rows_frames);
 // non-zero table indices per unit of a scanned stream, in the encoder's unit order (frame, channel, granule): see

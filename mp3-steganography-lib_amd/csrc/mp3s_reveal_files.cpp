@@ -70,7 +70,7 @@ int reveal_launch(mp3s_ctx *c, const uint8_t *const *mp3s, const size_t *lens, s
     }
     files.push_back({o_refs, rec.data(), rec.size()});
     HIPCHK(hipSetDevice(c->device));
-    uint8_t *d_in = (uint8_t *)c->grab(31, in_end + out_bytes);
+    uint8_t *d_in = (uint8_t *)c->grab(kPoolReveal, in_end + out_bytes);
     PinnedBlock down;
     if (!d_in || !down.reserve(out_bytes)) return fail(MP3S_E_NOMEM, "no memory for a reveal batch of %zu bytes", in_end + out_bytes);
     uint8_t *d_out = d_in + in_end;

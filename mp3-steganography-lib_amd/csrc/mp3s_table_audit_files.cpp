@@ -6,8 +6,6 @@
 
 namespace {
 
-constexpr int kSlotUnits = 7, kSlotSegs = 9, kSlotRes = 18;   // (the PCM, the inputs and the results of the pair calls: free here)
-
 void no_frames(const ParsedStream &p, mp3s_table_audit *out)
 {
     std::memset(out, 0, sizeof *out);
@@ -39,8 +37,9 @@ int audit_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nch
     std::vector<mp3s_table_audit_seg> segs(ns);
     for (size_t k = 0; k < ns; k++) segs[k] = {(int32_t)F.first_of[k], (int32_t)m.parsed[idx[k]].n_frames};
     const size_t o_prof = up16(ns * sizeof(mp3s_table_audit)), res_bytes = o_prof + (want_profile ? (size_t)n * 4 : 0);
-    void *d_units = c->grab(kSlotUnits, (size_t)n * 4 * sizeof(mp3s_table_audit_unit)), *d_segs = c->grab(kSlotSegs, ns * sizeof(mp3s_table_audit_seg)),
-         *d_res = c->grab(kSlotRes, res_bytes);
+    // (the unit records lie where other calls keep PCM: the audit decodes none -- PoolSlot, mp3s_internal.h)
+    void *d_units = c->grab(kPoolPcm0, (size_t)n * 4 * sizeof(mp3s_table_audit_unit)), *d_segs = c->grab(kPoolInputs, ns * sizeof(mp3s_table_audit_seg)),
+         *d_res = c->grab(kPoolSmall, res_bytes);
     if (!d_units || !d_segs || !d_res) return fail(MP3S_E_NOMEM, "hipMalloc failed for the audit of %ld frames", n);
     std::unique_ptr<mp3s_buf> part(new mp3s_buf());
     if (!part->big[2].reserve(res_bytes)) return fail(MP3S_E_NOMEM, "hipHostMalloc failed for %zu bytes of audit results", res_bytes);
@@ -78,7 +77,7 @@ int mp3s_table_audit_dev(mp3s_ctx *c, const int16_t *d_is, const mp3s_frame_side
     if (nch != 1 && nch != 2) return fail(MP3S_E_ARG, "nch=%d", nch);
     if (((uintptr_t)d_is & 3) || ((uintptr_t)d_units & 15)) return fail(MP3S_E_ARG, "d_is must be 4-byte, d_units 16-byte aligned");
     if (!d_units) {
-        d_units = (mp3s_table_audit_unit *)c->grab(kSlotUnits, (size_t)n_frames * 4 * sizeof(mp3s_table_audit_unit));
+        d_units = (mp3s_table_audit_unit *)c->grab(kPoolPcm0, (size_t)n_frames * 4 * sizeof(mp3s_table_audit_unit));
         if (!d_units) return fail(MP3S_E_NOMEM, "hipMalloc failed for the unit records of %d frames", n_frames);
     }
     const int e = launch_table_audit(c->stream, d_is, d_side, n_frames, nch, d_segs, n_segs, d_units, d_out, d_profile);

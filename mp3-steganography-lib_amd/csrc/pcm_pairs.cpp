@@ -42,8 +42,8 @@ int PcmPairBatch::run(mp3s_ctx *c, mp3s_multi &m, int nch, const uint8_t *in, si
                       const std::function<int(const int16_t *d_pcm, const uint8_t *d_in, uint8_t *d_res)> &launch)
 {
     if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
-    void *d_keep = c->grab(7, (size_t)rows_frames * 1152 * nch * 2);
-    uint8_t *d_in = (uint8_t *)c->grab(9, in_bytes), *d_res = (uint8_t *)c->grab(18, res_bytes);
+    void *d_keep = c->grab(kPoolPcm0, (size_t)rows_frames * 1152 * nch * 2);
+    uint8_t *d_in = (uint8_t *)c->grab(kPoolInputs, in_bytes), *d_res = (uint8_t *)c->grab(kPoolSmall, res_bytes);
     if (!d_keep || !d_in || !d_res) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
     part.reset(new mp3s_buf());
     if (!part->big[2].reserve(down_bytes)) return fail(MP3S_E_NOMEM, "host memory for %zu bytes of records", down_bytes);

@@ -400,6 +400,43 @@ bool prepare_fast(mp3s_pipe *P, Job &j, Slot &s, ParsedStream &p, size_t *blob_l
     return true;
 }
 
+// What the stages of a hide, clear or decode job share: its frames, the format of its PCM, its small results and the buffers of its set
+// (Job::set) in the context's pool.  Every stage asks again: behind the first the buffers have their size and come back as they are.
+struct JobView { int n, nch, out_format; size_t esz, frame_elems; int32_t *d_small; void *d_is, *d_si, *d_keep; };
+int job_view(mp3s_ctx *c, const Job &j, const Slot &s, JobView &v)
+{
+    v.n = j.n_total; v.nch = j.decode ? j.nch : 2; v.out_format = j.ck.on && j.decode ? j.ck.out_format : MP3S_PCM_I16;
+    v.esz = pcm_elem(v.out_format); v.frame_elems = (size_t)1152 * v.nch;
+    // a walked job brings its block, status words zeroed, with its inputs (the kernels OR into them directly); a scanned one uses the
+    // slot's, written by the last workgroup of each kernel
+    v.d_small = j.walked ? (int32_t *)(s.d_stage + j.o_small) : s.d_small;
+    const size_t ng = (size_t)std::max(v.n, j.grab_frames);
+    v.d_is = c->grab(kPoolIs[j.set], ng * 2304 * 2); v.d_si = c->grab(kPoolSi[j.set], ng * 4 * sizeof(mp3s_granule_si));
+    v.d_keep = c->grab(kPoolPcm[j.set], ng * v.frame_elems * v.esz);
+    return v.d_is && v.d_si && v.d_keep ? MP3S_OK : fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", v.n);
+}
+
+// The encode side's buffers of a hide or encode job -> j.dev: PCM at d_pcm, the inputs in the stage, the slot's scratch grown to the job
+// and carved up (enc_scratch_layout), its MP3 buffer, the context's chain aggregate and variant buffers.  The rest is the caller's.
+int slot_enc_dev(mp3s_ctx *c, Job &j, Slot &s, const void *d_pcm)
+{
+    const EncLayout &L = j.L;
+    const EncScratch o = enc_scratch_layout(L);
+    if (o.bytes > s.enc_cap) {   // (hipFree waits for the device; only while the slot is growing to its job size)
+        if (s.d_enc) (void)hipFree(s.d_enc);
+        s.d_enc = nullptr; s.enc_cap = 0;
+        if (hipMalloc((void **)&s.d_enc, o.bytes + o.bytes / 8) != hipSuccess) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", j.n_total);
+        s.enc_cap = o.bytes + o.bytes / 8;
+    }
+    void *d_agg = c->grab(kPoolChainAgg, chain_agg_bytes(L.n));
+    if (!d_agg) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", j.n_total);
+    EncDev &dev = j.dev = EncDev();
+    dev.d_agg = d_agg; dev.d_pcm = (const int16_t *)d_pcm; dev.d_in = s.d_stage + j.o_encblk; dev.d_mp3 = s.d_mp3;
+    dev.d_mdct_all = (int32_t *)(s.d_enc + o.o_mdct); dev.d_ix = (int16_t *)(s.d_enc + o.o_ix); dev.d_out = (mp3s_gr_out *)(s.d_enc + o.o_out);
+    dev.d_en = (int32_t *)(s.d_enc + o.o_en); dev.d_sc = (int32_t *)(s.d_enc + o.o_sc);
+    return enc_variant_buffers(c, L, dev) ? MP3S_OK : fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
+}
+
 }  // namespace
 
 // everything a fast job does on the device, queued on the streams; nothing is waited for
@@ -411,14 +448,10 @@ int issue_front(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23, boo
     const double t_issue0 = trace_on() ? now_ms() : 0;
     const EncLayout &L = j.L;
     const Chunk &ck = j.ck;
-    const int n = j.n_total, nch = j.decode ? j.nch : 2;
-    const int out_format = ck.on && j.decode ? ck.out_format : MP3S_PCM_I16;
-    const size_t esz = pcm_elem(out_format), frame_elems = (size_t)1152 * nch;
     const int set = j.set = (int)(P->issued++ & 1u);
-    const size_t ng = (size_t)std::max(n, j.grab_frames);
-    void *d_is = c->grab(set ? 24 : 0, ng * 2304 * 2), *d_si = c->grab(set ? 25 : 1, ng * 4 * sizeof(mp3s_granule_si)),
-         *d_keep = c->grab(set ? 26 : 7, ng * frame_elems * esz);
-    if (!d_is || !d_si || !d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+    JobView v;
+    if (const int rc = job_view(c, j, s, v)) return rc;
+    const int n = v.n;
     uint8_t *d_blob = s.d_stage, *d_side = s.d_stage + s.o_side;
     if (j.file_wide) { d_blob = P->up.d_blob; d_side = reinterpret_cast<uint8_t *>(P->up.d_side + ck.w0); }
     HIPCHK(hipEventRecord(s.e_start, P->s_up));
@@ -437,19 +470,16 @@ int issue_front(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23, boo
     HIPCHK(hipStreamWaitEvent(P->s_huff, s.e_up, 0));
     if (j.d_file) { const int rc = file_up_wait(P, j.file_need, P->s_huff); if (rc) return rc; }
     if (P->dec_used[set]) HIPCHK(hipStreamWaitEvent(P->s_huff, P->e_dec[set], 0));
-    // the small results: a walked job brings its block, status words zeroed, with its inputs (the kernels OR into them directly);
-    // a scanned one uses the slot's, written by the last workgroup of each kernel
-    int32_t *const d_small = j.walked ? (int32_t *)(s.d_stage + j.o_small) : s.d_small;
     if (j.walked) {
         uint64_t *d_tsel = j.decode ? (uint64_t *)(s.d_stage + s.o_tsel) : nullptr;
         const int e = launch_parse(P->s_huff, j.d_file ? j.d_file : s.d_image, j.image_base, (const FrameRef *)(s.d_stage + j.o_refs), (const StreamRef *)(s.d_stage + j.o_streams), n,
-                                   j.md_base, (mp3s_frame_side *)d_side, (mp3s_frame_hdr *)(s.d_stage + s.o_dechdr), d_blob, d_tsel, d_small + 4);
+                                   j.md_base, (mp3s_frame_side *)d_side, (mp3s_frame_hdr *)(s.d_stage + s.o_dechdr), d_blob, d_tsel, v.d_small + 4);
         if (e) return fail(MP3S_E_HIP, "parse launch: %s", hipGetErrorString((hipError_t)e));
     }
-    const int e = launch_huffman(P->s_huff, d_blob, (const mp3s_frame_side *)d_side, n, nch, max_p23, (int16_t *)d_is, (mp3s_granule_si *)d_si,
-                                 d_small + 3, j.walked ? nullptr : c->d_sync + 4, &c->prof, false, (int)c->opt[MP3S_OPT_HUF_LANES]);
+    const int e = launch_huffman(P->s_huff, d_blob, (const mp3s_frame_side *)d_side, n, v.nch, max_p23, (int16_t *)v.d_is, (mp3s_granule_si *)v.d_si,
+                                 v.d_small + 3, j.walked ? nullptr : c->d_sync + 4, &c->prof, false, (int)c->opt[MP3S_OPT_HUF_LANES]);
     if (e) return fail(MP3S_E_HIP, "huffman launch: %s", hipGetErrorString((hipError_t)e));
-    if (launch_place_frames(P->s_huff, s.d_stage + j.o_fix, j.n_fix, (int16_t *)d_is, (mp3s_granule_si *)d_si))
+    if (launch_place_frames(P->s_huff, s.d_stage + j.o_fix, j.n_fix, (int16_t *)v.d_is, (mp3s_granule_si *)v.d_si))
         return fail(MP3S_E_HIP, "placing the host-decoded frames failed");
     HIPCHK(hipEventRecord(s.e_huff, P->s_huff));
     if (trace_on()) fprintf(stderr, "mp3s:   front end queued %.3f ms after the job's start\n", now_ms() - t_issue0);
@@ -465,16 +495,11 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
     const double t_issue0 = trace_on() ? now_ms() : 0;
     const EncLayout &L = j.L;
     const Chunk &ck = j.ck;
-    const int n = j.n_total, nch = j.decode ? j.nch : 2;
-    const int out_format = ck.on && j.decode ? ck.out_format : MP3S_PCM_I16;
-    const size_t esz = pcm_elem(out_format), frame_elems = (size_t)1152 * nch;
     const int set = j.set;
-    const size_t ng = (size_t)std::max(n, j.grab_frames);
-    void *d_is = c->grab(set ? 24 : 0, ng * 2304 * 2), *d_si = c->grab(set ? 25 : 1, ng * 4 * sizeof(mp3s_granule_si)),
-         *d_keep = c->grab(set ? 26 : 7, ng * frame_elems * esz);
-    if (!d_is || !d_si || !d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+    JobView v;
+    if (const int rc = job_view(c, j, s, v)) return rc;
+    const int n = v.n;
     const mp3s_frame_hdr *d_dechdr = j.walked ? (const mp3s_frame_hdr *)(s.d_stage + s.o_dechdr) : (const mp3s_frame_hdr *)(s.d_stage + s.o_in);
-    int32_t *const d_small = j.walked ? (int32_t *)(s.d_stage + j.o_small) : s.d_small;
     if (inputs_later && j.pack_end > j.front_end) {
         HIPCHK(hipMemcpyAsync(s.d_stage + j.front_end, s.h_stage + j.front_end, j.pack_end - j.front_end, hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipEventRecord(s.e_in, P->s_up));
@@ -500,8 +525,8 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
         // (the last group's last dispatch signals e_dec itself where it can: a record is a packet of its own in the queue, 7-8 us of nothing
         //  between two kernels: tools/timeline.sh)
         const bool last_group = start + kDecodeChunk >= n;
-        const int rc = decode_transform_chunk(c, (const int16_t *)d_is, (const mp3s_granule_si *)d_si, d_dechdr, start - halo, cnt, nch, halo,
-                                              out_format, (uint8_t *)d_keep + (size_t)(start - halo0) * frame_elems * esz, ds,
+        const int rc = decode_transform_chunk(c, (const int16_t *)v.d_is, (const mp3s_granule_si *)v.d_si, d_dechdr, start - halo, cnt, v.nch, halo,
+                                              v.out_format, (uint8_t *)v.d_keep + (size_t)(start - halo0) * v.frame_elems * v.esz, ds,
                                               last_group && (c->opt[MP3S_OPT_PIPE_SIGNALS] & 1) ? P->e_dec[set] : nullptr);
         if (rc) return rc;
     }
@@ -515,31 +540,16 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
         j.down_pending = true;
         return defer_down ? MP3S_OK : issue_down(P, j, s);
     }
-    const int units = L.units;
-    const size_t b_mdct = (size_t)L.n_all * 2304 * 4, b_ix = (size_t)L.n * 2304 * 2, b_out = (size_t)units * sizeof(mp3s_gr_out),
-                 b_en = ((size_t)units * 22 * 4 + 255) & ~(size_t)255, b_sc = (size_t)L.n * 8 * 4;
-    const size_t need = b_mdct + b_ix + b_out + b_en + b_sc;
-    if (need > s.enc_cap) {   // (hipFree waits for the device; only while the slot is growing to its job size)
-        if (s.d_enc) (void)hipFree(s.d_enc);
-        s.d_enc = nullptr; s.enc_cap = 0;
-        if (hipMalloc((void **)&s.d_enc, need + need / 8) != hipSuccess) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
-        s.enc_cap = need + need / 8;
-    }
-    void *d_agg = c->grab(15, chain_agg_bytes(L.n));
-    if (!d_agg) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+    if (const int rc = slot_enc_dev(c, j, s, v.d_keep)) return rc;
     EncDev &dev = j.dev;
-    dev.d_pcm = (const int16_t *)d_keep; dev.d_in = s.d_stage + j.o_encblk; dev.d_mdct_all = (int32_t *)s.d_enc; dev.d_ix = (int16_t *)(s.d_enc + b_mdct);
-    dev.d_out = (mp3s_gr_out *)(s.d_enc + b_mdct + b_ix); dev.d_en = (int32_t *)(s.d_enc + b_mdct + b_ix + b_out); dev.d_agg = d_agg;
-    dev.d_mp3 = s.d_mp3; dev.d_sc = (int32_t *)(s.d_enc + b_mdct + b_ix + b_out + b_en);
-    dev.d_small = d_small; dev.direct_status = j.walked;
+    dev.d_small = v.d_small; dev.direct_status = j.walked;
     // the last chunk of a one-file call: nothing behind it hides its tail and its copy down, so the packer runs as two launches and
     // the first half of the bytes comes down under the second (the frame offsets are the host's own: enc_fill wrote them)
-    dev.pack_split = 0; dev.pack_half = nullptr; j.down_split = 0;
+    j.down_split = 0;
     if (ck.on && ck.last && j.walked && L.n >= 1024 && s.e_half && P->internal) {
         dev.pack_split = L.n / 2; dev.pack_half = s.e_half;
         j.down_split = reinterpret_cast<const uint32_t *>(s.h_stage + j.o_encblk + L.o_off)[dev.pack_split];
     }
-    if (!enc_variant_buffers(c, L, dev)) return fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
     const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, nullptr,
                              P->s_dec ? P->e_enc[set] : nullptr);
     if (rc) return rc;
@@ -557,11 +567,7 @@ int issue_down(mp3s_pipe *P, Job &j, Slot &s)
 {
     if (!j.down_pending) return MP3S_OK;
     j.down_pending = false;
-    mp3s_ctx *c = P->c;
     const Chunk &ck = j.ck;
-    const int n = j.n_total, nch = j.decode ? j.nch : 2;
-    const int out_format = ck.on && j.decode ? ck.out_format : MP3S_PCM_I16;
-    const size_t esz = pcm_elem(out_format), frame_elems = (size_t)1152 * nch;
     int32_t *const d_small = j.walked ? (int32_t *)(s.d_stage + j.o_small) : s.d_small;
     size_t done_bytes = 0;
     if (!j.decode && j.down_split > 0) {      // the bytes of the packer's first launch: behind ITS event, not the job's last kernel
@@ -572,17 +578,17 @@ int issue_down(mp3s_pipe *P, Job &j, Slot &s)
     }
     HIPCHK(hipStreamWaitEvent(P->s_down, s.e_comp, 0));
     if (j.decode) {
-        void *d_keep = c->grab(j.set ? 26 : 7, (size_t)std::max(n, j.grab_frames) * frame_elems * esz);
-        if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+        JobView v;
+        if (const int rc = job_view(P->c, j, s, v)) return rc;
         HIPCHK(hipMemcpyAsync(j.res->big[2].data(), d_small, kSmallHead, hipMemcpyDeviceToHost, P->s_down));
-        if (j.walked) HIPCHK(hipMemcpyAsync(j.res->big[1].data(), s.d_stage + s.o_tsel, (size_t)n * 8, hipMemcpyDeviceToHost, P->s_down));
+        if (j.walked) HIPCHK(hipMemcpyAsync(j.res->big[1].data(), s.d_stage + s.o_tsel, (size_t)v.n * 8, hipMemcpyDeviceToHost, P->s_down));
         if (ck.on) {
-            HIPCHK(hipMemcpyAsync(ck.dst, d_keep, (size_t)ck.count * frame_elems * esz, hipMemcpyDeviceToHost, P->s_down));
+            HIPCHK(hipMemcpyAsync(ck.dst, v.d_keep, (size_t)ck.count * v.frame_elems * v.esz, hipMemcpyDeviceToHost, P->s_down));
         } else {
             size_t first = 0;
             for (const auto &d : j.dec) {
-                const size_t bytes = (size_t)d.n_frames * frame_elems * 2;
-                HIPCHK(hipMemcpyAsync(j.res->mp3 + d.wav_off + 44, (const int16_t *)d_keep + first * frame_elems, bytes, hipMemcpyDeviceToHost, P->s_down));
+                const size_t bytes = (size_t)d.n_frames * v.frame_elems * 2;
+                HIPCHK(hipMemcpyAsync(j.res->mp3 + d.wav_off + 44, (const int16_t *)v.d_keep + first * v.frame_elems, bytes, hipMemcpyDeviceToHost, P->s_down));
                 first += (size_t)d.n_frames;
             }
         }
@@ -675,7 +681,7 @@ int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
     const EncLayout &L = j.L;
     const int n = j.n_total;
     const int set = j.set = (int)(P->issued++ & 1u);
-    void *d_keep = c->grab(set ? 26 : 7, (size_t)n * 2304 * 2);
+    void *d_keep = c->grab(kPoolPcm[set], (size_t)n * 2304 * 2);
     if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
     HIPCHK(hipEventRecord(s.e_start, P->s_up));
     for (const Upload &u : j.ups) HIPCHK(hipMemcpyAsync(s.d_wav + u.dst, u.src, u.bytes, hipMemcpyHostToDevice, P->s_up));
@@ -696,26 +702,10 @@ int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
     if (rw) return rw;
     HIPCHK(hipEventRecord(s.e_huff, P->s_huff));
     HIPCHK(hipStreamWaitEvent(c->stream, s.e_huff, 0));
-    const int units = L.units;
-    const size_t b_mdct = (size_t)L.n_all * 2304 * 4, b_ix = (size_t)L.n * 2304 * 2, b_out = (size_t)units * sizeof(mp3s_gr_out),
-                 b_en = ((size_t)units * 22 * 4 + 255) & ~(size_t)255, b_sc = (size_t)L.n * 8 * 4;
-    const size_t need = b_mdct + b_ix + b_out + b_en + b_sc;
-    if (need > s.enc_cap) {   // (hipFree waits for the device; only while the slot is growing to its job size)
-        if (s.d_enc) (void)hipFree(s.d_enc);
-        s.d_enc = nullptr; s.enc_cap = 0;
-        if (hipMalloc((void **)&s.d_enc, need + need / 8) != hipSuccess) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
-        s.enc_cap = need + need / 8;
-    }
-    void *d_agg = c->grab(15, chain_agg_bytes(L.n));
-    if (!d_agg) return fail(MP3S_E_NOMEM, "hipMalloc failed for a %d-frame job", n);
+    if (const int rc = slot_enc_dev(c, j, s, d_keep)) return rc;
     EncDev &dev = j.dev;
-    dev = EncDev();
-    dev.d_pcm = (const int16_t *)d_keep; dev.d_in = s.d_stage + j.o_encblk; dev.d_mdct_all = (int32_t *)s.d_enc; dev.d_ix = (int16_t *)(s.d_enc + b_mdct);
-    dev.d_out = (mp3s_gr_out *)(s.d_enc + b_mdct + b_ix); dev.d_en = (int32_t *)(s.d_enc + b_mdct + b_ix + b_out); dev.d_agg = d_agg;
-    dev.d_mp3 = s.d_mp3; dev.d_sc = (int32_t *)(s.d_enc + b_mdct + b_ix + b_out + b_en);
     dev.d_small = (int32_t *)(s.d_stage + j.o_small); dev.direct_status = true;
     j.down_split = 0;
-    if (!enc_variant_buffers(c, L, dev)) return fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
     const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, nullptr, P->e_enc[set]);
     if (rc) return rc;
     P->enc_used[set] = true; P->pcm_plain[set] = false;
