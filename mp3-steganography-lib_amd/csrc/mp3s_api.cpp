@@ -41,6 +41,58 @@ void select_entries(int first_unit, int reach, int first_entry, int hide_end, in
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the options
+// One row per MP3S_OPT_* (include/mp3s.h), row i for option i: what mp3s_ctx_create takes from the environment and mp3s_ctx_set_option from a caller.
+//   env: the variable that gives the default, read as a value (unset or empty: dflt) or, with env_off, by its presence alone -- set to anything, the empty
+//   string included, the option is 0.  kind: a flag (non-zero -> 1); a number; a number clamped to lo..hi; the bits of the mask hi; one of kResampleValues.
+// The two sides disagree, and both stay as they were: the environment turns a negative number into 0, applies the mask and turns a value outside the
+// set into 0; set_option refuses every negative value and a value outside the set, stores a mask's value as it is, and alone knows a number's
+// bounds (refused: a value other than 0 below lo, a value above hi -- while MP3S_CHUNK_FRAMES=2 is taken).
+enum OptKind { kOptFlag, kOptNumber, kOptClamped, kOptMask, kOptOneOf };
+struct OptRow { int id; const char *env; bool env_off; OptKind kind; int64_t dflt, lo, hi; };
+constexpr int64_t kOptNoLimit = INT64_MAX, kResampleValues[] = {0, 1, 32000, 44100, 48000};
+constexpr OptRow kOptions[] = {
+    {MP3S_OPT_ANALYSIS_SHARED, "MP3S_ANALYSIS_SHARED", false, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_SELECT, "MP3S_NO_SELECT", true, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_REDO, "MP3S_NO_REDO", true, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_FAST_IMDCT, "MP3S_FAST_IMDCT", false, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_PIPE_TAIL, "MP3S_PIPE_TAIL", false, kOptClamped, 1, 0, 2},
+    {MP3S_OPT_CHUNK_FRAMES, "MP3S_CHUNK_FRAMES", false, kOptNumber, 0, 4, kOptNoLimit},
+    {MP3S_OPT_DEVICE_PARSE, "MP3S_DEVICE_PARSE", false, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_FILE_PIPELINE, "MP3S_FILE_PIPELINE", false, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_SCAN_THREADS, "MP3S_SCAN_THREADS", false, kOptNumber, 0, 0, 64},
+    {MP3S_OPT_FIRST_CHUNK_FRAMES, "MP3S_FIRST_CHUNK_FRAMES", false, kOptNumber, 0, 4, kOptNoLimit},
+    {MP3S_OPT_FILE_UP, "MP3S_NO_FILE_UP", true, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_HUF_LANES, "MP3S_HUF_LANES", false, kOptNumber, 0, 0, kOptNoLimit},
+    {MP3S_OPT_NUMA, "MP3S_NO_NUMA", true, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_FLOAT_FAST, "MP3S_FLOAT_FAST", false, kOptFlag, 0, 0, 1},
+    {MP3S_OPT_FAIL_CHUNK, nullptr, false, kOptNumber, 0, 0, kOptNoLimit},
+    {MP3S_OPT_FUSED_DECODE, "MP3S_FUSED_DECODE", false, kOptFlag, 1, 0, 1},
+    {MP3S_OPT_FUSED_ENCODE, "MP3S_FUSED_ENCODE", false, kOptFlag, 0, 0, 1},
+    {MP3S_OPT_PIPE_DEC, "MP3S_PIPE_DEC", false, kOptFlag, 0, 0, 1},
+    {MP3S_OPT_RATE_SIGNALS, "MP3S_RATE_SIGNALS", false, kOptFlag, 0, 0, 1},
+    {MP3S_OPT_PIPE_SIGNALS, "MP3S_PIPE_SIGNALS", false, kOptMask, 0, 0, 3},
+    {MP3S_OPT_WAV_IMPORT, "MP3S_WAV_IMPORT", false, kOptFlag, 0, 0, 1},
+    {MP3S_OPT_WAV_RESAMPLE, "MP3S_WAV_RESAMPLE", false, kOptOneOf, 0, 0, 48000},
+};
+constexpr bool options_in_order(int i = 0) { return i == MP3S_OPT_COUNT || (kOptions[i].id == i && options_in_order(i + 1)); }
+static_assert(sizeof kOptions / sizeof *kOptions == MP3S_OPT_COUNT && options_in_order(), "one row per MP3S_OPT_*, row i for option i");
+
+static bool resample_value(int64_t v) { return std::find(std::begin(kResampleValues), std::end(kResampleValues), v) != std::end(kResampleValues); }
+static int64_t option_from_env(const OptRow &o)
+{
+    const char *v = o.env ? getenv(o.env) : nullptr;
+    if (o.env_off) return v ? 0 : o.dflt;
+    const int64_t x = v && *v ? (int64_t)atoll(v) : o.dflt;
+    switch (o.kind) {
+    case kOptFlag: return x != 0;
+    case kOptNumber: return std::max<int64_t>(0, x);
+    case kOptClamped: return std::min(o.hi, std::max(o.lo, x));
+    case kOptMask: return x & o.hi;
+    default: return resample_value(x) ? x : 0;
+    }
+}
+
 extern "C" {
 
 const char *mp3s_last_error(void) { return g_err.c_str(); }
@@ -109,33 +161,7 @@ int mp3s_ctx_create(int device, mp3s_ctx **out)
     if (e != hipSuccess) return fail(MP3S_E_NO_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
     mp3s_ctx *c = new mp3s_ctx();
     c->device = device;
-    {
-        // the environment provides the defaults, once
-        auto env = [](const char *name, int64_t dflt) { const char *v = getenv(name); return v && *v ? (int64_t)atoll(v) : dflt; };
-        c->opt[MP3S_OPT_SELECT] = getenv("MP3S_NO_SELECT") ? 0 : 1;
-        c->opt[MP3S_OPT_REDO] = getenv("MP3S_NO_REDO") ? 0 : 1;
-        c->opt[MP3S_OPT_FAST_IMDCT] = env("MP3S_FAST_IMDCT", 1) != 0;
-        c->opt[MP3S_OPT_PIPE_TAIL] = std::min<int64_t>(2, std::max<int64_t>(0, env("MP3S_PIPE_TAIL", 1)));
-        c->opt[MP3S_OPT_CHUNK_FRAMES] = std::max<int64_t>(0, env("MP3S_CHUNK_FRAMES", 0));
-        c->opt[MP3S_OPT_DEVICE_PARSE] = env("MP3S_DEVICE_PARSE", 1) != 0;
-        c->opt[MP3S_OPT_FILE_PIPELINE] = env("MP3S_FILE_PIPELINE", 1) != 0;
-        c->opt[MP3S_OPT_SCAN_THREADS] = std::max<int64_t>(0, env("MP3S_SCAN_THREADS", 0));
-        c->opt[MP3S_OPT_FIRST_CHUNK_FRAMES] = std::max<int64_t>(0, env("MP3S_FIRST_CHUNK_FRAMES", 0));
-        c->opt[MP3S_OPT_FILE_UP] = getenv("MP3S_NO_FILE_UP") ? 0 : 1;
-        c->opt[MP3S_OPT_HUF_LANES] = std::max<int64_t>(0, env("MP3S_HUF_LANES", 0));
-        c->opt[MP3S_OPT_NUMA] = getenv("MP3S_NO_NUMA") ? 0 : 1;
-        c->opt[MP3S_OPT_FLOAT_FAST] = env("MP3S_FLOAT_FAST", 0) != 0;
-        c->opt[MP3S_OPT_FAIL_CHUNK] = 0;
-        c->opt[MP3S_OPT_FUSED_DECODE] = env("MP3S_FUSED_DECODE", 1) != 0;
-        c->opt[MP3S_OPT_FUSED_ENCODE] = env("MP3S_FUSED_ENCODE", 0) != 0;
-        c->opt[MP3S_OPT_ANALYSIS_SHARED] = env("MP3S_ANALYSIS_SHARED", 1) != 0;
-        c->opt[MP3S_OPT_PIPE_DEC] = env("MP3S_PIPE_DEC", 0) != 0;
-        c->opt[MP3S_OPT_RATE_SIGNALS] = env("MP3S_RATE_SIGNALS", 0) != 0;
-        c->opt[MP3S_OPT_PIPE_SIGNALS] = env("MP3S_PIPE_SIGNALS", 0) & 3;
-        c->opt[MP3S_OPT_WAV_IMPORT] = env("MP3S_WAV_IMPORT", 0) != 0;
-        const int64_t rs = env("MP3S_WAV_RESAMPLE", 0);
-        c->opt[MP3S_OPT_WAV_RESAMPLE] = rs == 1 || rs == 32000 || rs == 44100 || rs == 48000 ? rs : 0;
-    }
+    for (const OptRow &o : kOptions) c->opt[o.id] = option_from_env(o);   // the environment provides the defaults, once
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming) != hipSuccess) {
@@ -193,13 +219,12 @@ int mp3s_ctx_host_share(mp3s_ctx *c, mp3s_host_share *out)
 int mp3s_ctx_set_option(mp3s_ctx *c, int option, int64_t value)
 {
     if (!c || option < 0 || option >= MP3S_OPT_COUNT) return fail(MP3S_E_ARG, "unknown option %d", option);
-    if (value < 0 || ((option == MP3S_OPT_CHUNK_FRAMES || option == MP3S_OPT_FIRST_CHUNK_FRAMES) && value != 0 && value < 4) || (option == MP3S_OPT_SCAN_THREADS && value > 64))
+    const OptRow &o = kOptions[option];
+    if (value < 0 || (o.kind == kOptNumber && ((value != 0 && value < o.lo) || value > o.hi)))
         return fail(MP3S_E_ARG, "option %d: value %lld out of range", option, (long long)value);
-    if (option == MP3S_OPT_WAV_RESAMPLE && value != 0 && value != 1 && value != 32000 && value != 44100 && value != 48000)
+    if (o.kind == kOptOneOf && !resample_value(value))
         return fail(MP3S_E_ARG, "option %d: %lld is not 0, 1, 32000, 44100 or 48000", option, (long long)value);
-    const bool number = option == MP3S_OPT_WAV_RESAMPLE || option == MP3S_OPT_CHUNK_FRAMES || option == MP3S_OPT_SCAN_THREADS || option == MP3S_OPT_FIRST_CHUNK_FRAMES ||
-                        option == MP3S_OPT_HUF_LANES || option == MP3S_OPT_FAIL_CHUNK || option == MP3S_OPT_PIPE_SIGNALS;
-    c->opt[option] = number ? value : (option == MP3S_OPT_PIPE_TAIL ? std::min<int64_t>(value, 2) : (value != 0));
+    c->opt[option] = o.kind == kOptFlag ? value != 0 : (o.kind == kOptClamped ? std::min(value, o.hi) : value);
     return MP3S_OK;
 }
 
@@ -398,17 +423,10 @@ int mp3s_decode_transform_dev(mp3s_ctx *c, const int16_t *d_is, const mp3s_granu
     if (!c || !d_is || !d_si || !d_hdr || !d_pcm) return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0 || nch < 1 || nch > 2 || n_halo < 0 || n_halo >= n_frames || out_format < 0 || out_format > 2)
         return fail(MP3S_E_ARG, "bad sizes: n_frames=%d nch=%d n_halo=%d fmt=%d", n_frames, nch, n_halo, out_format);
-    int rc = c->ensure_scratch(dec_scratch_bytes(n_frames, nch));
-    if (rc) return rc;
+    if (const int rc = c->ensure_scratch(dec_scratch_bytes(n_frames, nch))) return rc;
     if (int pe = guard_probe_usable(c, out_format)) return pe;
-    const int e = launch_decode(c->stream, d_is, d_si, d_hdr, n_frames, nch, n_halo, out_format, d_pcm, c->scratch, &c->prof, 0,
-                                c->synth_eps_scale, c->d_sync, c->opt[MP3S_OPT_FAST_IMDCT] != 0, c->opt[MP3S_OPT_FLOAT_FAST] != 0,
-                                c->opt[MP3S_OPT_FUSED_DECODE] != 0, nullptr, [&]() -> const GuardProbe * {
-                                    if (!c->guard_probe.x) return nullptr;
-                                    c->guard_probe.base = 0;
-                                    return &c->guard_probe; }());
-    if (e) return fail(MP3S_E_HIP, "decode launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+    const int e = launch_decode(c->stream, d_is, d_si, d_hdr, n_frames, nch, n_halo, out_format, d_pcm, c->scratch, &c->prof, decode_how(c, 0, nullptr, 0));
+    return e ? fail(MP3S_E_HIP, "decode launch: %s", hipGetErrorString((hipError_t)e)) : (int)MP3S_OK;
 }
 
 int mp3s_debug_guard_margin(mp3s_ctx *c, double *d_x, double *d_eps, int64_t capacity)
@@ -419,8 +437,6 @@ int mp3s_debug_guard_margin(mp3s_ctx *c, double *d_x, double *d_eps, int64_t cap
     c->guard_probe = GuardProbe{d_x, d_eps, 0, d_x ? capacity : 0};
     return MP3S_OK;
 }
-
-
 
 // frame 0 of a batch always starts from zero state; later frames must not point forward
 static int check_hdr(const mp3s_frame_hdr *hdr, int n)
@@ -468,17 +484,7 @@ int mp3s_encode_transform_dev(mp3s_ctx *c, const int16_t *d_pcm, const mp3s_fram
 {
     if (!c || !d_pcm || !d_hdr || !d_mdct) return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0) return fail(MP3S_E_ARG, "n_frames=%d", n_frames);
-    // k_enc_analysis computes a product once where the filter table repeats itself, exactly or up to sign (analysis_plan.h, analysis_sign_plan.h, generated from the table's values): a
-    // host whose libm rounds the table differently gets no wrong subband samples -- the encode entry points refuse, decoding is not affected
-    if (!host_tables().analysis_plan_ok)
-        return fail(MP3S_E_TABLES, "the analysis filter table built on this host does not repeat itself where the kernel shares products "
-                                   "(csrc/analysis_plan.h, csrc/analysis_sign_plan.h: run tools/gen_analysis_plan.py and tools/gen_analysis_sign_plan.py here and rebuild)");
-    const bool fused = c->opt[MP3S_OPT_FUSED_ENCODE] != 0;
-    int rc = fused ? MP3S_OK : c->ensure_scratch_enc(enc_scratch_bytes(n_frames));   // (the fused kernel keeps the subband samples in LDS)
-    if (rc) return rc;
-    const int e = launch_encode(c->stream, d_pcm, d_hdr, n_frames, d_mdct, c->scratch_enc, &c->prof, fused, c->opt[MP3S_OPT_ANALYSIS_SHARED] != 0);
-    if (e) return fail(MP3S_E_HIP, "encode launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+    return encode_transform_step(c, c->stream, d_pcm, d_hdr, n_frames, d_mdct);
 }
 
 int mp3s_encode_transform(mp3s_ctx *c, const int16_t *pcm, const mp3s_frame_hdr *hdr, int n_frames, int32_t *mdct)
@@ -510,14 +516,8 @@ int mp3s_rate_loop_dev(mp3s_ctx *c, const int32_t *d_mdct, const mp3s_rate_frame
     if (!c || !d_mdct || !d_frames || !d_ix || !d_out || !d_en) return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0 || n_hide < 0 || (n_hide > 0 && (!d_hide_bits || !d_cursor_in)))
         return fail(MP3S_E_ARG, "bad sizes / missing hide inputs");
-    const int e = launch_rate(c->stream, d_mdct, d_frames, n_frames, d_hide_bits, n_hide, d_cursor_in, d_state_in,
-                              d_unit_list, n_list, d_ix, d_out, d_en, &c->prof, 0, 0, nullptr,
-                              c->rate_done ? c->rate_done : (c->opt[MP3S_OPT_RATE_SIGNALS] ? c->ev_order : nullptr));
-    if (e) return fail(MP3S_E_HIP, "rate launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+    return rate_step(c, c->stream, rate_signal_default(c), d_mdct, d_frames, n_frames, d_hide_bits, n_hide, d_cursor_in, d_state_in, d_unit_list, n_list, d_ix, d_out, d_en);
 }
-
-
 
 void mp3s_select_patterns(uint8_t out[32])
 {
@@ -552,6 +552,52 @@ int select_plan(const mp3s_chain_seg *segs, int n_segs, mp3s_select_span *spans,
     return used;
 }
 
+int encode_transform_step(mp3s_ctx *c, hipStream_t stream, const int16_t *d_pcm, const mp3s_frame_hdr *d_hdr, int n_frames, int32_t *d_mdct)
+{
+    // k_enc_analysis computes a product once where the filter table repeats itself, exactly or up to sign (analysis_plan.h, analysis_sign_plan.h, generated from the table's values): a
+    // host whose libm rounds the table differently gets no wrong subband samples -- the encode entry points refuse, decoding is not affected
+    if (!host_tables().analysis_plan_ok)
+        return fail(MP3S_E_TABLES, "the analysis filter table built on this host does not repeat itself where the kernel shares products "
+                                   "(csrc/analysis_plan.h, csrc/analysis_sign_plan.h: run tools/gen_analysis_plan.py and tools/gen_analysis_sign_plan.py here and rebuild)");
+    const bool fused = c->opt[MP3S_OPT_FUSED_ENCODE] != 0;
+    if (const int rc = fused ? (int)MP3S_OK : c->ensure_scratch_enc(enc_scratch_bytes(n_frames))) return rc;   // (the fused kernel keeps the subband samples in LDS)
+    const int e = launch_encode(stream, d_pcm, d_hdr, n_frames, d_mdct, c->scratch_enc, &c->prof, fused, c->opt[MP3S_OPT_ANALYSIS_SHARED] != 0);
+    return e ? fail(MP3S_E_HIP, "encode launch: %s", hipGetErrorString((hipError_t)e)) : (int)MP3S_OK;
+}
+
+int rate_step(mp3s_ctx *c, hipStream_t stream, hipEvent_t done, const int32_t *d_mdct, const mp3s_rate_frame *d_frames, int n_frames, const uint8_t *d_hide,
+              int n_hide, const int32_t *d_cursor, const int32_t *d_state, const int32_t *d_list, int n_list, int16_t *d_ix, mp3s_gr_out *d_out, int32_t *d_en,
+              const RateVariantArgs *variants)
+{
+    // (a pipe runs the selection of the job in front on its tail stream: that one reads the variant buffers this launch writes)
+    if (variants && c->sel_pending && hipStreamWaitEvent(stream, c->ev_sel, 0) != hipSuccess) return fail(MP3S_E_HIP, "ordering behind the previous selection failed");
+    if (variants) c->sel_pending = false;
+    const int e = launch_rate(stream, d_mdct, d_frames, n_frames, d_hide, n_hide, d_cursor, d_state, d_list, n_list, d_ix, d_out, d_en, &c->prof, 0, 0, variants, done);
+    return e ? fail(MP3S_E_HIP, "rate launch: %s", hipGetErrorString((hipError_t)e)) : (int)MP3S_OK;
+}
+
+int select_step(mp3s_ctx *c, hipStream_t stream, const uint8_t *d_hide, int32_t *d_cursor, const mp3s_chain_seg *d_segs, const mp3s_select_span *d_spans,
+                int n_segs, int max_reach, const RateVariantArgs &va, int16_t *d_ix, mp3s_gr_out *d_out, int32_t *d_en)
+{
+    void *d_pairs = c->grab(kPoolSelectDev, (size_t)n_segs * max_reach * 8, stream);
+    if (!d_pairs) return fail(MP3S_E_NOMEM, "hipMalloc failed for the selection scratch");
+    const int e = launch_select(stream, d_segs, d_spans, n_segs, max_reach, d_hide, va, d_ix, d_en, d_out, d_cursor, d_pairs, &c->prof);
+    if (e) return fail(MP3S_E_HIP, "select launch: %s", hipGetErrorString((hipError_t)e));
+    if (stream == c->stream) return MP3S_OK;
+    // the variant buffers are the context's, and the next rate loop that writes them is queued on another stream than this reader
+    if (!c->ev_sel && hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming) != hipSuccess) return fail(MP3S_E_HIP, "event creation failed");
+    if (hipEventRecord(c->ev_sel, stream) != hipSuccess) return fail(MP3S_E_HIP, "event record failed");
+    c->sel_pending = true;
+    return MP3S_OK;
+}
+
+int pack_step(mp3s_ctx *c, hipStream_t stream, const int16_t *d_ix, const mp3s_gr_out *d_gr, const int32_t *d_en, int n_frames, int sri, int bri, int whole,
+              const uint32_t *d_frame_off, const uint8_t *d_padding, uint8_t *d_mp3, int32_t *d_scfsi, int32_t *d_status)
+{
+    const int e = launch_pack(stream, d_ix, d_gr, d_en, n_frames, sri, bri, whole, d_frame_off, d_padding, d_mp3, d_scfsi, d_status, c->d_sync, &c->prof);
+    return e ? fail(MP3S_E_HIP, "pack launch: %s", hipGetErrorString((hipError_t)e)) : (int)MP3S_OK;
+}
+
 extern "C" {
 
 int mp3s_rate_variants_dev(mp3s_ctx *c, const int32_t *d_mdct, const mp3s_rate_frame *d_frames, int n_frames, const uint8_t *d_hide_bits,
@@ -562,14 +608,8 @@ int mp3s_rate_variants_dev(mp3s_ctx *c, const int32_t *d_mdct, const mp3s_rate_f
         !d_outv || !d_env)
         return fail(MP3S_E_ARG, "null pointer");
     if (n_frames <= 0 || n_hide < 32 || n_entries <= 0) return fail(MP3S_E_ARG, "bad sizes");
-    // (a pipe runs the selection of the job in front on its tail stream: that one reads the variant buffers this launch writes)
-    if (c->sel_pending && hipStreamWaitEvent(c->stream, c->ev_sel, 0) != hipSuccess) return fail(MP3S_E_HIP, "ordering behind the previous selection failed");
-    c->sel_pending = false;
-    const RateVariantArgs va = {d_ent_unit, d_ent_cursor, n_entries, d_ixv, d_outv, d_env, (uint8_t *)(d_outv + n_entries)};
-    const int e = launch_rate(c->stream, d_mdct, d_frames, n_frames, d_hide_bits, n_hide, d_cursor, nullptr, nullptr, 0, d_ix, d_out, d_en,
-                              &c->prof, 0, 0, &va, c->rate_done ? c->rate_done : (c->opt[MP3S_OPT_RATE_SIGNALS] ? c->ev_order : nullptr));
-    if (e) return fail(MP3S_E_HIP, "rate launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+    const RateVariantArgs va = variant_args(d_ent_unit, d_ent_cursor, n_entries, d_ixv, d_outv, d_env);
+    return rate_step(c, c->stream, rate_signal_default(c), d_mdct, d_frames, n_frames, d_hide_bits, n_hide, d_cursor, nullptr, nullptr, 0, d_ix, d_out, d_en, &va);
 }
 
 int mp3s_select_dev(mp3s_ctx *c, const uint8_t *d_hide_bits, int32_t *d_cursor, const mp3s_chain_seg *d_segs, const mp3s_select_span *d_spans,
@@ -580,12 +620,8 @@ int mp3s_select_dev(mp3s_ctx *c, const uint8_t *d_hide_bits, int32_t *d_cursor, 
         !d_outv || !d_env)
         return fail(MP3S_E_ARG, "null pointer");
     if (n_segs <= 0 || n_entries <= 0 || max_reach <= 0 || max_reach > MP3S_SELECT_MAX_REACH) return fail(MP3S_E_ARG, "bad sizes");
-    const RateVariantArgs va = {d_ent_unit, d_ent_cursor, n_entries, d_ixv, d_outv, d_env, (uint8_t *)(d_outv + n_entries)};
-    void *d_pairs = c->grab(kPoolSelectDev, (size_t)n_segs * max_reach * 8);
-    if (!d_pairs) return fail(MP3S_E_NOMEM, "hipMalloc failed for the selection scratch");
-    const int e = launch_select(c->stream, d_segs, d_spans, n_segs, max_reach, d_hide_bits, va, d_ix, d_en, d_out, d_cursor, d_pairs, &c->prof);
-    if (e) return fail(MP3S_E_HIP, "select launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+    return select_step(c, c->stream, d_hide_bits, d_cursor, d_segs, d_spans, n_segs, max_reach, variant_args(d_ent_unit, d_ent_cursor, n_entries, d_ixv, d_outv, d_env),
+                       d_ix, d_out, d_en);
 }
 
 int mp3s_rate_select_dev(mp3s_ctx *c, const int32_t *d_mdct, const mp3s_rate_frame *d_frames, int n_frames, const uint8_t *d_hide_bits,
@@ -595,9 +631,8 @@ int mp3s_rate_select_dev(mp3s_ctx *c, const int32_t *d_mdct, const mp3s_rate_fra
 {
     if (!d_segs || !d_spans) return fail(MP3S_E_ARG, "null pointer");
     if (n_segs <= 0 || max_reach <= 0 || max_reach > MP3S_SELECT_MAX_REACH) return fail(MP3S_E_ARG, "bad sizes");
-    const int rc = mp3s_rate_variants_dev(c, d_mdct, d_frames, n_frames, d_hide_bits, n_hide, d_cursor, d_ent_unit, d_ent_cursor, n_entries, d_ix,
-                                          d_out, d_en, d_ixv, d_outv, d_env);
-    if (rc) return rc;
+    if (const int rc = mp3s_rate_variants_dev(c, d_mdct, d_frames, n_frames, d_hide_bits, n_hide, d_cursor, d_ent_unit, d_ent_cursor, n_entries, d_ix, d_out, d_en, d_ixv,
+                                              d_outv, d_env)) return rc;
     return mp3s_select_dev(c, d_hide_bits, d_cursor, d_segs, d_spans, n_segs, max_reach, d_ent_unit, d_ent_cursor, n_entries, d_ix, d_out, d_en,
                            d_ixv, d_outv, d_env);
 }
@@ -649,10 +684,7 @@ int mp3s_pack_frames_dev(mp3s_ctx *c, const int16_t *d_ix, const mp3s_gr_out *d_
     int sri, bri, whole;
     if (n_frames <= 0 || stream_params(samplerate, bitrate_kbps, &sri, &bri, &whole))
         return fail(MP3S_E_UNSUPPORTED, "unsupported samplerate/bitrate %d/%d", samplerate, bitrate_kbps);
-    const int e = launch_pack(c->stream, d_ix, d_gr, d_en, n_frames, sri, bri, whole, d_frame_off, d_padding, d_mp3, d_scfsi,
-                              d_status, c->d_sync, &c->prof);
-    if (e) return fail(MP3S_E_HIP, "pack launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+    return pack_step(c, c->stream, d_ix, d_gr, d_en, n_frames, sri, bri, whole, d_frame_off, d_padding, d_mp3, d_scfsi, d_status);
 }
 
 // ------------------------------------------------------------------------------------------------ host stages

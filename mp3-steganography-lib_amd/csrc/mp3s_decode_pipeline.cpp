@@ -67,17 +67,11 @@ int front_end(mp3s_multi &m, int i)
 int decode_transform_chunk(mp3s_ctx *c, const int16_t *d_is, const mp3s_granule_si *d_si, const mp3s_frame_hdr *d_hdr, long first, int cnt,
                            int nch, int halo, int out_format, void *d_pcm, hipStream_t stream, hipEvent_t done)
 {
-    int rc = c->ensure_scratch(dec_scratch_bytes(cnt, nch));
-    if (rc) return rc;
+    if (const int rc = c->ensure_scratch(dec_scratch_bytes(cnt, nch))) return rc;
     if (int pe = guard_probe_usable(c, out_format)) return pe;
     const int e = launch_decode(stream ? stream : c->stream, d_is + (size_t)first * 2304, d_si + (size_t)first * 4, d_hdr + first, cnt, nch, halo, out_format,
-                                d_pcm, c->scratch, &c->prof, (int)first, c->synth_eps_scale, c->d_sync, c->opt[MP3S_OPT_FAST_IMDCT] != 0, c->opt[MP3S_OPT_FLOAT_FAST] != 0,
-                                c->opt[MP3S_OPT_FUSED_DECODE] != 0, done, [&]() -> const GuardProbe * {
-                                    if (!c->guard_probe.x) return nullptr;
-                                    c->guard_probe.base = (int64_t)(first + halo) * 1152 * nch;   // (a batch's chunks fill the probe's arrays side by side)
-                                    return &c->guard_probe; }());
-    if (e) return fail(MP3S_E_HIP, "decode launch: %s", hipGetErrorString((hipError_t)e));
-    return MP3S_OK;
+                                d_pcm, c->scratch, &c->prof, decode_how(c, (int)first, done, (int64_t)(first + halo) * 1152 * nch));
+    return e ? fail(MP3S_E_HIP, "decode launch: %s", hipGetErrorString((hipError_t)e)) : (int)MP3S_OK;
 }
 
 // The front half of a decode batch (mp3s_internal.h): layout, upload, Huffman decode, the host's repair, host-parsed streams placed.

@@ -30,6 +30,7 @@ struct Profiler {
     unsigned mask = ~0u;                      // bit k: kernel k gets an event pair
     double total_ms[K_COUNT] = {0};
     long count[K_COUNT] = {0};
+    int take(int k);                          // a fresh event pair for kernel k: its index, or -1 (not enabled, not in the mask, none left)
     int begin(hipStream_t s, int k);          // returns pair index or -1
     void end(hipStream_t s, int pair);
     // the pair as the START and STOP event of one dispatch (hipExtLaunchKernelGGL): the kernel's own time stamps, no record packets around it
@@ -43,20 +44,18 @@ int dev_upload_tables(hipStream_t stream);
 struct GuardProbe { double *x, *eps; int64_t base, cap; };
 // scratch: time-domain subband samples, float64 [nch][36 n][32], + what the fast int16 path keeps beside them
 size_t dec_scratch_bytes(int n_frames, int nch);
+// how a batch is decoded: the context's part (decode_how, mp3s_internal.h) and the caller's (done, the probe's base)
+struct DecodeHow {
+    int sf_base;              // hdr[].stream_first counts from this frame of the batch; d_is / d_si / d_hdr start there
+    double eps_scale;         // int16 output: guard of the fast kernels (imdct_run<true>, k_dec_synth_fast); 0 = the exact kernels
+    int32_t *d_sync;          // the context's self-clearing words (8): [2] counts the samples the guard sent through the exact order, [6..7] belong to the fix-up list; null: the exact kernels
+    bool fast_imdct, float_fast, fused;   // MP3S_OPT_FAST_IMDCT: the mirrored, fused IMDCT under the fast synthesis; MP3S_OPT_FLOAT_FAST: float32 output through the fast sums,
+                              // unguarded (within 1e-5, not bit-identical); MP3S_OPT_FUSED_DECODE: the fast paths as one kernel (k_decode_stream.hpp)
+    hipEvent_t done;          // (may be null) recorded behind the transforms: as the last dispatch's own completion signal on the fused int16 path (no record packet), by a record otherwise
+    const GuardProbe *probe;  // the fused int16 path also writes its fast values and guard widths there (null, or x == null: no probe)
+};
 int launch_decode(hipStream_t stream, const int16_t *d_is, const mp3s_granule_si *d_si, const mp3s_frame_hdr *d_hdr,
-                  int n_frames, int nch, int n_halo, int out_format, void *d_pcm, void *d_scratch, Profiler *prof,
-                  int sf_base = 0 /* hdr[].stream_first counts from this frame of the batch; d_is / d_si / d_hdr start there */,
-                  double synth_eps_scale = 1.0 /* int16 output: guard of the fast kernels (imdct_run<true>, k_dec_synth_fast);
-                                                  0 = the exact kernels */,
-                  int32_t *d_sync = nullptr /* the context's self-clearing words (8): [2] counts the samples the guard sent
-                                               through the exact order, [6..7] belong to the fix-up list; without them the
-                                               exact kernels run */,
-                  bool fast_imdct = true /* MP3S_OPT_FAST_IMDCT: the mirrored, fused IMDCT under the fast synthesis */,
-                  bool float_fast = false /* MP3S_OPT_FLOAT_FAST: float32 output through the fast sums, unguarded (within 1e-5, not bit-identical) */,
-                  bool fused = true /* MP3S_OPT_FUSED_DECODE: the fast paths as one kernel, S in LDS (k_decode_fused.hpp) */,
-                  hipEvent_t done = nullptr /* recorded behind the transforms: as the last dispatch's own completion signal where the path has one
-                                               (the fused int16 path: no record packet in the queue), by a record otherwise */,
-                  const GuardProbe *probe = nullptr /* the fused int16 path also writes its fast values and guard widths there (a probe) */);
+                  int n_frames, int nch, int n_halo, int out_format, void *d_pcm, void *d_scratch, Profiler *prof, const DecodeHow &how);
 
 // scratch: subband samples int32 [2][32][36 n]
 size_t enc_scratch_bytes(int n_frames);

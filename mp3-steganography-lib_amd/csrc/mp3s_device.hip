@@ -39,7 +39,7 @@ __constant__ __attribute__((aligned(64))) int32_t c_fl_sign[ANALYSIS_SIGN_STREAM
 
 namespace mp3s {
 
-int Profiler::begin(hipStream_t s, int k)
+int Profiler::take(int k)
 {
     if (!enabled || !((mask >> k) & 1u)) return -1;
     if (n_pairs >= MAX_PAIRS) { dropped++; return -1; }
@@ -48,8 +48,13 @@ int Profiler::begin(hipStream_t s, int k)
         n_created++;
     }
     kid[n_pairs] = k;
-    (void)hipEventRecord(ev[2 * n_pairs], s);
     return n_pairs++;
+}
+int Profiler::begin(hipStream_t s, int k)
+{
+    const int pair = take(k);
+    if (pair >= 0) (void)hipEventRecord(ev[2 * pair], s);
+    return pair;
 }
 void Profiler::end(hipStream_t s, int pair)
 {
@@ -57,15 +62,9 @@ void Profiler::end(hipStream_t s, int pair)
 }
 bool Profiler::attach(int k, hipEvent_t *start, hipEvent_t *stop)
 {
-    if (!enabled || !((mask >> k) & 1u)) return false;
-    if (n_pairs >= MAX_PAIRS) { dropped++; return false; }
-    while (n_created < 2 * (n_pairs + 1)) {
-        if (hipEventCreate(&ev[n_created]) != hipSuccess) { dropped++; return false; }
-        n_created++;
-    }
-    kid[n_pairs] = k;
-    *start = ev[2 * n_pairs]; *stop = ev[2 * n_pairs + 1];
-    n_pairs++;
+    const int pair = take(k);
+    if (pair < 0) return false;
+    *start = ev[2 * pair]; *stop = ev[2 * pair + 1];
     return true;
 }
 
@@ -89,103 +88,86 @@ size_t dec_scratch_bytes(int n_frames, int nch)
     return dec_S_bytes(n_frames, nch) + dec_G_bytes(n_frames) + (size_t)nch * (size_t)n_frames * 36 * sizeof(uint2);
 }
 
-int launch_decode(hipStream_t stream, const int16_t *d_is, const mp3s_granule_si *d_si, const mp3s_frame_hdr *d_hdr,
-                  int n_frames, int nch, int n_halo, int out_format, void *d_pcm, void *d_scratch, Profiler *prof, int sf_base,
-                  double synth_eps_scale, int32_t *d_sync, bool fast_imdct, bool float_fast, bool fused, hipEvent_t done, const GuardProbe *probe)
+// granules per wave of a decode kernel: a wave primes itself with `priming` granules of work in front of its run, so longer runs waste
+// less; of r_min..r_max the run length that fills whole rounds of the chip's `slots` wave slots best
+static int dec_run_length(int n_gran, int r_min, int r_max, long slots, double priming)
 {
+    int run = r_max; double best = 1e30;
+    for (int r = r_min; r <= r_max; r++) {
+        const long waves = (n_gran + r - 1) / r;
+        const long rounds = (waves + slots - 1) / slots;
+        const double cost = (double)rounds * (r + priming);
+        if (cost < best) { best = cost; run = r; }
+    }
+    return run;
+}
+
+// the samples the guard of a fast int16 path could not vouch for, again from `is` in the reference's order (a handful per batch); `done`: the dispatch's own completion signal
+static void launch_dec_fixup(hipStream_t stream, hipEvent_t done, const int16_t *d_is, const mp3s_granule_si *d_si, const mp3s_frame_hdr *d_hdr,
+                             int n_gran, int nch, long T, int n_halo, int sf_base, void *d_pcm, const uint2 *fix_list, int32_t *d_sync)
+{
+    const int fix_groups = (int)((T * nch + DEC_A_WAVES - 1) / DEC_A_WAVES) < 128 ? (int)((T * nch + DEC_A_WAVES - 1) / DEC_A_WAVES) : 128;
+    if (done)
+        hipExtLaunchKernelGGL(k_dec_fixup, dim3(fix_groups), dim3(DEC_A_WAVES * 64), 0, stream, nullptr, done, 0, d_is, d_si, d_hdr, n_gran, nch, T, n_halo,
+                              sf_base, (int16_t *)d_pcm, fix_list, d_sync + 6, d_sync + 2);
+    else
+        hipLaunchKernelGGL(k_dec_fixup, dim3(fix_groups), dim3(DEC_A_WAVES * 64), 0, stream, d_is, d_si, d_hdr, n_gran, nch, T, n_halo,
+                           sf_base, (int16_t *)d_pcm, fix_list, d_sync + 6, d_sync + 2);
+}
+
+int launch_decode(hipStream_t stream, const int16_t *d_is, const mp3s_granule_si *d_si, const mp3s_frame_hdr *d_hdr,
+                  int n_frames, int nch, int n_halo, int out_format, void *d_pcm, void *d_scratch, Profiler *prof, const DecodeHow &how)
+{
+    const int sf_base = how.sf_base; int32_t *const d_sync = how.d_sync; hipEvent_t done = how.done;
     const long T = (long)n_frames * 36;
     double *S = (double *)d_scratch;
     double *G = (double *)((char *)d_scratch + dec_S_bytes(n_frames, nch));
     uint2 *fix_list = (uint2 *)((char *)G + dec_G_bytes(n_frames));
     const int n_gran = n_frames * 2;
     // int16 output through the fast kernels (guarded; needs the context's counters), everything else in the reference's order
-    const bool fast = out_format == MP3S_PCM_I16 && synth_eps_scale > 0 && d_sync;
+    const bool fast = out_format == MP3S_PCM_I16 && how.eps_scale > 0 && d_sync;
     // float32 output through the same fast sums, unguarded (MP3S_OPT_FLOAT_FAST: within 1e-5 of the reference, not bit-identical)
-    const bool fast32 = out_format == MP3S_PCM_F32 && float_fast;
+    const bool fast32 = out_format == MP3S_PCM_F32 && how.float_fast;
     // the fast paths as ONE kernel, a wave-local stream with no intermediate array (k_decode_stream.hpp); timed as the synthesis
-    if (fused && ((fast && fast_imdct) || fast32)) {
-        // granules per wave: a run is primed with a granule and a half of work in front of it, so longer runs waste less; short enough that
-        // the waves fill the chip's slots (two waves per SIMD: 2 048) in whole rounds
-        int run = 16;
-        {
-            double best = 1e30;
-            for (int r = 4; r <= 16; r++) {
-                const long waves = (n_gran + r - 1) / r;
-                const long rounds = (waves + 2047) / 2048;
-                const double cost = (double)rounds * (r + 1.6);
-                if (cost < best) { best = cost; run = r; }
-            }
-        }
-        const int runs = (n_gran + run - 1) / run;
-        const dim3 grid((runs + ST_WAVES - 1) / ST_WAVES), block(ST_WAVES * 64);
-        const int pf = prof ? prof->begin(stream, K_DEC_SYNTH) : -1;
-        if (fast32) {
-            if (nch == 2) hipLaunchKernelGGL((k_dec_stream<2, true>), grid, block, 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, 1.0, (uint2 *)nullptr, (int32_t *)nullptr, (double *)nullptr, (double *)nullptr, 0L, 0L);
-            else hipLaunchKernelGGL((k_dec_stream<1, true>), grid, block, 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, 1.0, (uint2 *)nullptr, (int32_t *)nullptr, (double *)nullptr, (double *)nullptr, 0L, 0L);
-        } else {
-            if (probe && probe->x) {     // (mp3s_debug_guard_margin: the probe's instantiation of the same kernel)
-                if (nch == 2) hipLaunchKernelGGL((k_dec_stream<2, false, true>), grid, block, 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, synth_eps_scale, fix_list, d_sync + 6, probe->x, probe->eps, (long)probe->base, (long)probe->cap);
-                else hipLaunchKernelGGL((k_dec_stream<1, false, true>), grid, block, 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, synth_eps_scale, fix_list, d_sync + 6, probe->x, probe->eps, (long)probe->base, (long)probe->cap);
-            } else if (nch == 2) hipLaunchKernelGGL((k_dec_stream<2, false>), grid, block, 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, synth_eps_scale, fix_list, d_sync + 6, (double *)nullptr, (double *)nullptr, 0L, 0L);
-            else hipLaunchKernelGGL((k_dec_stream<1, false>), grid, block, 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, synth_eps_scale, fix_list, d_sync + 6, (double *)nullptr, (double *)nullptr, 0L, 0L);
-            const int fix_groups = (int)((T * nch + DEC_A_WAVES - 1) / DEC_A_WAVES) < 128 ? (int)((T * nch + DEC_A_WAVES - 1) / DEC_A_WAVES) : 128;
-            if (done)
-                hipExtLaunchKernelGGL(k_dec_fixup, dim3(fix_groups), dim3(DEC_A_WAVES * 64), 0, stream, nullptr, done, 0, d_is, d_si, d_hdr, n_gran, nch, T, n_halo,
-                                      sf_base, (int16_t *)d_pcm, (const uint2 *)fix_list, d_sync + 6, d_sync + 2);
-            else
-                hipLaunchKernelGGL(k_dec_fixup, dim3(fix_groups), dim3(DEC_A_WAVES * 64), 0, stream, d_is, d_si, d_hdr, n_gran, nch, T, n_halo,
-                                   sf_base, (int16_t *)d_pcm, (const uint2 *)fix_list, d_sync + 6, d_sync + 2);
+    const bool streamed = how.fused && ((fast && how.fast_imdct) || fast32);
+    // granules per wave.  The stream kernel primes a run with a granule and a half of work and fills two waves per SIMD (2 048 slots); the IMDCT
+    // kernel primes a run with half an IMDCT of the granule in front of it (168 VGPRs -> 3 waves per SIMD -> 256 CUs x 12 = 3 072 slots)
+    const int run = streamed ? dec_run_length(n_gran, 4, 16, 2048, 1.6) : dec_run_length(n_gran, 2, 8, 3072, 0.55);
+    const int runs = (n_gran + run - 1) / run;
+    // what only the guarded int16 kernels take
+    const double eps = fast ? how.eps_scale : 1.0;
+    uint2 *const fix = fast ? fix_list : nullptr;
+    int32_t *const fix_count = fast ? d_sync + 6 : nullptr;
+    int pp;
+    if (streamed) {
+        const bool probing = !fast32 && how.probe && how.probe->x;   // (mp3s_debug_guard_margin: the probe's instantiation of the same kernel)
+        auto *const kernel = fast32 ? (nch == 2 ? k_dec_stream<2, true> : k_dec_stream<1, true>)
+                           : probing ? (nch == 2 ? k_dec_stream<2, false, true> : k_dec_stream<1, false, true>)
+                                     : (nch == 2 ? k_dec_stream<2, false> : k_dec_stream<1, false>);
+        pp = prof ? prof->begin(stream, K_DEC_SYNTH) : -1;
+        hipLaunchKernelGGL(kernel, dim3((runs + ST_WAVES - 1) / ST_WAVES), dim3(ST_WAVES * 64), 0, stream, d_is, d_si, d_hdr, n_gran, run, n_halo, d_pcm, sf_base, eps, fix, fix_count,
+                           probing ? how.probe->x : (double *)nullptr, probing ? how.probe->eps : (double *)nullptr, probing ? (long)how.probe->base : 0L,
+                           probing ? (long)how.probe->cap : 0L);
+        if (!fast32) {
+            launch_dec_fixup(stream, done, d_is, d_si, d_hdr, n_gran, nch, T, n_halo, sf_base, d_pcm, fix_list, d_sync);
             done = nullptr;                                  // (signalled by the dispatch itself)
         }
-        if (prof) prof->end(stream, pf);
-        if (done && hipEventRecord(done, stream) != hipSuccess) return (int)hipErrorUnknown;
-        return (int)hipGetLastError();
-    }
-    // granules per wave: each wave also primes itself with half an IMDCT of the granule before its run, so longer
-    // runs waste less; pick the run length (2..8) that fills whole rounds of the chip's wave slots best (168 VGPRs ->
-    // 3 waves per SIMD -> 256 CUs x 12 = 3072 slots)
-    int run = 8;
-    {
-        double best = 1e30;
-        for (int r = 2; r <= 8; r++) {
-            const long waves = (n_gran + r - 1) / r;
-            const long rounds = (waves + 3071) / 3072;
-            const double cost = (double)rounds * (r + 0.55);
-            if (cost < best) { best = cost; run = r; }
-        }
-    }
-    const int runs = (n_gran + run - 1) / run;
-    int pp = prof ? prof->begin(stream, K_DEC_IMDCT) : -1;
-    if ((fast && fast_imdct) || fast32)
-        hipLaunchKernelGGL(k_dec_imdct<true>, dim3((runs + DEC_A_WAVES - 1) / DEC_A_WAVES), dim3(DEC_A_WAVES * 64), 0, stream,
-                           d_is, d_si, d_hdr, n_gran, nch, run, S, T, sf_base, fast32 ? (double *)nullptr : G);
-    else
-        hipLaunchKernelGGL(k_dec_imdct<false>, dim3((runs + DEC_A_WAVES - 1) / DEC_A_WAVES), dim3(DEC_A_WAVES * 64), 0, stream,
-                           d_is, d_si, d_hdr, n_gran, nch, run, S, T, sf_base, (double *)nullptr);
-    if (prof) prof->end(stream, pp);
-    constexpr int TW = DEC_SYNTH_TW;
-    pp = prof ? prof->begin(stream, K_DEC_SYNTH) : -1;
-    if (fast32) {
-        constexpr int W = DEC_SYNTH_FAST_TW;
-        hipLaunchKernelGGL((k_dec_synth_fast<W, true>), dim3((unsigned)((T + (W * 64 - 15) - 1) / (W * 64 - 15))), dim3(W * 64 * nch), 0, stream,
-                           (const double *)S, T, d_hdr, nch, n_halo, (int16_t *)d_pcm, sf_base, 1.0, (const double *)nullptr, n_gran, (uint2 *)nullptr, (int32_t *)nullptr);
-    } else if (fast) {
-        constexpr int ftw = DEC_SYNTH_FAST_TW;
-        const double *Gk = fast_imdct ? G : nullptr;
-#define MP3S_FAST_LAUNCH(W)                                                                                                        \
-        hipLaunchKernelGGL(k_dec_synth_fast<W>, dim3((unsigned)((T + (W * 64 - 15) - 1) / (W * 64 - 15))), dim3(W * 64 * nch), 0, stream, \
-                           (const double *)S, T, d_hdr, nch, n_halo, (int16_t *)d_pcm, sf_base, synth_eps_scale, Gk, n_gran, fix_list, d_sync + 6)
-        MP3S_FAST_LAUNCH(ftw);
-#undef MP3S_FAST_LAUNCH
-        // the samples the guard could not vouch for, again from `is` in the reference's order (a handful per batch)
-        const int fix_groups = (int)((T * nch + DEC_A_WAVES - 1) / DEC_A_WAVES) < 128 ? (int)((T * nch + DEC_A_WAVES - 1) / DEC_A_WAVES) : 128;
-        hipLaunchKernelGGL(k_dec_fixup, dim3(fix_groups), dim3(DEC_A_WAVES * 64), 0, stream, d_is, d_si, d_hdr, n_gran, nch, T, n_halo,
-                           sf_base, (int16_t *)d_pcm, (const uint2 *)fix_list, d_sync + 6, d_sync + 2);
     } else {
-        const int out_per_tile = TW * 64 - 15;
-        const int tiles = (int)((T + out_per_tile - 1) / out_per_tile);
-        hipLaunchKernelGGL(k_dec_synth<TW>, dim3(tiles), dim3(TW * 64 * nch), 0, stream, (const double *)S, T, d_hdr, nch,
-                           n_halo, out_format, d_pcm, sf_base);
+        pp = prof ? prof->begin(stream, K_DEC_IMDCT) : -1;
+        const bool mirrored = (fast && how.fast_imdct) || fast32;
+        hipLaunchKernelGGL(mirrored ? k_dec_imdct<true> : k_dec_imdct<false>, dim3((runs + DEC_A_WAVES - 1) / DEC_A_WAVES), dim3(DEC_A_WAVES * 64), 0, stream,
+                           d_is, d_si, d_hdr, n_gran, nch, run, S, T, sf_base, mirrored && !fast32 ? G : (double *)nullptr);
+        if (prof) prof->end(stream, pp);
+        constexpr int TW = DEC_SYNTH_TW, W = DEC_SYNTH_FAST_TW;
+        pp = prof ? prof->begin(stream, K_DEC_SYNTH) : -1;
+        if (fast32 || fast) {
+            hipLaunchKernelGGL((fast32 ? k_dec_synth_fast<W, true> : k_dec_synth_fast<W>), dim3((unsigned)((T + (W * 64 - 15) - 1) / (W * 64 - 15))), dim3(W * 64 * nch), 0, stream,
+                               (const double *)S, T, d_hdr, nch, n_halo, (int16_t *)d_pcm, sf_base, eps, mirrored && !fast32 ? (const double *)G : nullptr, n_gran, fix, fix_count);
+            if (!fast32) launch_dec_fixup(stream, nullptr, d_is, d_si, d_hdr, n_gran, nch, T, n_halo, sf_base, d_pcm, fix_list, d_sync);
+        } else {
+            const int tiles = (int)((T + (TW * 64 - 15) - 1) / (TW * 64 - 15));
+            hipLaunchKernelGGL(k_dec_synth<TW>, dim3(tiles), dim3(TW * 64 * nch), 0, stream, (const double *)S, T, d_hdr, nch, n_halo, out_format, d_pcm, sf_base);
+        }
     }
     if (prof) prof->end(stream, pp);
     if (done && hipEventRecord(done, stream) != hipSuccess) return (int)hipErrorUnknown;

@@ -5,7 +5,6 @@
 #include <cerrno>
 #include "mp3s_internal.h"
 
-
 // message bits the frames in front of a block have taken
 static int64_t cursor0(const EncSeg &s)
 {
@@ -193,60 +192,36 @@ void tables_guess_of(const mp3s_frame_side *side, long n_frames, int extra, std:
     }
 }
 
-int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail, hipEvent_t tail_from, hipEvent_t rate_after, hipEvent_t pcm_read)
+int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail, hipEvent_t tail_from, hipEvent_t pcm_read)
 {
     const mp3s_frame_hdr *d_hdr = (const mp3s_frame_hdr *)d.d_in;
     const mp3s_rate_frame *d_rf = (const mp3s_rate_frame *)(d.d_in + L.o_rf);
-    const int32_t *d_cur = (const int32_t *)(d.d_in + L.o_cur);
+    int32_t *d_cur = const_cast<int32_t *>((const int32_t *)(d.d_in + L.o_cur));   // (written by the selection and the chain check's re-runs)
     const uint8_t *d_hide = d.d_in + L.o_hide;
     const mp3s_chain_seg *d_segs = (const mp3s_chain_seg *)(d.d_in + L.o_segs);
+    const mp3s_select_span *d_spans = (const mp3s_select_span *)(d.d_in + L.o_spans);
+    const int32_t *d_ent = (const int32_t *)(d.d_in + L.o_ent);
     const int32_t *d_mdct = d.d_mdct_all + (size_t)L.lead * 2304;   // the block's own frames
-    int rc = mp3s_encode_transform_dev(c, d.d_pcm, d_hdr, L.n_all, d.d_mdct_all);
+    int rc = encode_transform_step(c, c->stream, d.d_pcm, d_hdr, L.n_all, d.d_mdct_all);
     if (!rc && pcm_read && hipEventRecord(pcm_read, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "event record failed");   // the PCM buffer may be written again
-    // (the tail of the job in front is through before this job's rate loop starts: tails do not queue up behind one another)
-    if (!rc && rate_after && hipStreamWaitEvent(c->stream, rate_after, 0) != hipSuccess) rc = fail(MP3S_E_HIP, "ordering behind the previous tail failed");
-    const bool select_on_tail = tail && L.n_entries > 0;
+    // short messages (L.n_entries > 0): their variants run in the rate loop's launch and the device decides the cursor chain (no guess).  With a
+    // tail stream the selection (two small launches) belongs to the tail: the compute stream is free for the next job's decode transforms 25 us
+    // earlier.  The variant buffers are the context's: a rate loop that writes them waits for the selection in front of it (rate_step).
+    const RateVariantArgs va = variant_args(d_ent, d_ent + L.n_entries, L.n_entries, d.d_ixv, d.d_outv, d.d_env);
     // with a tail stream the rate loop is the compute stream's last launch of the job and the tail waits for IT: its dispatch carries
     // tail_from as its own completion signal (a record would be a packet of its own in the queue: 7-8 us of nothing in front of the
     // next job's decode, tools/timeline.sh)
-    const bool rate_signals = tail && tail_from && (select_on_tail || L.n_entries <= 0) && (c->opt[MP3S_OPT_PIPE_SIGNALS] & 2);
-    if (rate_signals) c->rate_done = tail_from;
-    if (!rc && L.n_entries > 0) {
-        // short messages: their variants run in the same launch and the device decides the cursor chain (no guess).  With a tail
-        // stream the selection (two small launches) belongs to the tail: the compute stream is free for the next job's decode
-        // transforms 25 us earlier.  The variant buffers are the context's: a rate loop that writes them waits for the selection in front of it (mp3s_rate_variants_dev).
-        const int32_t *d_ent = (const int32_t *)(d.d_in + L.o_ent);
-        if (!rc && !select_on_tail)
-            rc = mp3s_rate_select_dev(c, d_mdct, d_rf, L.n, d_hide, L.n_hide, const_cast<int32_t *>(d_cur), d_segs,
-                                      (const mp3s_select_span *)(d.d_in + L.o_spans), L.n_segs, L.max_reach, d_ent, d_ent + L.n_entries,
-                                      L.n_entries, d.d_ix, d.d_out, d.d_en, d.d_ixv, d.d_outv, d.d_env);
-        else if (!rc)
-            rc = mp3s_rate_variants_dev(c, d_mdct, d_rf, L.n, d_hide, L.n_hide, d_cur, d_ent, d_ent + L.n_entries, L.n_entries, d.d_ix, d.d_out, d.d_en,
-                                        d.d_ixv, d.d_outv, d.d_env);
-    } else if (!rc)
-        rc = mp3s_rate_loop_dev(c, d_mdct, d_rf, L.n, d_hide, L.n_hide, d_cur, nullptr, nullptr, 0, d.d_ix, d.d_out, d.d_en);
+    const bool rate_signals = tail && tail_from && (c->opt[MP3S_OPT_PIPE_SIGNALS] & 2);
+    if (!rc) rc = rate_step(c, c->stream, rate_signals ? tail_from : rate_signal_default(c), d_mdct, d_rf, L.n, d_hide, L.n_hide, d_cur, nullptr, nullptr, 0, d.d_ix, d.d_out,
+                            d.d_en, L.n_entries > 0 ? &va : nullptr);
     // The tail of a job -- selection, chain check (two small launches each) and bit packing -- reads only the job's own buffers: the pipe
     // gives it a stream of its own, so that the small launches and their gaps lie under the decode transforms of the next
     // job instead of in front of them (bench.py --pack-overlap: 0.829 -> 0.785 ms per step).  Every tail goes through the
     // same stream, so the context's chain scratch and the packer's sync words are still used by one launch at a time.
-    c->rate_done = nullptr;
-    hipStream_t ts = c->stream;
-    if (!rc && tail) {
-        if ((!rate_signals && hipEventRecord(tail_from, c->stream) != hipSuccess) || hipStreamWaitEvent(tail, tail_from, 0) != hipSuccess)
-            rc = fail(MP3S_E_HIP, "ordering the tail stream failed");
-        ts = tail;
-    }
-    if (!rc && select_on_tail) {
-        const int32_t *d_ent = (const int32_t *)(d.d_in + L.o_ent);
-        hipStream_t keep = c->stream;
-        c->stream = ts;                       // (the entry point launches on the context's stream)
-        rc = mp3s_select_dev(c, d_hide, const_cast<int32_t *>(d_cur), d_segs, (const mp3s_select_span *)(d.d_in + L.o_spans), L.n_segs, L.max_reach,
-                             d_ent, d_ent + L.n_entries, L.n_entries, d.d_ix, d.d_out, d.d_en, d.d_ixv, d.d_outv, d.d_env);
-        c->stream = keep;
-        if (!rc && !c->ev_sel && hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming) != hipSuccess) rc = fail(MP3S_E_HIP, "event creation failed");
-        if (!rc && hipEventRecord(c->ev_sel, ts) != hipSuccess) rc = fail(MP3S_E_HIP, "event record failed");
-        if (!rc) c->sel_pending = true;
-    }
+    const hipStream_t ts = tail ? tail : c->stream;
+    if (!rc && tail && ((!rate_signals && hipEventRecord(tail_from, c->stream) != hipSuccess) || hipStreamWaitEvent(tail, tail_from, 0) != hipSuccess))
+        rc = fail(MP3S_E_HIP, "ordering the tail stream failed");
+    if (!rc && L.n_entries > 0) rc = select_step(c, ts, d_hide, d_cur, d_segs, d_spans, L.n_segs, L.max_reach, va, d.d_ix, d.d_out, d.d_en);
     if (!rc) {
         // (with the device's own re-runs of the units that inherited other addresses than the zeros they were given)
         const ChainRedoArgs redo = {d_mdct, d_hide, L.n_hide, d.d_ix, d.d_en};
@@ -262,13 +237,12 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
     // packed on the assumption that the verdict is "nothing to redo" (the common case); the caller discards it otherwise
     if (!rc) {
         const bool halves = d.direct_status && d.pack_half && d.pack_split > 0 && d.pack_split < L.n;
-        int e = launch_pack(ts, d.d_ix, d.d_out, d.d_en, L.n, L.sri, L.bri, L.whole, (const uint32_t *)(d.d_in + L.o_off), d.d_in + L.o_pad, d.d_mp3,
-                            d.d_sc, d.d_small + 2, d.direct_status ? nullptr : c->d_sync, &c->prof, 0, halves ? d.pack_split : -1);
-        if (!e && halves) {
-            if (hipEventRecord(d.pack_half, ts) != hipSuccess) e = (int)hipErrorUnknown;
-            else e = launch_pack(ts, d.d_ix, d.d_out, d.d_en, L.n, L.sri, L.bri, L.whole, (const uint32_t *)(d.d_in + L.o_off), d.d_in + L.o_pad, d.d_mp3,
-                                 d.d_sc, d.d_small + 2, nullptr, &c->prof, d.pack_split, -1);
-        }
+        auto pack = [&](int32_t *d_sync, int f_begin, int f_end) {
+            return launch_pack(ts, d.d_ix, d.d_out, d.d_en, L.n, L.sri, L.bri, L.whole, (const uint32_t *)(d.d_in + L.o_off), d.d_in + L.o_pad, d.d_mp3, d.d_sc,
+                               d.d_small + 2, d_sync, &c->prof, f_begin, f_end);
+        };
+        int e = pack(d.direct_status ? nullptr : c->d_sync, 0, halves ? d.pack_split : -1);
+        if (!e && halves) e = hipEventRecord(d.pack_half, ts) != hipSuccess ? (int)hipErrorUnknown : pack(nullptr, d.pack_split, -1);
         if (e) rc = fail(MP3S_E_HIP, "pack launch: %s", hipGetErrorString((hipError_t)e));
     }
     return rc;
@@ -281,7 +255,7 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
 int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, const uint8_t *in, const EncDev &d, mp3s_buf *b, bool have_gr,
                 int *passes_out)
 {
-    const int n = L.n, units = L.units, n_hide = L.n_hide, samplerate = L.samplerate, bitrate_kbps = L.kbps;
+    const int n = L.n, units = L.units, n_hide = L.n_hide;
     const uint8_t *hide_all = in + L.o_hide;
     const uint8_t *const d_in = d.d_in;
     int16_t *const d_ix = d.d_ix; mp3s_gr_out *const d_out = d.d_out; int32_t *const d_en = d.d_en; uint8_t *const d_mp3 = d.d_mp3;
@@ -498,9 +472,7 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     if (!rc) {
         // ---- bit packing again, on the final GrInfo
         rc = mp3s_dev_upload(c, d_out, gr, (size_t)units * sizeof(mp3s_gr_out));
-        if (!rc) rc = mp3s_pack_frames_dev(c, (const int16_t *)d_ix, (const mp3s_gr_out *)d_out, (const int32_t *)d_en, n, samplerate,
-                                           bitrate_kbps, (const uint32_t *)((uint8_t *)d_in + L.o_off), (const uint8_t *)d_in + L.o_pad,
-                                           (uint8_t *)d_mp3, (int32_t *)d_sc, (int32_t *)d_small + 2);
+        if (!rc) rc = pack_step(c, c->stream, d_ix, d_out, d_en, n, L.sri, L.bri, L.whole, (const uint32_t *)(d_in + L.o_off), d_in + L.o_pad, d_mp3, d_sc, d_small + 2);
         int32_t st = 0;
         if (!rc) rc = mp3s_dev_download(c, &st, (int32_t *)d_small + 2, sizeof st);
         if (!rc && st) rc = fail(MP3S_E_HIP, "bit packer reported status %d", st);
@@ -511,7 +483,6 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     if (passes_out) *passes_out = passes;
     return rc;
 }
-
 
 // Encode the streams of `segs` (stereo, one sampling rate and bitrate) as ONE batch: transforms, rate loop, bit packing.
 // pcm_dev != nullptr: the int16 PCM is already in HBM (re-encode after a device decode) and pcm is ignored.

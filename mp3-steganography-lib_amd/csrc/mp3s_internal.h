@@ -43,9 +43,9 @@ using namespace mp3s;
 //   A pipe owns its context while it exists (mp3s.h): no other call runs beside its jobs.  They alternate between two sets of {Is, Si, Pcm}
 //   -- job k + 1 fills the other set while job k's is read -- and a set is written again only behind the events of the job that had it
 //   (e_dec, e_enc, e_down: pipe_jobs.cpp).  ChainAgg and the Var* buffers are one per context: the jobs' rate loops, selections and chain
-//   checks follow each other on the compute and tail streams (tail_from, rate_after, ev_sel).
+//   checks follow each other on the compute and tail streams (tail_from, ev_sel).
 //   The _dev calls (test aids on the caller's device arrays, nothing waited for) queue on the context's stream: what a later call writes
-//   to a buffer they share lies behind their reads, and a regrow synchronises that stream first.  SelectDev and ChainDev are theirs alone.
+//   to a buffer they share lies behind their reads, and a regrow synchronises that stream first.  ChainDev is theirs alone.
 enum PoolSlot : int {
     kPoolIs0, kPoolSi0,     // Huffman output of a decode batch (decode_front) or of set 0 of a pipe: samples [frames][2][2][576] int16, granule records
     kPoolFrameHdr, kPoolPcmChunk, kPoolHufStatus, kPoolMainData, kPoolSideInfo,   // decode_front: headers, a chunk of PCM on its way down, Huffman status, main data, side records
@@ -62,7 +62,9 @@ enum PoolSlot : int {
                             // (enc_variant_buffers) Ix, Out and Energy -- their selection is through before a resolve begins
     kPoolIs1, kPoolSi1, kPoolPcm1,      // set 1 of a pipe
     kPoolWavImage, kPoolResampleRows,   // wav_to_device: the files' bytes with the kernels' records behind them; PCM at the source rate for the resampler
-    kPoolSelectDev, kPoolChainDev,      // scratch of mp3s_select_dev; of mp3s_chain_resolve_dev and mp3s_chain_redo_dev
+    kPoolSelectDev,         // scratch of select_step, grown behind a synchronise of the stream the step was given alone: its users all run on one stream at a time -- the
+                            // context's, or for the jobs of a pipe with a tail stream that tail (from pipe_create, which drains the context's stream, to pipe_quiesce, which drains the pipe's)
+    kPoolChainDev,          // scratch of mp3s_chain_resolve_dev and mp3s_chain_redo_dev
     kPoolReveal,            // mp3s_reveal_messages: a batch's [files | records | packed bits out]
     kPoolSlotCount
 };
@@ -79,13 +81,12 @@ struct mp3s_ctx {
    // mp3s_*_fd: the file the result goes to, how many of its bytes (behind sink_base: the WAV header's place) run_file has written already
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_order = nullptr;
-    hipEvent_t ev_sel = nullptr; bool sel_pending = false;   // a selection on a tail stream has read the variant buffers (enc_issue)
-    hipEvent_t rate_done = nullptr;   // set by enc_issue around its call of a rate entry point: the rate loop's dispatch signals it (no record packet)
+    hipEvent_t ev_sel = nullptr; bool sel_pending = false;   // a selection on another stream than the context's has read the variant buffers (select_step; rate_step waits)
     int32_t *d_sync = nullptr;        // 64-bit word {finished workgroups | error bits} of the pack kernel in flight (k_sync.hpp): self-clearing;
                                       // [2] counts the samples the fast synthesis computed again in the exact order
     double synth_eps_scale = 1.0;     // int16 decode: scale of the fast synthesis guard (0 = always the exact kernel)
     GuardProbe guard_probe = {nullptr, nullptr, 0, 0};   // mp3s_debug_guard_margin
-    void *scratch = nullptr; size_t scratch_bytes = 0;
+    void *scratch = nullptr, *scratch_enc = nullptr; size_t scratch_bytes = 0, scratch_enc_bytes = 0;   // of the decode, of the encode transforms
     Profiler prof;
     // device buffers of the stream pipelines, kept between calls (hipMalloc/hipFree cost more than a small file's work)
     static constexpr int kPoolSlots = 32;
@@ -94,12 +95,12 @@ struct mp3s_ctx {
     std::vector<ResampleTaps> res_taps;
     void *pool[kPoolSlots] = {nullptr};
     size_t pool_bytes[kPoolSlots] = {0};
-    void *grab(PoolSlot slot, size_t bytes)
+    void *grab(PoolSlot slot, size_t bytes, hipStream_t user = nullptr /* the stream the buffer's users run on; null: the context's */)
     {
         if (slot < 0 || slot >= kPoolSlots) return nullptr;   // (callers answer MP3S_E_NOMEM)
         if (bytes < 16) bytes = 16;
         if (pool_bytes[slot] >= bytes) return pool[slot];
-        if (pool[slot]) { hipStreamSynchronize(stream); hipFree(pool[slot]); pool[slot] = nullptr; pool_bytes[slot] = 0; }
+        if (pool[slot]) { hipStreamSynchronize(user ? user : stream); hipFree(pool[slot]); pool[slot] = nullptr; pool_bytes[slot] = 0; }
         const size_t want = bytes + bytes / 4;   // head room: similar-sized files reuse the buffer
         if (hipMalloc(&pool[slot], want) != hipSuccess) { pool[slot] = nullptr; return nullptr; }
         pool_bytes[slot] = want;
@@ -124,27 +125,19 @@ struct mp3s_ctx {
     hipEvent_t ev_pcm_tiles = nullptr;
     // ... and the block [workgroup table | given lags] of the last mp3s_pcm_align_dev, by the same rule and behind the same event
     std::vector<uint8_t> h_pcm_align;
-    int ensure_scratch(size_t bytes)
+    static int ensure(void *&buf, size_t &have, size_t bytes)
     {
-        if (bytes <= scratch_bytes) return 0;
-        if (scratch) { hipFree(scratch); scratch = nullptr; scratch_bytes = 0; }
-        hipError_t e = hipMalloc(&scratch, bytes);
+        if (bytes <= have) return 0;
+        if (buf) { hipFree(buf); buf = nullptr; have = 0; }
+        hipError_t e = hipMalloc(&buf, bytes);
         if (e != hipSuccess) return fail(MP3S_E_NOMEM, "hipMalloc(%zu) for scratch: %s", bytes, hipGetErrorString(e));
-        scratch_bytes = bytes;
+        have = bytes;
         return 0;
     }
+    int ensure_scratch(size_t bytes) { return ensure(scratch, scratch_bytes, bytes); }
     // the encode transforms' scratch (subband samples between analysis and MDCT) is a buffer of its own: in the pipe the decode
     // transforms of the next job run on another stream beside them
-    void *scratch_enc = nullptr; size_t scratch_enc_bytes = 0;
-    int ensure_scratch_enc(size_t bytes)
-    {
-        if (bytes <= scratch_enc_bytes) return 0;
-        if (scratch_enc) { hipFree(scratch_enc); scratch_enc = nullptr; scratch_enc_bytes = 0; }
-        hipError_t e = hipMalloc(&scratch_enc, bytes);
-        if (e != hipSuccess) return fail(MP3S_E_NOMEM, "hipMalloc(%zu) for scratch: %s", bytes, hipGetErrorString(e));
-        scratch_enc_bytes = bytes;
-        return 0;
-    }
+    int ensure_scratch_enc(size_t bytes) { return ensure(scratch_enc, scratch_enc_bytes, bytes); }
 };
 static_assert(kPoolSlotCount <= mp3s_ctx::kPoolSlots, "every PoolSlot needs a place in mp3s_ctx::pool");
 
@@ -160,6 +153,15 @@ inline int guard_probe_usable(const mp3s_ctx *c, int out_format)
     if (c->opt[MP3S_OPT_FUSED_DECODE] && c->opt[MP3S_OPT_FAST_IMDCT] && c->synth_eps_scale > 0 && c->d_sync) return MP3S_OK;
     return fail(MP3S_E_ARG, "the guard probe is set (mp3s_debug_guard_margin) and this int16 decode would not run the stream kernel that fills it "
                             "(MP3S_OPT_FUSED_DECODE / MP3S_OPT_FAST_IMDCT off, or the guard's scale is 0)");
+}
+
+// How this context decodes (DecodeHow, mp3s_device.h): its options, its guard scale and its counters.  The caller's: sf_base, the event the
+// transforms complete, and where the launch's first sample lies in the guard probe's arrays (a batch's chunks fill them side by side).
+inline DecodeHow decode_how(mp3s_ctx *c, int sf_base, hipEvent_t done, int64_t probe_base)
+{
+    if (c->guard_probe.x) c->guard_probe.base = probe_base;
+    return {sf_base, c->synth_eps_scale, c->d_sync, c->opt[MP3S_OPT_FAST_IMDCT] != 0, c->opt[MP3S_OPT_FLOAT_FAST] != 0, c->opt[MP3S_OPT_FUSED_DECODE] != 0,
+            done, c->guard_probe.x ? &c->guard_probe : nullptr};
 }
 
 int local_world_size();   // mp3s_hostinfo.cpp: LOCAL_WORLD_SIZE of the launcher (1 without one)
@@ -531,11 +533,30 @@ inline EncScratch enc_scratch_layout(const EncLayout &L)
 void select_entries(int first_unit, int reach, int first_entry, int hide_end, int64_t bits_left, int32_t *ent_unit, int32_t *ent_cursor);
 // device buffers for L.n_entries variant entries from the context's pool (kPoolVarIx, kPoolVarOut, kPoolVarEnergy: the host's variants', free at that point)
 bool enc_variant_buffers(mp3s_ctx *c, const EncLayout &L, EncDev &d);
-// transforms -> rate loop on the guessed cursors -> chain check -> bit packing (with d.d_cap: k_capacity in its place), all on c->stream,
-// nothing waited for.  The packed bytes (the capacity records) are final iff verdict[0] == 0 and verdict[1] == 0 (d_small[0], d_small[1]).
-int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail = nullptr /* chain check + packing on this stream, ordered behind the rate loop through tail_from */,
-              hipEvent_t tail_from = nullptr, hipEvent_t rate_after = nullptr /* the rate loop waits for this event (the previous job's tail) */,
-              hipEvent_t pcm_read = nullptr /* recorded behind the encode transforms: the PCM they read may be overwritten */);
+// The device steps of an encode (mp3s_api.cpp), each queued on the stream its caller names, nothing waited for; MP3S_OK, or the code and text
+// of the entry point of the same name (mp3s_*_dev), which is the step on the context's stream behind its argument checks.
+int encode_transform_step(mp3s_ctx *c, hipStream_t stream, const int16_t *d_pcm, const mp3s_frame_hdr *d_hdr, int n_frames, int32_t *d_mdct);
+// the variant entries of a rate loop and of the selection behind it, from the arrays the entry points take (the table counts lie behind the records)
+inline RateVariantArgs variant_args(const int32_t *d_ent_unit, const int32_t *d_ent_cursor, int n_entries, int16_t *d_ixv, mp3s_gr_out *d_outv, int32_t *d_env)
+{
+    return {d_ent_unit, d_ent_cursor, n_entries, d_ixv, d_outv, d_env, (uint8_t *)(d_outv + n_entries)};
+}
+// the completion event of a rate loop whose caller has none of its own (MP3S_OPT_RATE_SIGNALS: the dispatch signals ev_order, mp3s_ctx_wait_last)
+inline hipEvent_t rate_signal_default(const mp3s_ctx *c) { return c->opt[MP3S_OPT_RATE_SIGNALS] ? c->ev_order : nullptr; }
+// done (may be null): the dispatch's own completion signal, no record packet.  With variants the launch writes the context's variant buffers: it waits for a selection that read them on another stream (sel_pending)
+int rate_step(mp3s_ctx *c, hipStream_t stream, hipEvent_t done, const int32_t *d_mdct, const mp3s_rate_frame *d_frames, int n_frames, const uint8_t *d_hide,
+              int n_hide, const int32_t *d_cursor, const int32_t *d_state, const int32_t *d_list, int n_list, int16_t *d_ix, mp3s_gr_out *d_out, int32_t *d_en,
+              const RateVariantArgs *variants = nullptr);
+// on another stream than the context's the step records ev_sel behind itself and sets sel_pending, for the next rate_step with variants
+int select_step(mp3s_ctx *c, hipStream_t stream, const uint8_t *d_hide, int32_t *d_cursor, const mp3s_chain_seg *d_segs, const mp3s_select_span *d_spans,
+                int n_segs, int max_reach, const RateVariantArgs &va, int16_t *d_ix, mp3s_gr_out *d_out, int32_t *d_en);
+// the packer in one launch, through the context's sync words (one launch at a time)
+int pack_step(mp3s_ctx *c, hipStream_t stream, const int16_t *d_ix, const mp3s_gr_out *d_gr, const int32_t *d_en, int n_frames, int sri, int bri, int whole,
+              const uint32_t *d_frame_off, const uint8_t *d_padding, uint8_t *d_mp3, int32_t *d_scfsi, int32_t *d_status);
+// transforms -> rate loop on the guessed cursors, on c->stream; selection -> chain check -> bit packing (with d.d_cap: k_capacity in its place) on `tail`, or on
+// c->stream without one; nothing waited for.  The packed bytes (the capacity records) are final iff verdict[0] == 0 and verdict[1] == 0 (d_small[0], d_small[1]).
+int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail = nullptr /* ordered behind the rate loop through tail_from */,
+              hipEvent_t tail_from = nullptr, hipEvent_t pcm_read = nullptr /* recorded behind the encode transforms: the PCM they read may be overwritten */);
 // verdict != 0: the host resolves the chains on the first pass's device buffers (walk, message variants, exact re-runs,
 // packing again); `in` = the host copy of the block.  Pool buffers of its own: kPoolRedo, kPoolVarEntries .. kPoolVarPairs.
 int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, const uint8_t *in, const EncDev &d, mp3s_buf *b, bool have_gr,

@@ -550,8 +550,7 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
         dev.pack_split = L.n / 2; dev.pack_half = s.e_half;
         j.down_split = reinterpret_cast<const uint32_t *>(s.h_stage + j.o_encblk + L.o_off)[dev.pack_split];
     }
-    const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, nullptr,
-                             P->s_dec ? P->e_enc[set] : nullptr);
+    const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, P->s_dec ? P->e_enc[set] : nullptr);
     if (rc) return rc;
     if (trace_on()) fprintf(stderr, "mp3s:   encode side queued %.3f ms after the job's start\n", now_ms() - t_issue0);
     if (P->s_dec) P->enc_used[set] = true;
@@ -706,7 +705,7 @@ int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
     EncDev &dev = j.dev;
     dev.d_small = (int32_t *)(s.d_stage + j.o_small); dev.direct_status = true;
     j.down_split = 0;
-    const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, nullptr, P->e_enc[set]);
+    const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, P->e_enc[set]);
     if (rc) return rc;
     P->enc_used[set] = true; P->pcm_plain[set] = false;
     HIPCHK(hipEventRecord(s.e_comp, P->s_tail ? P->s_tail : c->stream));
