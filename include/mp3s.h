@@ -354,8 +354,10 @@ int mp3s_chain_resolve_dev(mp3s_ctx *ctx, mp3s_gr_out *d_gr, const mp3s_rate_fra
  * quiet granules behind a silence), or ran on another cursor, are listed on the device, run again on the cursor and
  * addresses the check found (results in place, d_cursor updated for them) and everything is checked once more.  The
  * verdict is the second check's: 0 = final.  What it still finds (a re-run changed what later units inherit, more than
- * 1 024 units listed) is left to the host as before.  Operands as for mp3s_rate_loop_dev / mp3s_chain_resolve_dev; every
- * unit must have run without d_state_in (the records carry what they were given). */
+ * 4 096 units listed, a row of inheriting units longer than one re-run follows) is left to the host as before -- or to
+ * another call on the same buffers: every re-run records what it was given, so the call may be repeated and goes on
+ * where the one before stopped (tests/test_chain_redo.py).  Operands as for mp3s_rate_loop_dev / mp3s_chain_resolve_dev;
+ * every unit must have run without d_state_in (the records carry what they were given). */
 int mp3s_chain_redo_dev(mp3s_ctx *ctx, const int32_t *d_mdct, const mp3s_rate_frame *d_frames, int n_frames,
                         const uint8_t *d_hide_bits, int n_hide, int32_t *d_cursor, const mp3s_chain_seg *d_segs, int n_segs,
                         int16_t *d_ix, mp3s_gr_out *d_gr, int32_t *d_en, int32_t *d_verdict, mp3s_chain_seg_out *d_seg_out);

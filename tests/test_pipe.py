@@ -207,37 +207,15 @@ def test_chain_check_on_the_device(ctx, mlib):
     finally:
         for p in (d_mdct, d_rf, d_hide, d_cur, d_segs, d_ix, d_out, d_en, d_ver, d_so):
             ctx.free(p)
-    # the host walk (what csrc/mp3s_encode_pipeline.cpp's walk() does)
-    exp = before.copy()
-    n_redo = 0
-    for s in range(2):
-        f0, nf = int(segs["first_frame"][s]), int(segs["n_frames"][s])
-        c, end = int(segs["hide_begin"][s]), int(segs["hide_end"][s])
-        chain = segs["chain_in"][s].copy()
-        own = [False] * 4
-        used_carry = c < end
-        for u in range(f0 * 4, (f0 + nf) * 4):
-            k = u & 3
-            g = exp[u]
-            active = bool(g["flags"] & mlib.RF_ACTIVE)
-            used_addr = bool(g["flags"] & mlib.RF_USED_ADDR_IN)
-            if not own[k] and (not active or used_addr):
-                used_carry = True
-            if active:
-                own[k] = True
-            redo = active and int(cur[u]) != c and min(int(cur[u]), c) < end
-            if used_addr and tuple(chain[k][:3]) != (0, 0, 0):
-                redo = True
-            n_redo += int(redo)
-            if active:
-                c += int(g["n_tables"])
-                chain[k] = list(g["address"]) + [g["quantizer_step"]]
-            else:
-                exp["address"][u] = chain[k][:3]
-                exp["quantizer_step"][u] = chain[k][3]
-        assert int(so["cursor"][s]) == c, s
-        assert np.array_equal(so["chain"][s], chain), s
-        assert bool(so["carry_used"][s]) == used_carry, s
+    # the host walk (what csrc/mp3s_encode_pipeline.cpp's walk() does: tests/chain_model.py)
+    import chain_model
+    walked = chain_model.walk(before, rf, segs, cur)
+    for s, w in enumerate(walked):
+        assert int(so["cursor"][s]) == w["end_cursor"], s
+        assert np.array_equal(so["chain"][s], w["end_chain"]), s
+        assert bool(so["carry_used"][s]) == w["carry_used"], s
+    exp = np.concatenate([w["records"] for w in walked])
+    n_redo = sum(len(w["faulted"]) for w in walked)
     assert np.array_equal(after, exp)
     assert (before["flags"] & mlib.RF_ACTIVE == 0).sum() >= 40 * 4   # the silent stretches are really silent
     assert int(ver[0]) == n_redo and int(ver[1]) == 0
