@@ -186,7 +186,12 @@ int launch_wav_resample(hipStream_t stream, const uint32_t *d_rows, const WavRes
 int launch_wav_import(hipStream_t stream, const uint8_t *d_image, const WavImportRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 
-constexpr size_t kPlaceEntry = 4912;   // [int32 frame, pad to 16 | int16 is[2304] | mp3s_granule_si si[4]]
+// a frame the host decoded (the last frame of a stream: E14) on its way into the Huffman outputs: k_place_frames copies is / si to frame `frame`
+struct PlaceEntry { int32_t frame; int32_t pad[3]; int16_t is[2304]; mp3s_granule_si si[4]; };
+static_assert(sizeof(PlaceEntry) == 4912 && offsetof(PlaceEntry, is) == 16 && offsetof(PlaceEntry, si) == 16 + 4608, "k_place_frames copies dwords from byte 16 on");
+// the ONE way an entry is written on the host: its head, then decode(is, si) -> true: the entry is to be used
+template <class Decode>
+static inline bool fill_place_entry(PlaceEntry &e, int32_t frame, Decode &&decode) { e.frame = frame; e.pad[0] = e.pad[1] = e.pad[2] = 0; return decode(e.is, e.si); }
 int launch_place_frames(hipStream_t stream, const uint8_t *d_entries, int n_entries, int16_t *d_is, mp3s_granule_si *d_si);
 int launch_copy(hipStream_t stream, const void *d_src, void *d_dst, size_t bytes);
 // one wave that occupies its hardware queue for about `microseconds`; a kernel that does nothing

@@ -454,11 +454,11 @@ int launch_pcm_align(hipStream_t stream, const int16_t *d_pcm, int nch, const mp
 }
 
 // host-decoded frames (the asynchronous pipe decodes the last frame of every stream on the host: E14) into their places:
-// entry = [int32 frame, 12 bytes pad | int16 is[2304] | mp3s_granule_si si[4]] = 4912 bytes, one workgroup per entry
+// one workgroup per entry (PlaceEntry, mp3s_device.h)
 __global__ __launch_bounds__(256) void k_place_frames(const uint8_t *__restrict__ entries, int n_entries, int16_t *__restrict__ is,
                                                       mp3s_granule_si *__restrict__ si)
 {
-    const uint8_t *e = entries + (size_t)blockIdx.x * 4912;
+    const uint8_t *e = entries + (size_t)blockIdx.x * sizeof(PlaceEntry);
     const int f = *reinterpret_cast<const int32_t *>(e);
     const uint32_t *src = reinterpret_cast<const uint32_t *>(e + 16);
     uint32_t *d_is = reinterpret_cast<uint32_t *>(is + (size_t)f * 2304), *d_si = reinterpret_cast<uint32_t *>(si + (size_t)f * 4);

@@ -109,7 +109,7 @@ static bool enc_pool_buffers(mp3s_ctx *c, const EncLayout &L, bool want_pcm, boo
            (d.d_ix = (int16_t *)c->grab(kPoolIx, n * 2304 * 2)) && (d.d_out = (mp3s_gr_out *)c->grab(kPoolGrOut, units * sizeof(mp3s_gr_out))) &&
            (d.d_en = (int32_t *)c->grab(kPoolEnergy, units * 22 * 4)) && (d.d_agg = c->grab(kPoolChainAgg, chain_agg_bytes(L.n))) &&
            (!want_mp3 || ((d.d_mp3 = (uint8_t *)c->grab(kPoolMp3, L.mp3_bytes + 16)) && (d.d_sc = (int32_t *)c->grab(kPoolScfsi, n * 8 * 4)))) &&
-           (d.d_small = (int32_t *)c->grab(kPoolSmall, small_room));
+           (d.d_small = (SmallHead *)c->grab(kPoolSmall, small_room));
 }
 
 int enc_fill(std::vector<EncSeg> &segs, EncLayout &L, uint8_t *dst)
@@ -225,8 +225,8 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
     if (!rc) {
         // (with the device's own re-runs of the units that inherited other addresses than the zeros they were given)
         const ChainRedoArgs redo = {d_mdct, d_hide, L.n_hide, d.d_ix, d.d_en};
-        const int e = launch_chain(ts, d.d_out, d_rf, L.n, d_segs, d_cur, nullptr, d.d_agg, d.d_small,
-                                   (mp3s_chain_seg_out *)((uint8_t *)d.d_small + kSmallHead), &c->prof, !c->opt[MP3S_OPT_REDO] || !L.redo ? nullptr : &redo);
+        const int e = launch_chain(ts, d.d_out, d_rf, L.n, d_segs, d_cur, nullptr, d.d_agg, &d.d_small->redo_units,
+                                   small_seg_out(d.d_small), &c->prof, !c->opt[MP3S_OPT_REDO] || !L.redo ? nullptr : &redo);
         if (e) rc = fail(MP3S_E_HIP, "chain launch: %s", hipGetErrorString((hipError_t)e));
     }
     // a job without its tail: the streams are counted where they would have been packed (the same assumption about the verdict)
@@ -239,7 +239,7 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
         const bool halves = d.direct_status && d.pack_half && d.pack_split > 0 && d.pack_split < L.n;
         auto pack = [&](int32_t *d_sync, int f_begin, int f_end) {
             return launch_pack(ts, d.d_ix, d.d_out, d.d_en, L.n, L.sri, L.bri, L.whole, (const uint32_t *)(d.d_in + L.o_off), d.d_in + L.o_pad, d.d_mp3, d.d_sc,
-                               d.d_small + 2, d_sync, &c->prof, f_begin, f_end);
+                               &d.d_small->pack_status, d_sync, &c->prof, f_begin, f_end);
         };
         int e = pack(d.direct_status ? nullptr : c->d_sync, 0, halves ? d.pack_split : -1);
         if (!e && halves) e = hipEventRecord(d.pack_half, ts) != hipSuccess ? (int)hipErrorUnknown : pack(nullptr, d.pack_split, -1);
@@ -259,7 +259,7 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     const uint8_t *hide_all = in + L.o_hide;
     const uint8_t *const d_in = d.d_in;
     int16_t *const d_ix = d.d_ix; mp3s_gr_out *const d_out = d.d_out; int32_t *const d_en = d.d_en; uint8_t *const d_mp3 = d.d_mp3;
-    int32_t *const d_sc = d.d_sc, *const d_small = d.d_small;
+    int32_t *const d_sc = d.d_sc, *const d_pack_status = &d.d_small->pack_status;
     const int32_t *d_mdct = d.d_mdct_all + (size_t)L.lead * 2304;   // the block's own frames
     const mp3s_rate_frame *d_rf = (const mp3s_rate_frame *)(d_in + L.o_rf);
     const uint8_t *d_hide = d_in + L.o_hide;
@@ -472,9 +472,9 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     if (!rc) {
         // ---- bit packing again, on the final GrInfo
         rc = mp3s_dev_upload(c, d_out, gr, (size_t)units * sizeof(mp3s_gr_out));
-        if (!rc) rc = pack_step(c, c->stream, d_ix, d_out, d_en, n, L.sri, L.bri, L.whole, (const uint32_t *)(d_in + L.o_off), d_in + L.o_pad, d_mp3, d_sc, d_small + 2);
+        if (!rc) rc = pack_step(c, c->stream, d_ix, d_out, d_en, n, L.sri, L.bri, L.whole, (const uint32_t *)(d_in + L.o_off), d_in + L.o_pad, d_mp3, d_sc, d_pack_status);
         int32_t st = 0;
-        if (!rc) rc = mp3s_dev_download(c, &st, (int32_t *)d_small + 2, sizeof st);
+        if (!rc) rc = mp3s_dev_download(c, &st, d_pack_status, sizeof st);
         if (!rc && st) rc = fail(MP3S_E_HIP, "bit packer reported status %d", st);
         if (!rc) rc = mp3s_dev_download(c, b->mp3, d_mp3, total);
         if (!rc) rc = mp3s_dev_download(c, b->scfsi.data(), d_sc, (size_t)n * 8 * 4);
@@ -514,8 +514,7 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
         return fail(MP3S_E_NOMEM, "host memory for a %d-frame encode", n);
     }
     b->mp3 = b->big[0].data();
-    int32_t *const small = (int32_t *)b->big[2].data();
-    const mp3s_chain_seg_out *const seg_out = (const mp3s_chain_seg_out *)(b->big[2].data() + kSmallHead);
+    const SmallView small{b->big[2].data()};
     if (want_gr) b->scfsi.assign((size_t)n * 8, 0);
     // ---- one pass, nothing waited for in between: inputs up, transforms, rate loop on the guessed cursors, the chain
     //      check on the device, bit packing, results down.  The verdict says whether the guesses held.
@@ -526,7 +525,7 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     auto down = [&](void *dst, const void *src, size_t bytes) {
         if (!rc && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
     };
-    down(small, dev.d_small, small_bytes(L.n_segs));
+    down(b->big[2].data(), dev.d_small, small_bytes(L.n_segs));
     down(b->mp3, dev.d_mp3, total);
     if (want_gr) {
         down(b->big[1].data(), dev.d_out, (size_t)units * sizeof(mp3s_gr_out));
@@ -535,20 +534,18 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "sync failed");
     if (rc) { cleanup(); return rc; }
     if (want_gr) b->gr_out = (mp3s_gr_out *)b->big[1].data();
-    if (small[0] == 0 && small[1] == 0) {
-        if (small[2]) { cleanup(); return fail(MP3S_E_HIP, "bit packer reported status %d", small[2]); }
+    const SmallHead &head = small.head();
+    if (head.chains_settled()) {
+        if (!head.pack_clean()) { cleanup(); return fail(MP3S_E_HIP, "bit packer reported status %d", head.pack_status); }
         for (size_t si = 0; si < segs.size(); si++) {
-            EncSeg &s = segs[si];
-            s.hide_offset = seg_out[si].cursor - s.hide_base;
-            s.carry_out.cursor = s.hide_offset;
-            std::memcpy(s.carry_out.chain, seg_out[si].chain, sizeof s.carry_out.chain);
-            s.carry_used = seg_out[si].carry_used != 0;
+            const SegEnd e = seg_end(segs[si], small.seg_out(si), false);
+            segs[si].hide_offset = e.hide_offset; segs[si].carry_out = e.out; segs[si].carry_used = e.carry_used;
         }
         if (passes_out) *passes_out = 1;
         return MP3S_OK;
     }
     // ---- the guesses did not hold: resolve the chains on the host, as round 1 did
-    if (trace_on()) fprintf(stderr, "mp3s: encode of %d frames: %d units still to redo behind the device's re-runs (step range %d), %d variant entries, redo launches %d -> the host resolves\n", n, small[0], small[1], L.n_entries, (int)L.redo);
+    if (trace_on()) fprintf(stderr, "mp3s: encode of %d frames: %d units still to redo behind the device's re-runs (step range %d), %d variant entries, redo launches %d -> the host resolves\n", n, head.redo_units, head.step_range, L.n_entries, (int)L.redo);
     rc = enc_resolve(c, L, segs, in.data(), dev, b, want_gr, passes_out);
     cleanup();
     return rc;
@@ -582,8 +579,7 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
         return fail(MP3S_E_NOMEM, "host memory for a %d-frame encode", n);
     }
     uint8_t *const small8 = b->big[2].data();
-    const int32_t *const small = (const int32_t *)small8;
-    const mp3s_chain_seg_out *const seg_out = (const mp3s_chain_seg_out *)(small8 + kSmallHead);
+    const SmallView small{small8};
     if (hipMemcpyAsync(const_cast<uint8_t *>(dev.d_in), in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
     dev.d_pcm = pcm_dev;
     dev.d_cap = (mp3s_capacity_seg *)((uint8_t *)dev.d_small + o_cap);
@@ -594,11 +590,11 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "sync failed");
     if (rc) { cleanup(); return rc; }
     out->down_bytes = down_bytes;
-    if (small[0] != 0 || small[1] != 0) {
-        if (trace_on()) fprintf(stderr, "mp3s: capacity of %d frames: %d units still to redo (step range %d) -> the full encode counts\n", n, small[0], small[1]);
+    if (!small.head().chains_settled()) {
+        if (trace_on()) fprintf(stderr, "mp3s: capacity of %d frames: %d units still to redo (step range %d) -> the full encode counts\n", n, small.head().redo_units, small.head().step_range);
         return MP3S_OK;
     }
-    for (size_t si = 0; si < segs.size(); si++) segs[si].hide_offset = seg_out[si].cursor - segs[si].hide_base;
+    for (size_t si = 0; si < segs.size(); si++) segs[si].hide_offset = seg_end(segs[si], small.seg_out(si), false).hide_offset;
     out->counted = true;
     out->seg = (const mp3s_capacity_seg *)(small8 + o_cap);
     out->profile = want_profile ? (const uint32_t *)(small8 + o_prof) : nullptr;

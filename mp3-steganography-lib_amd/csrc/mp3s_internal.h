@@ -9,6 +9,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -496,9 +497,42 @@ struct EncLayout {
     size_t mp3_bytes = 0;          // all frames of the batch
     int64_t bytes_before = 0;      // size of the frames in front of a block (E14: the tail cut depends on it)
 };
-// small results of a batch, in one block: verdict[2] (mp3s_chain_resolve_dev), pack status, Huffman status, parse status, then seg_out[n_segs]
-constexpr size_t kSmallHead = 32;          // (word 4: status of the device-side parse, MP3S_PS_*; 5..7 spare)
-inline size_t small_bytes(int n_segs) { return kSmallHead + (size_t)n_segs * sizeof(mp3s_chain_seg_out); }
+// small results of a batch, in one block: this head, then mp3s_chain_seg_out[n_segs].  Every word is zero when all went well; the kernels
+// that own a word write or OR into it, the host only reads.
+struct SmallHead {
+    int32_t redo_units, step_range;                      // the chain check's verdict (mp3s_chain_resolve_dev: d_verdict[0], [1])
+    int32_t pack_status, huffman_status, parse_status;   // the bit packer's, the Huffman decode's, the device-side parse's (MP3S_PS_*)
+    int32_t spare[3];
+    bool chains_settled() const { return redo_units == 0 && step_range == 0; }
+    bool pack_clean() const { return pack_status == 0; }
+    bool huffman_clean() const { return huffman_status == 0; }
+    bool parse_clean() const { return (parse_status & kParseMismatch) == 0; }
+    bool inherits_across_frames() const { return (parse_status & kParseInherits) != 0; }
+    // final after the first pass: a decode job, a hide / clear / encode job (walked: the job's frames were parsed on the device)
+    bool decode_final(bool walked) const { return (!walked || parse_clean()) && huffman_clean(); }
+    bool encode_final(bool walked) const { return (!walked || parse_clean()) && chains_settled() && pack_clean() && huffman_clean(); }
+    // only the cursor / address guesses failed: the host can resolve the chains on the job's own device buffers
+    bool resolvable(bool walked) const { return (!walked || parse_clean()) && redo_units != 0 && step_range == 0 && huffman_clean(); }
+    bool all_clean() const { return chains_settled() && pack_clean() && huffman_clean() && parse_clean(); }   // no word says anything, whatever the job is
+};
+static_assert(sizeof(SmallHead) == 32 && offsetof(SmallHead, redo_units) == 0 && offsetof(SmallHead, step_range) == 4 && offsetof(SmallHead, pack_status) == 8 &&
+              offsetof(SmallHead, huffman_status) == 12 && offsetof(SmallHead, parse_status) == 16 && offsetof(SmallHead, spare) == 20, "the kernels are handed these words' addresses");
+inline size_t small_bytes(int n_segs) { return sizeof(SmallHead) + (size_t)n_segs * sizeof(mp3s_chain_seg_out); }
+inline mp3s_chain_seg_out *small_seg_out(SmallHead *head) { return reinterpret_cast<mp3s_chain_seg_out *>(head + 1); }   // (on the device: for the launchers)
+struct SmallView {   // a block that has come down
+    const uint8_t *block;
+    const SmallHead &head() const { return *reinterpret_cast<const SmallHead *>(block); }
+    const mp3s_chain_seg_out &seg_out(size_t i) const { return reinterpret_cast<const mp3s_chain_seg_out *>(block + sizeof(SmallHead))[i]; }
+};
+// How stream i of a batch ended: from the stream's record when the host resolved the chains (enc_resolve filled it), from the device's otherwise
+struct SegEnd { mp3s_carry out; bool carry_used; int64_t hide_offset; };
+inline SegEnd seg_end(const EncSeg &sg, const mp3s_chain_seg_out &so, bool resolved)
+{
+    if (resolved) return {sg.carry_out, sg.carry_used, sg.hide_offset};
+    SegEnd e = {{so.cursor - sg.hide_base, {}}, so.carry_used != 0, so.cursor - sg.hide_base};
+    std::memcpy(e.out.chain, so.chain, sizeof e.out.chain);
+    return e;
+}
 // checks the streams and fills first / hide_base of each
 int enc_layout(std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncLayout &L, bool select = true /* MP3S_OPT_SELECT */);
 // writes the block (L.bytes at dst); *mp3_off_len: per stream {offset, length} of its bytes in the batch's output
@@ -510,7 +544,7 @@ struct EncDev {
     int16_t *d_ix = nullptr; mp3s_gr_out *d_out = nullptr; int32_t *d_en = nullptr;
     void *d_agg = nullptr;               // chain_agg_bytes(n)
     uint8_t *d_mp3 = nullptr; int32_t *d_sc = nullptr;
-    int32_t *d_small = nullptr;          // small_bytes(n_segs)
+    SmallHead *d_small = nullptr;        // small_bytes(n_segs)
     bool direct_status = false;          // d_small's status words were zeroed with the job's inputs: the kernels OR into them directly
     // the bit packer in two launches, frames [0, pack_split) and the rest, pack_half recorded between them (the last chunk of a
     // one-file call: its first half comes down while the second is packed); 0: one launch
@@ -554,7 +588,7 @@ int select_step(mp3s_ctx *c, hipStream_t stream, const uint8_t *d_hide, int32_t 
 int pack_step(mp3s_ctx *c, hipStream_t stream, const int16_t *d_ix, const mp3s_gr_out *d_gr, const int32_t *d_en, int n_frames, int sri, int bri, int whole,
               const uint32_t *d_frame_off, const uint8_t *d_padding, uint8_t *d_mp3, int32_t *d_scfsi, int32_t *d_status);
 // transforms -> rate loop on the guessed cursors, on c->stream; selection -> chain check -> bit packing (with d.d_cap: k_capacity in its place) on `tail`, or on
-// c->stream without one; nothing waited for.  The packed bytes (the capacity records) are final iff verdict[0] == 0 and verdict[1] == 0 (d_small[0], d_small[1]).
+// c->stream without one; nothing waited for.  The packed bytes (the capacity records) are final iff d_small->chains_settled().
 int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail = nullptr /* ordered behind the rate loop through tail_from */,
               hipEvent_t tail_from = nullptr, hipEvent_t pcm_read = nullptr /* recorded behind the encode transforms: the PCM they read may be overwritten */);
 // verdict != 0: the host resolves the chains on the first pass's device buffers (walk, message variants, exact re-runs,

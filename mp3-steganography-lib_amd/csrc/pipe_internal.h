@@ -8,6 +8,7 @@
 #include <deque>
 
 #include "mp3s_internal.h"
+#include "pipe_pack.h"
 
 constexpr int kMaxFastFiles = 1024;
 constexpr uint32_t kImageLead = 1024;                 // bytes in front of a chunk's first frame its reservoir pointers can name (511 + 8 x 38)
@@ -25,7 +26,7 @@ struct Slot {
     uint8_t *d_wav = nullptr; size_t wav_cap = 0;
     uint8_t *h_wav = nullptr; size_t h_wav_cap = 0;      // page-locked, made and grown on need: short WAV files are laid end to end here first
     uint8_t *d_mp3 = nullptr; size_t mp3_cap = 0;
-    int32_t *d_small = nullptr;
+    SmallHead *d_small = nullptr;        // a scanned job's small results (a walked job brings its block with its inputs)
     // the encoder's intermediates of the slot's job (mdct, quantised lines, GrInfo, energies, scfsi): the slot's own, so
     // that a job whose cursor guess failed is resolved on them at collect time while later jobs have long been issued
     uint8_t *d_enc = nullptr; size_t enc_cap = 0;
@@ -48,21 +49,36 @@ struct Chunk {
     uint8_t *dst = nullptr;              // where the chunk's bytes go on the host (MP3 frames; PCM of a decode)
     const uint8_t *file = nullptr; size_t file_len = 0;
     uint32_t image_lo = 0, image_hi = 0; // the piece of the file that goes up
-    const uint8_t *fix = nullptr;        // kPlaceEntry bytes: the stream's last frame decoded on the host (index in the window filled in here), or null
+    const PlaceEntry *fix = nullptr;     // the stream's last frame decoded on the host (its index in the window is filled in by prepare_chunk), or null
     const uint8_t *tables = nullptr; int n_tables = 0; int any_silent = -1;   // the walk's table counts for the chunk's own units
     const uint8_t *hide = nullptr; int n_hide = 0;
     int rate = 0, kbps = 0, nch = 2;
     bool decode = false;
 };
 
+// frames [first, first + count) of a walked stream as a chunk: its window with the lead and halo in front, the piece of the file it reads
+static inline void chunk_window(Chunk &k, const FrameRef *refs, long first, long count, bool last, const uint8_t *file, size_t len)
+{
+    k.on = true; k.refs = refs; k.first = first; k.count = count; k.last = last; k.file = file; k.file_len = len;
+    k.lead = !k.decode && first > 0 ? 1 : 0;
+    k.halo = first - k.lead > 0 ? 1 : 0;
+    k.w0 = first - k.lead - k.halo; k.n_win = count + k.lead + k.halo;
+    const uint32_t lo = refs[(size_t)k.w0].file_off;
+    k.image_lo = first == 0 ? 0 : (lo > kImageLead ? lo - kImageLead : 0);
+    const FrameRef &lr = refs[(size_t)(first + count - 1)];
+    k.image_hi = (uint32_t)std::min<uint64_t>(len, (uint64_t)lr.file_off + lr.frame_size + 64);
+}
+
 struct Job {
     int64_t ticket = 0;
     int slot = -1;
     std::vector<std::pair<const uint8_t *, size_t>> files, msgs;   // borrowed until the job is collected
     bool clear_all = false;
-    bool decode = false;                 // MP3 -> WAV (int16) instead of hide / clear
-    // WAV -> MP3 (mp3s_pipe_submit_encode): files = the WAV images, msgs = per file {hide bits, their count}, enc_kbps per file
-    bool encode = false, enc_hide = false;
+    // HIDE: hide / clear (also a chunk of a one-file call); DECODE: MP3 -> WAV (int16); ENCODE: WAV -> MP3 (mp3s_pipe_submit_encode: files = the
+    // WAV images, msgs = per file {hide bits, their count}, enc_kbps per file); BLOCK: one rank's share of a stream (mp3s_pipe_submit_block)
+    enum Kind { HIDE, DECODE, ENCODE, BLOCK } kind = HIDE;
+    bool decode() const { return kind == DECODE; }
+    bool enc_hide = false;
     std::vector<int32_t> enc_kbps;
     WavBatch wav;                        // the files' places in the slot's d_wav, the kernels' records (inside the packed inputs) and grids
     enum State { QUEUED, ISSUED, SLOW_DONE } state = QUEUED;
@@ -96,15 +112,13 @@ struct Job {
     // decode jobs: per file the frames, rows, header fields, where its WAV starts in the result block, its stego bits
     struct DecFile { int n_frames, nch, rate, bit_rate; size_t wav_off, bits_off, n_bits; long first; };
     std::vector<DecFile> dec;
-    std::vector<uint8_t> res_bits;
     int nch = 2, n_total = 0, max_p23 = 0;
     Chunk ck;
-    // block jobs (mp3s_pipe_submit_block): one rank's share of a stream
-    bool block = false;
+    // block jobs
     int rank = 0, world = 1;
     bool has_carry = false; mp3s_carry carry = {};
     std::vector<FrameRef> refs;          // the stream's frames as walked (ck.refs points here)
-    std::vector<uint8_t> fix;            // its last frame decoded on the host (kPlaceEntry bytes), if that is needed
+    std::unique_ptr<PlaceEntry> fix;     // its last frame decoded on the host, if that is needed
     mp3s_block blk = {};                 // what the caller gets
     mp3s_buf *blk_owner = nullptr;       // ... from the synchronous path
 };
@@ -128,13 +142,6 @@ struct FileUp {
     mp3s_frame_side *d_side = nullptr; size_t side_cap = 0 /* frames */;
     uint8_t *d_blob = nullptr; size_t blob_cap = 0;
     bool active = false;                 // the call in progress reads its file from d_file
-};
-
-struct WalkOut {                         // the walker's state behind a chunk of a one-file call
-    long got = 0;
-    bool ended = false, irregular = false, dup_last = false, any_silent = false, have_fix = false;
-    int nch = 0, sampling_rate = 0, bit_rate = 0, max_p23 = 0;
-    long tables_frames = 0;
 };
 
 // what choosing a pipe's streams took and found (mp3s_pipe_stats / mp3s_run_stats hand it out)

@@ -45,49 +45,85 @@ int reencode_params(int sampling_rate, int bit_rate, int nch, long n_frames, int
 
 namespace {
 
-// the result block of a decode job: per file a WAV image, its PCM 64 bytes into an aligned region, the 44-byte header right
-// in front of it (what mp3s_decode_file hands out)
-bool decode_result(Job &j)
+// ---- what the preparers share.  Each starts here: nothing of an earlier attempt at the job (the walk, then the scan) is left; false: too many files
+bool job_begin(Job &j, int n_files, bool walked)
 {
-    size_t off = 0;
+    if (n_files > kMaxFastFiles) return false;
+    j.walked = walked;
+    j.segs.assign((size_t)n_files, EncSeg()); j.bits.assign((size_t)n_files, {}); j.guess.assign((size_t)n_files, {});
+    j.stream_first.assign((size_t)n_files, 0);
+    j.dec.clear(); j.ups.clear();
+    j.n_fix = 0; j.image_base = 0; j.md_base = 0; j.L = EncLayout();
+    return true;
+}
+
+// A job is one device batch, and a batch takes one class of streams: a decode job one channel count; every other job stereo streams the encoder
+// takes (reencode_params), of one (rate, bitrate).  Stream 0 sets the class (j.nch, or j.rate and j.kbps).
+bool admit_stream(Job &j, int i, int nch, int sampling_rate, int bit_rate, long n_frames, bool dup_last)
+{
+    if (j.decode()) {
+        if (i == 0) j.nch = nch;
+        return n_frames > 0 && !dup_last && nch >= 1 && nch <= 2 && nch == j.nch;
+    }
+    int kbps = 0;
+    if (reencode_params(sampling_rate, bit_rate, nch, n_frames, dup_last ? 1 : 0, &kbps)) return false;
+    if (i == 0) { j.rate = sampling_rate; j.kbps = kbps; }
+    return sampling_rate == j.rate && kbps == j.kbps;
+}
+
+// file i's message as the bits the encoder hides -> j.bits[i]; false: more than `limit` of them
+bool frame_message(Job &j, size_t i, size_t limit) { message_frame(j.msgs[i].first, j.msgs[i].second, j.bits[i]); return j.bits[i].size() <= limit; }
+
+// The result block of a list job: the batch's MP3 frames (j.L) and its small results -- or, of a decode job, per file of j.dec a WAV image (PCM 64 bytes into an aligned
+// region, the 44-byte header right in front of it: what mp3s_decode_file hands out), the head of the small results and, for a walked job, the table-index words of the stego bits
+bool reserve_results(Job &j)
+{
+    size_t bytes = j.decode() ? 0 : j.L.mp3_bytes;
     for (auto &d : j.dec) {
-        d.wav_off = off + 64 - 44;
-        off += 64 + (((size_t)d.n_frames * 1152 * d.nch * 2 + 63) & ~(size_t)63);
+        d.wav_off = bytes + 64 - 44;
+        bytes += 64 + (((size_t)d.n_frames * 1152 * d.nch * 2 + 63) & ~(size_t)63);
     }
     j.res.reset(new mp3s_buf());
-    if (!j.res->big[0].reserve(off) || !j.res->big[2].reserve(small_bytes(1))) return false;
-    if (j.walked && !j.res->big[1].reserve((size_t)j.n_total * 8 + 16)) return false;   // the table-index words the stego bits are made of
+    if (!j.res->big[0].reserve(bytes) || !j.res->big[2].reserve(small_bytes(j.decode() ? 1 : j.L.n_segs))) return false;
+    if (j.decode() && j.walked && !j.res->big[1].reserve((size_t)j.n_total * 8 + 16)) return false;
     j.res->mp3 = j.res->big[0].data();
     for (const auto &d : j.dec) wav_header((int64_t)d.n_frames * 1152, d.nch, d.rate, j.res->mp3 + d.wav_off);
     return true;
 }
 
-bool encode_inputs(Job &j, Slot &s, uint8_t *encblk, size_t room, bool select)
+// the encoder's inputs of the job's streams, laid out (j.L) and written at o_encblk of the stage, where `room` bytes are free
+bool encode_inputs(mp3s_pipe *P, Job &j, Slot &s, size_t room)
 {
-    if (enc_layout(j.segs, j.rate, j.kbps, j.L, select)) return false;
-    if (j.L.bytes > room) return false;
-    if (enc_fill(j.segs, j.L, encblk)) return false;
-    if (j.L.mp3_bytes + 16 > s.mp3_cap) return false;
-    return true;
+    return !enc_layout(j.segs, j.rate, j.kbps, j.L, P->c->opt[MP3S_OPT_SELECT] != 0) && j.L.bytes <= room && !enc_fill(j.segs, j.L, s.h_stage + j.o_encblk) &&
+           j.L.mp3_bytes + 16 <= s.mp3_cap;
 }
 
-// ---- the walk: frame table + what the encoder needs of every stream, packed [encoder inputs | host-decoded frames | refs |
-//      streams] behind o_in; false = not for this path (the byte-level scan, or the synchronous path, takes the job)
+// The front of a list job's packed area, [small results, head zeroed | encoder inputs (a decode job has none)], and the job's result block.
+// The inputs end at in_cap: behind it the walk has parked the parts that follow them.
+bool pack_front(mp3s_pipe *P, Job &j, Slot &s, StagePacker &pk, int n_small)
+{
+    pk.begin(s.o_in, s.o_in + s.pack_cap);
+    j.o_small = pk.add(small_bytes(n_small));
+    std::memset(s.h_stage + j.o_small, 0, sizeof(SmallHead));
+    j.o_encblk = pk.add(0);
+    if (j.decode()) return reserve_results(j);
+    const size_t in_end = s.o_in + s.in_cap;
+    if (j.o_encblk >= in_end || !encode_inputs(P, j, s, in_end - j.o_encblk)) return false;
+    pk.add(j.L.bytes);
+    return reserve_results(j);
+}
+
+// ---- the walk: frame table + what the encoder needs of every stream, packed [small | encoder inputs | host-decoded frames | refs |
+//      streams] from o_in; false = not for this path (the byte-level scan, or the synchronous path, takes the job)
 bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
 {
     const int nf = (int)j.files.size();
-    if (nf > kMaxFastFiles) return false;
-    j.walked = true;
-    j.segs.assign((size_t)nf, EncSeg());
-    j.bits.assign((size_t)nf, {});
-    j.guess.assign((size_t)nf, {});
-    j.dec.clear(); j.res_bits.clear(); j.ups.clear(); j.stream_first.assign((size_t)nf, 0);
-    j.n_fix = 0; j.image_base = 0; j.md_base = 0;
-    // refs and streams are written at the END of the packed area first (their place depends on the encoder block's size) and
-    // moved down once that is known; room for them is what the packed area has behind in_cap
-    FrameRef *refs = reinterpret_cast<FrameRef *>(s.h_stage + s.o_in + s.in_cap + s.fix_cap * kPlaceEntry);
-    StreamRef *streams = reinterpret_cast<StreamRef *>(reinterpret_cast<uint8_t *>(refs) + s.side_cap * sizeof(FrameRef));
-    uint8_t *fix = s.h_stage + s.o_in + s.in_cap;
+    if (!job_begin(j, nf, true)) return false;
+    // host-decoded frames, refs and streams are written at the END of the packed area first (their place depends on the encoder block's size)
+    // and moved down once that is known; room for them is what the packed area has behind in_cap
+    PlaceEntry *fix = reinterpret_cast<PlaceEntry *>(s.h_stage + s.o_in + s.in_cap);
+    FrameRef *refs = reinterpret_cast<FrameRef *>(fix + s.fix_cap);
+    StreamRef *streams = reinterpret_cast<StreamRef *>(refs + s.side_cap);
     long n = 0;
     size_t img = 0;                  // bytes of d_image in use
     std::vector<Upload> lay;         // every file's place in the image
@@ -103,10 +139,9 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
         FrameWalker w;
         if (w.open(file, len)) return false;
         w.md_cursor = md;
-        const bool hiding = !j.decode && !j.clear_all && j.msgs[i].first;
+        const bool hiding = !j.decode() && !j.clear_all && j.msgs[i].first;
         if (hiding) {
-            message_frame(j.msgs[i].first, j.msgs[i].second, j.bits[i]);
-            if (j.bits[i].size() > 0x7fffffff) return false;
+            if (!frame_message(j, i, 0x7fffffff)) return false;
             w.tables_wanted = (long)j.bits[i].size() + (long)j.bits[i].size() / 16 + 64;
             j.guess[i].resize((len / 96 + 16) * 4);     // (a silence offers no tables: the counting may go on for the whole file)
         }
@@ -119,17 +154,8 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
             got += w.next(refs + n + got, cap, tb, (uint32_t)img, (uint16_t)i);
         }
         if (w.irregular || got <= 0) return false;
-        if (j.decode) {
-            if (w.dup_last || w.nch < 1 || w.nch > 2) return false;
-            if (i == 0) j.nch = w.nch;
-            else if (w.nch != j.nch) return false;        // one device batch per channel count
-            j.dec.push_back({(int)got, w.nch, w.sampling_rate, w.bit_rate, 0, 0, 0, n});
-        } else {
-            int kbps = 0;
-            if (reencode_params(w.sampling_rate, w.bit_rate, w.nch, got, w.dup_last ? 1 : 0, &kbps)) return false;
-            if (i == 0) { j.rate = w.sampling_rate; j.kbps = kbps; }
-            else if (w.sampling_rate != j.rate || kbps != j.kbps) return false;   // more than one device batch
-        }
+        if (!admit_stream(j, i, w.nch, w.sampling_rate, w.bit_rate, got, w.dup_last)) return false;
+        if (j.decode()) j.dec.push_back({(int)got, w.nch, w.sampling_rate, w.bit_rate, 0, 0, 0, n});
         StreamRef &sr = streams[i];
         std::memset(&sr, 0, sizeof sr);
         sr.base = (uint32_t)img; sr.end = (uint32_t)(img + len); sr.first_frame = (uint32_t)n; sr.n_frames = (uint32_t)got;
@@ -141,15 +167,9 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
         // cheap on the host, so it is decoded here, the kernel skips it, and its samples are placed behind the kernel --
         // unless it inherits scalefactors from earlier frames (then the kernel's walk back through the stream has the answer).
         if ((size_t)j.n_fix >= s.fix_cap) return false;
-        {
-            uint8_t *e = fix + (size_t)j.n_fix * kPlaceEntry;
-            bool alone = false;
-            std::memset(e, 0, 16);
-            *reinterpret_cast<int32_t *>(e) = (int32_t)(n + got - 1);
-            if (w.decode_last(reinterpret_cast<int16_t *>(e + 16), reinterpret_cast<mp3s_granule_si *>(e + 16 + 4608), &alone) == 0 && alone) {
-                refs[n + got - 1].flags |= MP3S_FS_HOST_DECODED;
-                j.n_fix++;
-            }
+        if (fill_place_entry(fix[j.n_fix], (int32_t)(n + got - 1), [&](int16_t *is, mp3s_granule_si *si) { bool alone = false; return w.decode_last(is, si, &alone) == 0 && alone; })) {
+            refs[n + got - 1].flags |= MP3S_FS_HOST_DECODED;
+            j.n_fix++;
         }
         j.segs[i].n_frames = (int)got;
         if (hiding) {
@@ -169,33 +189,19 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
             return s.h_image;
         }, j.ups)) return false;
     j.n_total = (int)n;
-    j.L = EncLayout();
     j.max_p23 = max_p23;
-    size_t enc_bytes = 0;
-    // pack: [small results, zeroed | encoder inputs | host-decoded frames | refs | streams], one copy up
-    j.o_small = s.o_in;
-    const size_t small_room = up16(small_bytes(j.decode ? 1 : nf));
-    std::memset(s.h_stage + j.o_small, 0, kSmallHead);
-    j.o_encblk = j.o_small + small_room;
-    if (j.decode) {
-        if (!decode_result(j)) return false;
-    } else {
-        if (small_room >= s.in_cap || !encode_inputs(j, s, s.h_stage + j.o_encblk, s.in_cap - small_room, P->c->opt[MP3S_OPT_SELECT] != 0)) return false;
-        enc_bytes = j.L.bytes;
-        j.res.reset(new mp3s_buf());
-        if (!j.res->big[0].reserve(j.L.mp3_bytes) || !j.res->big[2].reserve(small_bytes(j.L.n_segs))) return false;
-        j.res->mp3 = j.res->big[0].data();
-    }
-    if (trace_on() && !j.decode) fprintf(stderr, "mp3s:   walk job %lld: %d stream(s), redo launches %d, variant entries %d, first stream: any_silent %d, tables known for %d units, reach %d\n",
+    StagePacker pk;
+    if (!pack_front(P, j, s, pk, j.decode() ? 1 : nf)) return false;
+    if (trace_on() && !j.decode()) fprintf(stderr, "mp3s:   walk job %lld: %d stream(s), redo launches %d, variant entries %d, first stream: any_silent %d, tables known for %d units, reach %d\n",
                                          (long long)j.ticket, nf, (int)j.L.redo, j.L.n_entries, j.segs[0].any_silent, j.segs[0].n_guess, j.segs[0].reach);
-    j.o_fix = up16(j.o_encblk + enc_bytes);
-    if (j.o_fix != s.o_in + s.in_cap) std::memmove(s.h_stage + j.o_fix, fix, (size_t)j.n_fix * kPlaceEntry);
-    j.o_refs = up16(j.o_fix + (size_t)j.n_fix * kPlaceEntry);
+    j.o_fix = pk.add((size_t)j.n_fix * sizeof(PlaceEntry));
+    j.o_refs = pk.add((size_t)n * sizeof(FrameRef));
+    j.o_streams = pk.add((size_t)nf * sizeof(StreamRef));
+    j.pack_end = pk.end();
+    if (!pk.ok) return false;
+    if (j.o_fix != s.o_in + s.in_cap) std::memmove(s.h_stage + j.o_fix, fix, (size_t)j.n_fix * sizeof(PlaceEntry));
     std::memmove(s.h_stage + j.o_refs, refs, (size_t)n * sizeof(FrameRef));
-    j.o_streams = up16(j.o_refs + (size_t)n * sizeof(FrameRef));
     std::memmove(s.h_stage + j.o_streams, streams, (size_t)nf * sizeof(StreamRef));
-    j.pack_end = j.o_streams + (size_t)nf * sizeof(StreamRef);
-    j.ck.on = false;
     return true;
 }
 
@@ -204,10 +210,8 @@ bool prepare_walk(mp3s_pipe *P, Job &j, Slot &s)
 bool prepare_chunk(mp3s_pipe *P, Job &j, Slot &s, int max_p23)
 {
     Chunk &k = j.ck;
-    j.walked = true; j.decode = k.decode; j.clear_all = k.n_hide == 0;
-    j.segs.assign(1, EncSeg());
-    j.dec.clear(); j.ups.clear(); j.stream_first.assign(1, 0);
-    j.n_fix = 0;
+    (void)job_begin(j, 1, true);
+    if (k.decode) j.kind = Job::DECODE;          // (a chunk of a one-file decode; a hide chunk and a block job keep what they are)
     j.n_total = (int)k.n_win; j.nch = k.nch; j.rate = k.rate; j.kbps = k.kbps;
     const bool on_device = P->up.active;
     if ((size_t)k.n_win > s.side_cap || (!on_device && k.image_hi - k.image_lo + 64 > s.image_cap)) return false;
@@ -219,35 +223,36 @@ bool prepare_chunk(mp3s_pipe *P, Job &j, Slot &s, int max_p23)
     j.d_file = on_device ? P->up.d_file : nullptr; j.file_need = k.image_hi;
     if (!j.file_wide && (size_t)lastr.md_off - j.md_base + lastr.md_len + 64 > s.blob_cap) return false;
     if (!on_device) j.ups.push_back({0, k.file + k.image_lo, (size_t)(k.image_hi - k.image_lo)});
-    j.L = EncLayout();
-    // packed [small results | host-decoded frame | refs | stream | encoder inputs]: what the front end reads comes first and goes
+    // packed [small results | host-decoded frame | refs | stream || encoder inputs]: what the front end reads comes first and goes
     // up first -- the encoder's inputs are laid out (prepare_chunk_encode) while parse and Huffman kernels already run
-    j.o_small = s.o_in;
-    std::memset(s.h_stage + j.o_small, 0, kSmallHead);
+    if (k.fix && s.fix_cap < 1) return false;
+    j.n_fix = k.fix ? 1 : 0;
+    StagePacker pk;
+    pk.begin(s.o_in, s.o_in + s.pack_cap);
+    j.o_small = pk.add(small_bytes(1));
+    j.o_fix = pk.add((size_t)j.n_fix * sizeof(PlaceEntry));
+    j.o_refs = pk.add((size_t)k.n_win * sizeof(FrameRef));
+    j.o_streams = pk.add(sizeof(StreamRef));
+    j.o_encblk = j.front_end = j.pack_end = pk.add(0);
+    if (!pk.ok) return false;
+    std::memset(s.h_stage + j.o_small, 0, sizeof(SmallHead));
     j.res.reset(new mp3s_buf());
     if (!j.res->big[2].reserve(small_bytes(1))) return false;
     if (k.decode && !j.res->big[1].reserve((size_t)k.n_win * 8 + 16)) return false;
-    j.o_fix = j.o_small + up16(small_bytes(1));
     if (k.fix) {
-        if (s.fix_cap < 1) return false;
-        std::memcpy(s.h_stage + j.o_fix, k.fix, kPlaceEntry);
-        *reinterpret_cast<int32_t *>(s.h_stage + j.o_fix) = (int32_t)(k.n_win - 1);
-        j.n_fix = 1;
+        PlaceEntry *e = reinterpret_cast<PlaceEntry *>(s.h_stage + j.o_fix);
+        *e = *k.fix;
+        e->frame = (int32_t)(k.n_win - 1);
     }
-    j.o_refs = up16(j.o_fix + (size_t)j.n_fix * kPlaceEntry);
     FrameRef *refs = reinterpret_cast<FrameRef *>(s.h_stage + j.o_refs);
     std::memcpy(refs, k.refs + k.w0, (size_t)k.n_win * sizeof(FrameRef));
     for (long f = 0; f < k.n_win; f++) { refs[f].stream = 0; refs[f].flags = 0; }
     if (k.fix) refs[k.n_win - 1].flags = MP3S_FS_HOST_DECODED;
-    j.o_streams = up16(j.o_refs + (size_t)k.n_win * sizeof(FrameRef));
     StreamRef *sr = reinterpret_cast<StreamRef *>(s.h_stage + j.o_streams);
     std::memset(sr, 0, sizeof *sr);
     sr->base = 0; sr->end = (uint32_t)k.file_len; sr->first_frame = 0; sr->n_frames = (uint32_t)k.n_win;
     if (j.file_wide) { sr->side_back[0] = (uint16_t)((uint32_t)k.w0 & 0xffffu); sr->side_back[1] = (uint16_t)((uint32_t)k.w0 >> 16); }
     FrameWalker::history(k.refs, k.w0, sr->prev_size);
-    j.o_encblk = up16(j.o_streams + sizeof(StreamRef));
-    j.front_end = j.pack_end = j.o_encblk;
-    if (j.pack_end > s.o_in + s.pack_cap) return false;
     j.max_p23 = max_p23;
     return true;
 }
@@ -261,9 +266,9 @@ bool prepare_chunk_encode(mp3s_pipe *P, Job &j, Slot &s)
     sg.n_frames = (int)k.count; sg.hide = k.hide; sg.n_hide = k.n_hide;
     sg.lead = k.lead; sg.first_frame = k.first; sg.last = k.last; sg.carry_in = k.has_carry ? &k.carry_in : nullptr;
     sg.tables_guess = k.tables; sg.n_guess = k.tables ? k.n_tables : -1; sg.any_silent = k.any_silent;
-    if (!encode_inputs(j, s, s.h_stage + j.o_encblk, s.o_in + s.pack_cap - j.o_encblk, P->c->opt[MP3S_OPT_SELECT] != 0)) return false;
+    if (!encode_inputs(P, j, s, s.o_in + s.pack_cap - j.o_encblk)) return false;
     j.pack_end = j.o_encblk + j.L.bytes;
-    return j.pack_end <= s.o_in + s.pack_cap;
+    return true;
 }
 
 namespace {
@@ -274,42 +279,32 @@ bool prepare_block(mp3s_pipe *P, Job &j, Slot &s)
     const uint8_t *file = j.files[0].first;
     const size_t len = j.files[0].second;
     if (!file || len > 0xffff0000ull) return false;
-    j.bits.assign(1, {});
-    if (j.msgs[0].first) {
-        message_frame(j.msgs[0].first, j.msgs[0].second, j.bits[0]);
-        if (j.bits[0].size() > 0x3fffff00) return false;
-    }
     FrameWalker w;
     const long n = walk_whole(file, len, j.refs, w);
     if (n <= 0 || w.dup_last) return false;
-    int kbps = 0;
-    if (reencode_params(w.sampling_rate, w.bit_rate, w.nch, n, 0, &kbps)) return false;
+    if (!admit_stream(j, 0, w.nch, w.sampling_rate, w.bit_rate, n, false)) return false;
     const long base = n / j.world, rem = n % j.world;
     const long first = j.rank * base + std::min<long>(j.rank, rem), count = base + (j.rank < rem ? 1 : 0);
     std::memset(&j.blk, 0, sizeof j.blk);
     j.blk.total_frames = n; j.blk.first_frame = first; j.blk.n_frames = count; j.blk.is_last = first + count == n;
-    j.blk.file.kbps = kbps; j.blk.file.sampling_rate = w.sampling_rate; j.blk.file.channels = 2;
+    j.blk.file.kbps = j.kbps; j.blk.file.sampling_rate = w.sampling_rate; j.blk.file.channels = 2;
     if (count <= 0 || count > kDecodeChunk - 2) return false;    // (an empty share, or one longer than a transform group: the synchronous path)
     if ((first == 0) != !j.has_carry) return false;
     Chunk &k = j.ck;
     k = Chunk();
-    k.on = true; k.decode = false; k.refs = j.refs.data(); k.first = first; k.count = count; k.last = j.blk.is_last != 0;
-    k.lead = first > 0 ? 1 : 0; k.halo = first - k.lead > 0 ? 1 : 0;
-    k.w0 = first - k.lead - k.halo; k.n_win = count + k.lead + k.halo;
-    k.file = file; k.file_len = len; k.rate = w.sampling_rate; k.kbps = kbps; k.nch = 2;
-    const uint32_t lo = j.refs[(size_t)k.w0].file_off;
-    k.image_lo = first == 0 ? 0 : (lo > kImageLead ? lo - kImageLead : 0);
-    const FrameRef &lr = j.refs[(size_t)(first + count - 1)];
-    k.image_hi = (uint32_t)std::min<uint64_t>(len, (uint64_t)lr.file_off + lr.frame_size + 64);
+    chunk_window(k, j.refs.data(), first, count, j.blk.is_last != 0, file, len);
+    k.rate = w.sampling_rate; k.kbps = j.kbps; k.nch = 2;
     if (k.last) {
-        j.fix.assign(kPlaceEntry, 0);
-        bool alone = false;
-        if (w.decode_last(reinterpret_cast<int16_t *>(j.fix.data() + 16), reinterpret_cast<mp3s_granule_si *>(j.fix.data() + 16 + 4608), &alone) == 0 && alone) k.fix = j.fix.data();
+        j.fix.reset(new PlaceEntry());
+        if (fill_place_entry(*j.fix, 0, [&](int16_t *is, mp3s_granule_si *si) { bool alone = false; return w.decode_last(is, si, &alone) == 0 && alone; })) k.fix = j.fix.get();
     }
-    k.hide = j.bits[0].data(); k.n_hide = (int)j.bits[0].size();
     k.has_carry = j.has_carry; k.carry_in = j.carry;
     k.any_silent = w.any_silent ? 1 : 0;
-    if (!prepare_chunk(P, j, s, w.max_p23) || !prepare_chunk_encode(P, j, s)) return false;
+    // (the message is framed behind prepare_chunk, which begins the job: prepare_chunk_encode is the first to look at it)
+    if (!prepare_chunk(P, j, s, w.max_p23)) return false;
+    if (j.msgs[0].first && !frame_message(j, 0, 0x3fffff00)) return false;
+    k.hide = j.bits[0].data(); k.n_hide = (int)j.bits[0].size();
+    if (!prepare_chunk_encode(P, j, s)) return false;
     if (!j.res->big[0].reserve(j.L.mp3_bytes + 16)) return false;
     j.res->mp3 = j.res->big[0].data();
     j.ck.dst = j.res->mp3;
@@ -321,38 +316,25 @@ bool prepare_block(mp3s_pipe *P, Job &j, Slot &s)
 bool prepare_fast(mp3s_pipe *P, Job &j, Slot &s, ParsedStream &p, size_t *blob_len, int *max_p23)
 {
     const int nf = (int)j.files.size();
-    if (nf > kMaxFastFiles) return false;
-    j.walked = false; j.ck.on = false;
+    if (!job_begin(j, nf, false)) return false;
     mp3s_frame_side *side = (mp3s_frame_side *)(s.h_stage + s.o_side);
-    uint8_t *in = s.h_stage + s.o_in;
     size_t base = 0;
     long n = 0;
-    j.segs.assign((size_t)nf, EncSeg());
-    j.bits.assign((size_t)nf, {});
-    j.guess.assign((size_t)nf, {});
-    j.stream_first.assign((size_t)nf, 0);
-    j.n_fix = 0;
-    j.dec.clear(); j.res_bits.clear(); j.ups.clear();
-    mp3s_frame_hdr *dechdr = (mp3s_frame_hdr *)in;      // the input block starts with the decoder's frame headers
+    PlaceEntry *fix = reinterpret_cast<PlaceEntry *>(s.h_stage + s.o_in + s.in_cap);      // the slot's own place for them (j.o_fix)
+    std::vector<uint8_t> res_bits;                       // a decode job's stego bits, file after file
+    mp3s_frame_hdr *dechdr = (mp3s_frame_hdr *)(s.h_stage + s.o_in);     // the input block starts with the decoder's frame headers
     for (int i = 0; i < nf; i++) {
         if (!j.files[i].first) return false;
         ScanSink k;
         k.blob = s.h_stage + base; k.blob_cap = s.blob_cap - base;
         k.side = side + n; k.side_cap = s.side_cap - (size_t)n;
         k.hdr = dechdr + n;
-        k.lean = !j.decode;                              // a decode job hands out the stego bits too
+        k.lean = !j.decode();                            // a decode job hands out the stego bits too
         if (parse_stream_sink(j.files[i].first, j.files[i].second, p, &k)) return false;
-        if (j.decode) {
-            if (p.n_frames <= 0 || p.dup_last_frame || p.nch < 1 || p.nch > 2) return false;
-            if (i == 0) j.nch = p.nch;
-            else if (p.nch != j.nch) return false;        // one device batch per channel count
-            j.dec.push_back({p.n_frames, p.nch, p.sampling_rate, p.bit_rate, 0, j.res_bits.size(), p.bits.size(), n});
-            j.res_bits.insert(j.res_bits.end(), p.bits.begin(), p.bits.end());
-        } else {
-            int kbps = 0;
-            if (reencode_params(p.sampling_rate, p.bit_rate, p.nch, p.n_frames, p.dup_last_frame, &kbps)) return false;
-            if (i == 0) { j.rate = p.sampling_rate; j.kbps = kbps; }
-            else if (p.sampling_rate != j.rate || kbps != j.kbps) return false;   // more than one device batch
+        if (!admit_stream(j, i, p.nch, p.sampling_rate, p.bit_rate, p.n_frames, p.dup_last_frame != 0)) return false;
+        if (j.decode()) {
+            j.dec.push_back({p.n_frames, p.nch, p.sampling_rate, p.bit_rate, 0, res_bits.size(), p.bits.size(), n});
+            res_bits.insert(res_bits.end(), p.bits.begin(), p.bits.end());
         }
         j.stream_first[(size_t)i] = (uint32_t)n;
         for (int f = 0; f < p.n_frames; f++) {
@@ -363,18 +345,14 @@ bool prepare_fast(mp3s_pipe *P, Job &j, Slot &s, ParsedStream &p, size_t *blob_l
         *max_p23 = std::max(*max_p23, max_part2_3(side + n, p.n_frames));
         if (k.gpu_ok) {   // (a frame of a stream with inherited scalefactors cannot be decoded on its own; E14: see prepare_walk)
             if ((size_t)j.n_fix >= s.fix_cap) return false;
-            uint8_t *e = s.h_stage + s.o_in + s.in_cap + (size_t)j.n_fix * kPlaceEntry;
             mp3s_frame_side &last = side[n + p.n_frames - 1];
-            std::memset(e, 0, 16);
-            *reinterpret_cast<int32_t *>(e) = (int32_t)(n + p.n_frames - 1);
-            if (parse_scanned_frame(last, s.h_stage, reinterpret_cast<int16_t *>(e + 16), reinterpret_cast<mp3s_granule_si *>(e + 16 + 4608))) return false;
+            if (!fill_place_entry(fix[j.n_fix], (int32_t)(n + p.n_frames - 1), [&](int16_t *is, mp3s_granule_si *si) { return parse_scanned_frame(last, s.h_stage, is, si) == 0; })) return false;
             last.flags |= MP3S_FS_HOST_DECODED;
             j.n_fix++;
         }
         j.segs[i].n_frames = p.n_frames;
-        if (!j.decode && !j.clear_all && j.msgs[i].first) {
-            message_frame(j.msgs[i].first, j.msgs[i].second, j.bits[i]);
-            if (j.bits[i].size() > 0x7fffffff) return false;
+        if (!j.decode() && !j.clear_all && j.msgs[i].first) {
+            if (!frame_message(j, i, 0x7fffffff)) return false;
             j.segs[i].hide = j.bits[i].data(); j.segs[i].n_hide = (int)j.bits[i].size();
             tables_guess_of(side + n, p.n_frames, 0, j.guess[i]);        // the cursor guess of the first pass: the input's own tables
             j.segs[i].tables_guess = j.guess[i].data();
@@ -385,31 +363,31 @@ bool prepare_fast(mp3s_pipe *P, Job &j, Slot &s, ParsedStream &p, size_t *blob_l
     }
     *blob_len = base;
     j.n_total = (int)n;
+    // the slot's fixed areas: [dec headers, encoder inputs] inside in_cap, the host-decoded frames behind it
+    StagePacker pk;
+    pk.begin(s.o_in, s.o_in + s.in_cap);
+    pk.add((size_t)n * sizeof(mp3s_frame_hdr));
+    j.o_encblk = pk.add(0);
     j.o_fix = s.o_in + s.in_cap;
-    if (j.decode) {
-        if (!decode_result(j)) return false;
-        j.res->bits = std::move(j.res_bits);
+    if (j.decode()) {
+        if (!reserve_results(j)) return false;
+        j.res->bits = std::move(res_bits);
         return true;
     }
-    const size_t o_enc = up16((size_t)n * sizeof(mp3s_frame_hdr));
-    if (o_enc > s.in_cap || !encode_inputs(j, s, in + o_enc, s.in_cap - o_enc, P->c->opt[MP3S_OPT_SELECT] != 0)) return false;
-    j.o_encblk = s.o_in + o_enc;
-    j.res.reset(new mp3s_buf());
-    if (!j.res->big[0].reserve(j.L.mp3_bytes) || !j.res->big[2].reserve(small_bytes(j.L.n_segs))) return false;
-    j.res->mp3 = j.res->big[0].data();
-    return true;
+    if (!pk.ok || !encode_inputs(P, j, s, s.o_in + s.in_cap - j.o_encblk)) return false;
+    return reserve_results(j);
 }
 
 // What the stages of a hide, clear or decode job share: its frames, the format of its PCM, its small results and the buffers of its set
 // (Job::set) in the context's pool.  Every stage asks again: behind the first the buffers have their size and come back as they are.
-struct JobView { int n, nch, out_format; size_t esz, frame_elems; int32_t *d_small; void *d_is, *d_si, *d_keep; };
+struct JobView { int n, nch, out_format; size_t esz, frame_elems; SmallHead *d_small; void *d_is, *d_si, *d_keep; };
 int job_view(mp3s_ctx *c, const Job &j, const Slot &s, JobView &v)
 {
-    v.n = j.n_total; v.nch = j.decode ? j.nch : 2; v.out_format = j.ck.on && j.decode ? j.ck.out_format : MP3S_PCM_I16;
+    v.n = j.n_total; v.nch = j.decode() ? j.nch : 2; v.out_format = j.ck.on && j.decode() ? j.ck.out_format : MP3S_PCM_I16;
     v.esz = pcm_elem(v.out_format); v.frame_elems = (size_t)1152 * v.nch;
     // a walked job brings its block, status words zeroed, with its inputs (the kernels OR into them directly); a scanned one uses the
     // slot's, written by the last workgroup of each kernel
-    v.d_small = j.walked ? (int32_t *)(s.d_stage + j.o_small) : s.d_small;
+    v.d_small = j.walked ? (SmallHead *)(s.d_stage + j.o_small) : s.d_small;
     const size_t ng = (size_t)std::max(v.n, j.grab_frames);
     v.d_is = c->grab(kPoolIs[j.set], ng * 2304 * 2); v.d_si = c->grab(kPoolSi[j.set], ng * 4 * sizeof(mp3s_granule_si));
     v.d_keep = c->grab(kPoolPcm[j.set], ng * v.frame_elems * v.esz);
@@ -459,11 +437,11 @@ int issue_front(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23, boo
         for (const Upload &u : j.ups) HIPCHK(hipMemcpyAsync(s.d_image + u.dst, u.src, u.bytes, hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipMemcpyAsync(s.d_stage + j.o_small, s.h_stage + j.o_small, (inputs_later ? j.front_end : j.pack_end) - j.o_small, hipMemcpyHostToDevice, P->s_up));
     } else {
-        const size_t o_enc = j.o_encblk - s.o_in, in_bytes = j.decode ? up16((size_t)n * sizeof(mp3s_frame_hdr)) : o_enc + L.bytes;
+        const size_t o_enc = j.o_encblk - s.o_in, in_bytes = j.decode() ? up16((size_t)n * sizeof(mp3s_frame_hdr)) : o_enc + L.bytes;
         HIPCHK(hipMemcpyAsync(d_blob, s.h_stage, blob_len, hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipMemcpyAsync(d_side, s.h_stage + s.o_side, (size_t)n * sizeof(mp3s_frame_side), hipMemcpyHostToDevice, P->s_up));
         HIPCHK(hipMemcpyAsync(s.d_stage + s.o_in, s.h_stage + s.o_in, in_bytes, hipMemcpyHostToDevice, P->s_up));
-        HIPCHK(hipMemcpyAsync(s.d_stage + j.o_fix, s.h_stage + j.o_fix, (size_t)j.n_fix * kPlaceEntry, hipMemcpyHostToDevice, P->s_up));
+        HIPCHK(hipMemcpyAsync(s.d_stage + j.o_fix, s.h_stage + j.o_fix, (size_t)j.n_fix * sizeof(PlaceEntry), hipMemcpyHostToDevice, P->s_up));
     }
     HIPCHK(hipEventRecord(s.e_up, P->s_up));
     if (trace_on()) fprintf(stderr, "mp3s:   uploads queued %.3f ms after the job's start\n", now_ms() - t_issue0);
@@ -471,13 +449,13 @@ int issue_front(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23, boo
     if (j.d_file) { const int rc = file_up_wait(P, j.file_need, P->s_huff); if (rc) return rc; }
     if (P->dec_used[set]) HIPCHK(hipStreamWaitEvent(P->s_huff, P->e_dec[set], 0));
     if (j.walked) {
-        uint64_t *d_tsel = j.decode ? (uint64_t *)(s.d_stage + s.o_tsel) : nullptr;
+        uint64_t *d_tsel = j.decode() ? (uint64_t *)(s.d_stage + s.o_tsel) : nullptr;
         const int e = launch_parse(P->s_huff, j.d_file ? j.d_file : s.d_image, j.image_base, (const FrameRef *)(s.d_stage + j.o_refs), (const StreamRef *)(s.d_stage + j.o_streams), n,
-                                   j.md_base, (mp3s_frame_side *)d_side, (mp3s_frame_hdr *)(s.d_stage + s.o_dechdr), d_blob, d_tsel, v.d_small + 4);
+                                   j.md_base, (mp3s_frame_side *)d_side, (mp3s_frame_hdr *)(s.d_stage + s.o_dechdr), d_blob, d_tsel, &v.d_small->parse_status);
         if (e) return fail(MP3S_E_HIP, "parse launch: %s", hipGetErrorString((hipError_t)e));
     }
     const int e = launch_huffman(P->s_huff, d_blob, (const mp3s_frame_side *)d_side, n, v.nch, max_p23, (int16_t *)v.d_is, (mp3s_granule_si *)v.d_si,
-                                 v.d_small + 3, j.walked ? nullptr : c->d_sync + 4, &c->prof, false, (int)c->opt[MP3S_OPT_HUF_LANES]);
+                                 &v.d_small->huffman_status, j.walked ? nullptr : c->d_sync + 4, &c->prof, false, (int)c->opt[MP3S_OPT_HUF_LANES]);
     if (e) return fail(MP3S_E_HIP, "huffman launch: %s", hipGetErrorString((hipError_t)e));
     if (launch_place_frames(P->s_huff, s.d_stage + j.o_fix, j.n_fix, (int16_t *)v.d_is, (mp3s_granule_si *)v.d_si))
         return fail(MP3S_E_HIP, "placing the host-decoded frames failed");
@@ -510,7 +488,7 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
     HIPCHK(hipStreamWaitEvent(ds, s.e_huff, 0));
     // the PCM buffer of this set may still be read by the download of the decode job that used it last ...
     if (P->keep_slot[set] >= 0) HIPCHK(hipStreamWaitEvent(ds, P->slots[(size_t)P->keep_slot[set]].e_down, 0));
-    P->keep_slot[set] = j.decode ? j.slot : -1;
+    P->keep_slot[set] = j.decode() ? j.slot : -1;
     // ... or by the encode transforms of the job before last (on the compute stream)
     if (P->s_dec && P->enc_used[set]) HIPCHK(hipStreamWaitEvent(ds, P->e_enc[set], 0));
     // a transform group that starts inside a stream re-runs one frame of it for the state (the chunk's own halo comes first)
@@ -533,9 +511,9 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
     if (n <= halo0 || !(c->opt[MP3S_OPT_PIPE_SIGNALS] & 1)) HIPCHK(hipEventRecord(P->e_dec[set], ds));     // (no group ran: nothing has signalled it)
     if (trace_on()) fprintf(stderr, "mp3s:   decode transforms queued %.3f ms after the job's start\n", now_ms() - t_issue0);
     P->dec_used[set] = true;
-    if (P->s_dec && !j.decode) HIPCHK(hipStreamWaitEvent(c->stream, P->e_dec[set], 0));   // the encode side starts when the PCM is there
-    if (inputs_later && j.pack_end > j.front_end && !j.decode) HIPCHK(hipStreamWaitEvent(c->stream, s.e_in, 0));   // ... and its own inputs
-    if (j.decode) {
+    if (P->s_dec && !j.decode()) HIPCHK(hipStreamWaitEvent(c->stream, P->e_dec[set], 0));   // the encode side starts when the PCM is there
+    if (inputs_later && j.pack_end > j.front_end && !j.decode()) HIPCHK(hipStreamWaitEvent(c->stream, s.e_in, 0));   // ... and its own inputs
+    if (j.decode()) {
         HIPCHK(hipEventRecord(s.e_comp, ds));
         j.down_pending = true;
         return defer_down ? MP3S_OK : issue_down(P, j, s);
@@ -567,19 +545,19 @@ int issue_down(mp3s_pipe *P, Job &j, Slot &s)
     if (!j.down_pending) return MP3S_OK;
     j.down_pending = false;
     const Chunk &ck = j.ck;
-    int32_t *const d_small = j.walked ? (int32_t *)(s.d_stage + j.o_small) : s.d_small;
+    const SmallHead *const d_small = j.walked ? (const SmallHead *)(s.d_stage + j.o_small) : s.d_small;
     size_t done_bytes = 0;
-    if (!j.decode && j.down_split > 0) {      // the bytes of the packer's first launch: behind ITS event, not the job's last kernel
+    if (!j.decode() && j.down_split > 0) {      // the bytes of the packer's first launch: behind ITS event, not the job's last kernel
         const size_t total = j.segs.back().mp3_off + j.segs.back().mp3_len;
         done_bytes = std::min(j.down_split & ~(size_t)3, total);
         HIPCHK(hipStreamWaitEvent(P->s_down, s.e_half, 0));
         if (done_bytes) HIPCHK(hipMemcpyAsync((ck.on ? ck.dst : j.res->mp3), s.d_mp3, done_bytes, hipMemcpyDeviceToHost, P->s_down));
     }
     HIPCHK(hipStreamWaitEvent(P->s_down, s.e_comp, 0));
-    if (j.decode) {
+    if (j.decode()) {
         JobView v;
         if (const int rc = job_view(P->c, j, s, v)) return rc;
-        HIPCHK(hipMemcpyAsync(j.res->big[2].data(), d_small, kSmallHead, hipMemcpyDeviceToHost, P->s_down));
+        HIPCHK(hipMemcpyAsync(j.res->big[2].data(), d_small, sizeof(SmallHead), hipMemcpyDeviceToHost, P->s_down));
         if (j.walked) HIPCHK(hipMemcpyAsync(j.res->big[1].data(), s.d_stage + s.o_tsel, (size_t)v.n * 8, hipMemcpyDeviceToHost, P->s_down));
         if (ck.on) {
             HIPCHK(hipMemcpyAsync(ck.dst, v.d_keep, (size_t)ck.count * v.frame_elems * v.esz, hipMemcpyDeviceToHost, P->s_down));
@@ -607,11 +585,7 @@ int issue_down(mp3s_pipe *P, Job &j, Slot &s)
 bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
 {
     const int nf = (int)j.files.size();
-    if (nf > kMaxFastFiles) return false;
-    j.walked = true; j.ck.on = false;      // (walked: the job brings its small results block, status words zeroed, with its inputs)
-    j.segs.assign((size_t)nf, EncSeg());
-    j.bits.clear(); j.guess.clear(); j.dec.clear(); j.res_bits.clear(); j.ups.clear(); j.stream_first.assign((size_t)nf, 0);
-    j.n_fix = 0; j.image_base = 0; j.md_base = 0;
+    if (!job_begin(j, nf, true)) return false;   // (walked: the job brings its small results block, status words zeroed, with its inputs)
     // The slot's WAV image: as many frames as the slot's other buffers are made for (side_cap), 4 608 bytes each, + a header
     // and the alignment of every file: 48 x max_job_bytes on the device (4 608 bytes per frame where the slot counts 96), e.g.
     // 402 MB per slot of a pipe made for 8 MB jobs.  The page-locked staging for short files is sized by what they need (below).
@@ -652,20 +626,14 @@ bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s)
             return s.h_wav;
         }, j.ups)) return false;
     j.n_total = (int)b.n_all;
-    j.L = EncLayout();
-    j.o_small = s.o_in;
-    const size_t small_room = up16(small_bytes(nf));
-    std::memset(s.h_stage + j.o_small, 0, kSmallHead);
-    j.o_encblk = j.o_small + small_room;
     // (no stream to ask for table counts: the cursors are guessed at three per unit as mp3s_encode_pcm does, the selection on the
     //  device covers what the message can reach)
-    if (small_room >= s.in_cap || !encode_inputs(j, s, s.h_stage + j.o_encblk, s.in_cap - small_room, P->c->opt[MP3S_OPT_SELECT] != 0)) return false;
-    j.res.reset(new mp3s_buf());
-    if (!j.res->big[0].reserve(j.L.mp3_bytes) || !j.res->big[2].reserve(small_bytes(j.L.n_segs))) return false;
-    j.res->mp3 = j.res->big[0].data();
-    b.place_records(j.o_encblk + j.L.bytes);
-    j.pack_end = b.rec_end;
-    if (j.pack_end > s.o_in + s.pack_cap) return false;
+    StagePacker pk;
+    if (!pack_front(P, j, s, pk, nf)) return false;
+    b.place_records(pk.end());
+    pk.add(b.rec_end - b.o_runs);          // (the batch's records: o_runs is where the packer puts them)
+    j.pack_end = pk.end();
+    if (!pk.ok) return false;
     for (const WavBatch::Part &p : b.parts())
         if (p.bytes) std::memcpy(s.h_stage + p.at, p.data, p.bytes);
     return true;
@@ -703,7 +671,7 @@ int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down)
     HIPCHK(hipStreamWaitEvent(c->stream, s.e_huff, 0));
     if (const int rc = slot_enc_dev(c, j, s, d_keep)) return rc;
     EncDev &dev = j.dev;
-    dev.d_small = (int32_t *)(s.d_stage + j.o_small); dev.direct_status = true;
+    dev.d_small = (SmallHead *)(s.d_stage + j.o_small); dev.direct_status = true;
     j.down_split = 0;
     const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, P->e_enc[set]);
     if (rc) return rc;
@@ -721,17 +689,21 @@ namespace {
 // runtime shares between the copy streams) until then -- the device sits idle for that job's front end.  There the copy down is
 // queued behind the next job's issue instead, or by the collector if that comes first (as the one-file calls do since round 3;
 // deeper pipes have their jobs' inputs up long before the job in front asks for its results).
+int pending_down_now(mp3s_pipe *P, const Job &j)     // the copy down of the job issued last, unless that is j
+{
+    Job *q = P->pending_down;
+    if (!q || q == &j) return MP3S_OK;
+    P->pending_down = nullptr;
+    return issue_down(P, *q, P->slots[(size_t)q->slot]);
+}
+
 int issue_fast(mp3s_pipe *P, Job &j, Slot &s, size_t blob_len, int max_p23)
 {
     const bool defer = P->depth <= 2 && !P->internal;
-    int rc = j.encode ? issue_encode(P, j, s, defer) : issue_front(P, j, s, blob_len, max_p23, false);
-    if (!rc && !j.encode) rc = issue_back(P, j, s, false, defer);
-    if (P->pending_down && P->pending_down != &j) {           // the job in front: its results may come down now
-        Job *q = P->pending_down;
-        P->pending_down = nullptr;
-        const int rd = issue_down(P, *q, P->slots[(size_t)q->slot]);
-        if (!rc) rc = rd;
-    }
+    int rc = j.kind == Job::ENCODE ? issue_encode(P, j, s, defer) : issue_front(P, j, s, blob_len, max_p23, false);
+    if (!rc && j.kind != Job::ENCODE) rc = issue_back(P, j, s, false, defer);
+    const int rd = pending_down_now(P, j);                    // the job in front: its results may come down now
+    if (!rc) rc = rd;
     if (!rc && defer && j.down_pending) P->pending_down = &j;
     return rc;
 }
@@ -769,11 +741,7 @@ void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held
     }
     // (a shallow pipe's last issued job may still wait for its copy down to be queued: the synchronous path below writes the PCM and
     // Huffman buffers it would read)
-    if (P->pending_down && P->pending_down != &j) {
-        Job *q = P->pending_down;
-        P->pending_down = nullptr;
-        (void)issue_down(P, *q, P->slots[(size_t)q->slot]);
-    }
+    (void)pending_down_now(P, j);
     (void)hipStreamSynchronize(P->s_huff);   // the synchronous path uses the same Huffman output buffers
     if (P->s_dec) (void)hipStreamSynchronize(P->s_dec);   // ... and the decode scratch
     (void)hipStreamSynchronize(P->s_down);   // ... and the PCM buffer a download may still be reading
@@ -784,16 +752,16 @@ void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held
     // (the context's own pipe is not entered from here: this pipe owns the context)
     const int64_t keep = P->c->opt[MP3S_OPT_FILE_PIPELINE];
     P->c->opt[MP3S_OPT_FILE_PIPELINE] = 0;
-    if (j.encode) {
+    if (j.kind == Job::ENCODE) {
         std::vector<int32_t> nh(nf);
         for (int i = 0; i < nf; i++) { mp[i] = j.msgs[i].first; nh[i] = (int32_t)j.msgs[i].second; }
         j.slow_rc = encode_files_as(P->c, P->wav, fp.data(), fl.data(), nf, j.enc_kbps.data(), j.enc_hide ? mp.data() : nullptr, j.enc_hide ? nh.data() : nullptr,
                                       &j.slow_owner, j.slow_out.data(), j.slow_st.data());
         j.slow_err = mp3s_last_error();
-    } else if (j.block) {
+    } else if (j.kind == Job::BLOCK) {
         j.slow_rc = mp3s_reencode_block(P->c, fp[0], fl[0], mp[0], ml[0], j.rank, j.world, j.has_carry ? &j.carry : nullptr, &j.blk_owner, &j.blk);
         j.slow_err = mp3s_last_error();
-    } else if (j.decode) {
+    } else if (j.decode()) {
         // file by file through mp3s_decode_file; the owners travel in one
         std::unique_ptr<mp3s_buf> top(new mp3s_buf());
         for (int i = 0; i < nf; i++) {
@@ -844,8 +812,8 @@ void worker(mp3s_pipe *P, int me)
         size_t blob_len = 0;
         int max_p23 = 0;
         bool fast;
-        if (j->encode) fast = prepare_encode(P, *j, s);
-        else if (j->block) {
+        if (j->kind == Job::ENCODE) fast = prepare_encode(P, *j, s);
+        else if (j->kind == Job::BLOCK) {
             fast = P->c->opt[MP3S_OPT_DEVICE_PARSE] && prepare_block(P, *j, s);
             max_p23 = j->max_p23;
         } else {
@@ -854,7 +822,7 @@ void worker(mp3s_pipe *P, int me)
             else fast = prepare_fast(P, *j, s, scratch, &blob_len, &max_p23);
         }
         const double t1 = now_ms(), c1 = thread_cpu_ms();
-        if (trace_on()) fprintf(stderr, "mp3s: pipe job %lld slot %d on cpu %d: %s + layout %.3f ms (cpu %.3f)%s\n", (long long)j->ticket, j->slot, sched_getcpu(), j->encode ? "headers" : j->walked ? "walk" : "scan", t1 - t0, c1 - c0, fast ? "" : " -> synchronous path");
+        if (trace_on()) fprintf(stderr, "mp3s: pipe job %lld slot %d on cpu %d: %s + layout %.3f ms (cpu %.3f)%s\n", (long long)j->ticket, j->slot, sched_getcpu(), j->kind == Job::ENCODE ? "headers" : j->walked ? "walk" : "scan", t1 - t0, c1 - c0, fast ? "" : " -> synchronous path");
         Job::State st;
         bool cancelled = false;
         {
@@ -931,7 +899,7 @@ bool pipe_slot_ready(mp3s_pipe *P, Slot &s)
         s.o_side = s.blob_cap;
         s.o_in = up16(s.o_side + s.side_cap * sizeof(mp3s_frame_side));
         s.fix_cap = internal ? 8 : std::min<size_t>(kMaxFastFiles, s.side_cap);     // (host-decoded last frames: one per file of a job; the context's own pipe runs ONE file's chunks)
-        s.pack_cap = up16(s.in_cap + s.fix_cap * kPlaceEntry + s.side_cap * sizeof(FrameRef) + (size_t)kMaxFastFiles * sizeof(StreamRef) + 256);
+        s.pack_cap = up16(s.in_cap + s.fix_cap * sizeof(PlaceEntry) + s.side_cap * sizeof(FrameRef) + (size_t)kMaxFastFiles * sizeof(StreamRef) + 256);
         s.stage_bytes = s.o_in + s.pack_cap;
         s.o_dechdr = s.stage_bytes;
         s.o_tsel = up16(s.o_dechdr + s.side_cap * sizeof(mp3s_frame_hdr));
@@ -1004,17 +972,16 @@ int pipe_create(mp3s_ctx *c, int depth, size_t max_job_bytes, int scan_threads, 
 // the job's results are on the host: are they final?  *resolved: the host had to resolve the chains (on the job's own buffers)
 bool finish_fast(mp3s_pipe *P, Job *j, Slot &s, bool *resolved)
 {
-    const int32_t *small = (const int32_t *)j->res->big[2].data();
-    const bool parse_ok = !j->walked || (small[4] & kParseMismatch) == 0;
-    bool fast_ok = parse_ok && (j->decode ? small[3] == 0 : (small[0] == 0 && small[1] == 0 && small[2] == 0 && small[3] == 0));
+    const SmallHead &head = SmallView{j->res->big[2].data()}.head();
+    const bool fast_ok = j->decode() ? head.decode_final(j->walked) : head.encode_final(j->walked);
     *resolved = false;
     if (!fast_ok) {
         if (trace_on()) fprintf(stderr, "mp3s: pipe job %lld: verdict %d units to redo, step range %d, packer %d, Huffman status 0x%x, parse status 0x%x\n",
-                                (long long)j->ticket, small[0], small[1], small[2], small[3], small[4]);
+                                (long long)j->ticket, head.redo_units, head.step_range, head.pack_status, head.huffman_status, head.parse_status);
         // only the cursor / address guesses failed (a long message, a start the input's tables did not predict):
         // the host resolves the chains on the job's own device buffers -- scan, decode and transforms stand
         if (P->s_tail) (void)hipStreamSynchronize(P->s_tail);   // (later jobs' tails: the resolve below packs through the same context)
-        if (parse_ok && !j->decode && small[0] != 0 && small[1] == 0 && small[3] == 0) {
+        if (!j->decode() && head.resolvable(j->walked)) {
             int passes = 0;
             *resolved = enc_resolve(P->c, j->L, j->segs, s.h_stage + j->o_encblk, j->dev, j->res.get(), false, &passes) == MP3S_OK;
             if (hipStreamSynchronize(P->c->stream) != hipSuccess) *resolved = false;
@@ -1050,6 +1017,51 @@ void pipe_quiesce(mp3s_pipe *P)
     if (P->s_ctx) { P->c->stream = P->s_ctx; P->s_ctx = nullptr; }
 }
 
+namespace {
+
+// ---- what collecting a job is, whatever it hands out: wait for its results, settle its verdict, give its slot back
+struct Collected { bool fast_ok = false, resolved = false; double span_ms = -1; };
+
+// (the job has taken the synchronous path, or it was issued: then its results are on the host afterwards)
+int collect_wait(mp3s_pipe *P, Job *j, Collected &k)
+{
+    if (j->state != Job::ISSUED) return MP3S_OK;
+    Slot &s = P->slots[(size_t)j->slot];
+    (void)hipSetDevice(P->c->device);
+    down_now(P, *j, s);
+    if (hipEventSynchronize(s.e_down) != hipSuccess) return fail(MP3S_E_HIP, "waiting for the job's results failed");
+    float ms = 0;
+    if (j->kind != Job::BLOCK && hipEventElapsedTime(&ms, s.e_start, s.e_down) == hipSuccess) k.span_ms = ms;
+    return MP3S_OK;
+}
+
+// Is what came down final?  If not, the host resolves the chains, or the synchronous path decides, file by file (damaged Huffman data, a quantiser
+// step out of range, a failed resolve).  Both touch the context: mu_issue -- a block job takes it at once, another job when a word of the head says anything.
+void collect_settle(mp3s_pipe *P, Job *j, Collected &k)
+{
+    if (j->state != Job::ISSUED) return;
+    Slot &s = P->slots[(size_t)j->slot];
+    const SmallHead &head = SmallView{j->res->big[2].data()}.head();
+    std::unique_lock<std::mutex> gi(P->mu_issue, std::defer_lock);
+    if (j->kind == Job::BLOCK || !head.all_clean()) gi.lock();
+    k.fast_ok = finish_fast(P, j, s, &k.resolved);
+    // (a share of a stream that inherits scalefactors across frames cannot look back on the device)
+    if (j->kind == Job::BLOCK && (k.fast_ok || k.resolved) && head.inherits_across_frames() && j->world > 1) k.fast_ok = k.resolved = false;
+    if (!k.fast_ok && !k.resolved) { if (!gi.owns_lock()) gi.lock(); run_slow(P, *j); }
+}
+
+void collect_release(mp3s_pipe *P, Job *j, const Collected &k)
+{
+    std::lock_guard<std::mutex> g(P->mu);
+    P->st.collected++;
+    if (k.span_ms >= 0) P->st.last_device_span_ms = k.span_ms;
+    if (k.fast_ok) P->st.fast++; else if (k.resolved) P->st.resolved++; else P->st.slow++;
+    P->slots[(size_t)j->slot].busy = false;
+    P->inflight.pop_front();
+}
+
+}  // namespace
+
 extern "C" {
 
 int mp3s_pipe_create(mp3s_ctx *c, int depth, size_t max_job_bytes, int scan_threads, mp3s_pipe **out)
@@ -1076,6 +1088,16 @@ void mp3s_pipe_destroy(mp3s_pipe *P)
     delete P;
 }
 
+// a job of `kind` over n_files files, no messages yet
+static std::unique_ptr<Job> new_job(Job::Kind kind, const uint8_t *const *files, const size_t *lens, int n_files)
+{
+    std::unique_ptr<Job> j(new Job());
+    j->kind = kind; j->clear_all = true;
+    j->files.resize((size_t)n_files); j->msgs.assign((size_t)n_files, {nullptr, 0});
+    for (int i = 0; i < n_files; i++) j->files[i] = {files[i], lens[i]};
+    return j;
+}
+
 static int submit_job(mp3s_pipe *P, std::unique_ptr<Job> j, int64_t *ticket)
 {
     {
@@ -1098,15 +1120,11 @@ int mp3s_pipe_submit(mp3s_pipe *P, const uint8_t *const *mp3s, const size_t *len
                      const size_t *msg_lens, int64_t *ticket)
 {
     if (!P || P->internal || !mp3s || !lens || n_files <= 0 || (msgs && !msg_lens)) return fail(MP3S_E_ARG, "bad argument");
-    std::unique_ptr<Job> j(new Job());
-    j->files.resize((size_t)n_files); j->msgs.assign((size_t)n_files, {nullptr, 0});
+    std::unique_ptr<Job> j = new_job(Job::HIDE, mp3s, lens, n_files);
     j->clear_all = msgs == nullptr;
-    for (int i = 0; i < n_files; i++) {
-        j->files[i] = {mp3s[i], lens[i]};
-        if (msgs) {
-            if (!msgs[i] && msg_lens[i]) return fail(MP3S_E_ARG, "file %d: null message of non-zero length", i);
-            j->msgs[i] = {msgs[i], msg_lens[i]};
-        }
+    for (int i = 0; msgs && i < n_files; i++) {
+        if (!msgs[i] && msg_lens[i]) return fail(MP3S_E_ARG, "file %d: null message of non-zero length", i);
+        j->msgs[i] = {msgs[i], msg_lens[i]};
     }
     return submit_job(P, std::move(j), ticket);
 }
@@ -1114,26 +1132,18 @@ int mp3s_pipe_submit(mp3s_pipe *P, const uint8_t *const *mp3s, const size_t *len
 int mp3s_pipe_submit_decode(mp3s_pipe *P, const uint8_t *const *mp3s, const size_t *lens, int n_files, int64_t *ticket)
 {
     if (!P || P->internal || !mp3s || !lens || n_files <= 0) return fail(MP3S_E_ARG, "bad argument");
-    std::unique_ptr<Job> j(new Job());
-    j->decode = true; j->clear_all = true;
-    j->files.resize((size_t)n_files); j->msgs.assign((size_t)n_files, {nullptr, 0});
-    for (int i = 0; i < n_files; i++) j->files[i] = {mp3s[i], lens[i]};
-    return submit_job(P, std::move(j), ticket);
+    return submit_job(P, new_job(Job::DECODE, mp3s, lens, n_files), ticket);
 }
 
 int mp3s_pipe_submit_encode(mp3s_pipe *P, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,
                             const uint8_t *const *hide_bits, const int32_t *n_hide, int64_t *ticket)
 {
     if (!P || P->internal || !wavs || !lens || !bitrate_kbps || n_files <= 0 || (hide_bits && !n_hide)) return fail(MP3S_E_ARG, "bad argument");
-    std::unique_ptr<Job> j(new Job());
-    j->encode = true; j->clear_all = true; j->enc_hide = hide_bits != nullptr;
-    j->files.resize((size_t)n_files); j->msgs.assign((size_t)n_files, {nullptr, 0});
+    std::unique_ptr<Job> j = new_job(Job::ENCODE, wavs, lens, n_files);
+    j->enc_hide = hide_bits != nullptr;
     j->enc_kbps.assign(bitrate_kbps, bitrate_kbps + n_files);
-    for (int i = 0; i < n_files; i++) {
-        j->files[i] = {wavs[i], lens[i]};
-        // (a negative count is the file's own MP3S_E_ARG at collect time, as mp3s_encode_files gives it)
-        if (hide_bits) j->msgs[i] = {hide_bits[i], (size_t)(int64_t)n_hide[i]};
-    }
+    // (a negative count is the file's own MP3S_E_ARG at collect time, as mp3s_encode_files gives it)
+    for (int i = 0; hide_bits && i < n_files; i++) j->msgs[i] = {hide_bits[i], (size_t)(int64_t)n_hide[i]};
     return submit_job(P, std::move(j), ticket);
 }
 
@@ -1148,31 +1158,15 @@ int mp3s_pipe_collect(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3s_file
         if (ticket) *ticket = j->ticket;   // (also when the call fails: the caller learns which job it is stuck on)
         if (n_files) *n_files = (int)j->files.size();
         if ((int)j->files.size() > max_files) return fail(MP3S_E_ARG, "the next job has %zu files, room for %d", j->files.size(), max_files);
-        if (j->block) return fail(MP3S_E_ARG, "the next job is a block job: mp3s_pipe_collect_block");
+        if (j->kind == Job::BLOCK) return fail(MP3S_E_ARG, "the next job is a block job: mp3s_pipe_collect_block");
         P->cv_done.wait(g, [&] { return j->state != Job::QUEUED; });
     }
-    Slot &s = P->slots[(size_t)j->slot];
     const int nf = (int)j->files.size();
-    int rc = MP3S_OK;
-    bool fast_ok = false, resolved = false;
-    double span_ms = -1;
-    if (j->state == Job::ISSUED) {
-        (void)hipSetDevice(P->c->device);
-        down_now(P, *j, s);
-        if (hipEventSynchronize(s.e_down) != hipSuccess) rc = fail(MP3S_E_HIP, "waiting for the job's results failed");
-        else {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, s.e_start, s.e_down) == hipSuccess) span_ms = ms;
-            std::unique_lock<std::mutex> gi(P->mu_issue, std::defer_lock);
-            const int32_t *small = (const int32_t *)j->res->big[2].data();
-            if (!(small[0] == 0 && small[1] == 0 && small[2] == 0 && small[3] == 0 && (small[4] & kParseMismatch) == 0)) gi.lock();
-            fast_ok = finish_fast(P, j, s, &resolved);
-            // damaged Huffman data, a quantiser step out of range, a failed resolve: the synchronous path decides, file by file
-            if (!fast_ok && !resolved) { if (!gi.owns_lock()) gi.lock(); run_slow(P, *j); }
-        }
-    }
+    Collected k;
+    int rc = collect_wait(P, j, k);
     if (!rc) {
-        if (fast_ok && j->decode) {
+        collect_settle(P, j, k);
+        if (k.fast_ok && j->decode()) {
             if (j->walked) {
                 // the stego bits: a serial pass over the table-index words the device left
                 const uint64_t *tsel = (const uint64_t *)j->res->big[1].data();
@@ -1194,11 +1188,11 @@ int mp3s_pipe_collect(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3s_file
                 status[i] = MP3S_OK;
             }
             *owner = j->res.release();
-        } else if (fast_ok || resolved) {
-            const mp3s_chain_seg_out *so = (const mp3s_chain_seg_out *)(j->res->big[2].data() + kSmallHead);
+        } else if (k.fast_ok || k.resolved) {
+            const SmallView small{j->res->big[2].data()};
             for (int i = 0; i < nf; i++) {
                 const EncSeg &sg = j->segs[(size_t)i];
-                file_from_seg(sg, j->res->mp3, j->kbps, j->rate, resolved ? sg.hide_offset : so[i].cursor - sg.hide_base, &out[i]);
+                file_from_seg(sg, j->res->mp3, j->kbps, j->rate, seg_end(sg, small.seg_out((size_t)i), k.resolved).hide_offset, &out[i]);
                 status[i] = MP3S_OK;
             }
             *owner = j->res.release();
@@ -1212,14 +1206,7 @@ int mp3s_pipe_collect(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3s_file
             }
         }
     }
-    {
-        std::lock_guard<std::mutex> g(P->mu);
-        P->st.collected++;
-        if (span_ms >= 0) P->st.last_device_span_ms = span_ms;
-        if (fast_ok) P->st.fast++; else if (resolved) P->st.resolved++; else P->st.slow++;
-        s.busy = false;
-        P->inflight.pop_front();
-    }
+    collect_release(P, j, k);
     return rc;
 }
 
@@ -1228,9 +1215,9 @@ int mp3s_pipe_submit_block(mp3s_pipe *P, const uint8_t *mp3, size_t len, const u
 {
     if (!P || P->internal || !mp3 || world <= 0 || rank < 0 || rank >= world || (rank == 0 && carry_in) || (rank > 0 && !carry_in) || (!utf8 && n_msg))
         return fail(MP3S_E_ARG, "bad argument (rank 0 has no carry, every other rank has one)");
-    std::unique_ptr<Job> j(new Job());
-    j->block = true; j->rank = rank; j->world = world;
-    j->files.assign(1, {mp3, len}); j->msgs.assign(1, {utf8, n_msg});
+    std::unique_ptr<Job> j = new_job(Job::BLOCK, &mp3, &len, 1);
+    j->rank = rank; j->world = world;
+    j->msgs[0] = {utf8, n_msg};
     j->clear_all = utf8 == nullptr;
     if (carry_in) { j->has_carry = true; j->carry = *carry_in; }
     return submit_job(P, std::move(j), ticket);
@@ -1241,7 +1228,7 @@ int mp3s_pipe_next_is_block(mp3s_pipe *P)
     if (!P) return fail(MP3S_E_ARG, "null pointer");
     std::lock_guard<std::mutex> g(P->mu);
     if (P->inflight.empty()) return fail(MP3S_E_BUSY, "nothing in flight");
-    return P->inflight.front()->block ? 1 : 0;
+    return P->inflight.front()->kind == Job::BLOCK ? 1 : 0;
 }
 
 int mp3s_pipe_collect_block(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3s_block *out)
@@ -1253,37 +1240,19 @@ int mp3s_pipe_collect_block(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3
         if (P->inflight.empty()) return fail(MP3S_E_BUSY, "nothing in flight");
         j = P->inflight.front().get();
         if (ticket) *ticket = j->ticket;
-        if (!j->block) return fail(MP3S_E_ARG, "the next job is not a block job: mp3s_pipe_collect");
+        if (j->kind != Job::BLOCK) return fail(MP3S_E_ARG, "the next job is not a block job: mp3s_pipe_collect");
         P->cv_done.wait(g, [&] { return j->state != Job::QUEUED; });
     }
-    Slot &s = P->slots[(size_t)j->slot];
-    int rc = MP3S_OK;
-    bool fast_ok = false, resolved = false;
-    if (j->state == Job::ISSUED) {
-        (void)hipSetDevice(P->c->device);
-        down_now(P, *j, s);
-        if (hipEventSynchronize(s.e_down) != hipSuccess) rc = fail(MP3S_E_HIP, "waiting for the job's results failed");
-        else {
-            std::lock_guard<std::mutex> gi(P->mu_issue);
-            fast_ok = finish_fast(P, j, s, &resolved);
-            const int32_t *small = (const int32_t *)j->res->big[2].data();
-            // (a share of a stream that inherits scalefactors across frames cannot look back on the device)
-            if ((fast_ok || resolved) && (small[4] & kParseInherits) && j->world > 1) fast_ok = resolved = false;
-            if (!fast_ok && !resolved) run_slow(P, *j);
-        }
-    }
+    Collected k;
+    int rc = collect_wait(P, j, k);
     if (!rc) {
-        if (fast_ok || resolved) {
+        collect_settle(P, j, k);
+        if (k.fast_ok || k.resolved) {
             const EncSeg &sg = j->segs[0];
-            const mp3s_chain_seg_out *so = (const mp3s_chain_seg_out *)(j->res->big[2].data() + kSmallHead);
-            if (resolved) { j->blk.carry_out = sg.carry_out; j->blk.carry_used = sg.carry_used ? 1 : 0; }
-            else {
-                j->blk.carry_out.cursor = so[0].cursor - sg.hide_base;
-                std::memcpy(j->blk.carry_out.chain, so[0].chain, sizeof j->blk.carry_out.chain);
-                j->blk.carry_used = so[0].carry_used != 0;
-            }
+            const SegEnd e = seg_end(sg, SmallView{j->res->big[2].data()}.seg_out(0), k.resolved);
+            j->blk.carry_out = e.out; j->blk.carry_used = e.carry_used ? 1 : 0;
             j->blk.file.data = j->res->mp3 + sg.mp3_off; j->blk.file.len = sg.mp3_len; j->blk.file.n_frames = (int32_t)j->blk.n_frames;
-            j->blk.file.hide_offset = j->blk.carry_out.cursor;
+            j->blk.file.hide_offset = e.hide_offset;
             j->blk.file.too_long = j->blk.file.hide_offset < (int64_t)sg.n_hide - 1 ? 1 : 0;
             *out = j->blk;
             *owner = j->res.release();
@@ -1293,13 +1262,7 @@ int mp3s_pipe_collect_block(mp3s_pipe *P, int64_t *ticket, mp3s_buf **owner, mp3
             else { *out = j->blk; *owner = j->blk_owner; j->blk_owner = nullptr; }
         }
     }
-    {
-        std::lock_guard<std::mutex> g(P->mu);
-        P->st.collected++;
-        if (fast_ok) P->st.fast++; else if (resolved) P->st.resolved++; else P->st.slow++;
-        s.busy = false;
-        P->inflight.pop_front();
-    }
+    collect_release(P, j, k);
     return rc;
 }
 

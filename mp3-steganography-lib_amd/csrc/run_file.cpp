@@ -141,10 +141,9 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
     std::vector<uint8_t> &tables = c->h_tables;
     if (n_hide) { w.tables_wanted = (long)n_hide + (long)n_hide / 16 + 64; tables.resize((size_t)first_chunk * 4 + 16); }
     long n_walked = 0;
-    WalkOut wv;                                  // the walker's state behind the chunk in hand
     std::unique_ptr<mp3s_buf> res(new mp3s_buf());
     std::vector<RunChunk> chunks;
-    uint8_t fix[kPlaceEntry];
+    PlaceEntry fix;                              // the stream's last frame, decoded here when the walk ends (E14)
     bool have_fix = false;
     int rate = 0, kbps = 0, nch = 0;
     const size_t esz = pcm_elem(out_format);
@@ -185,22 +184,16 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         const bool ok = finish_fast(P, j, s, &resolved);
         if (!ok && !resolved) return kRunFallback;
         if (resolved) c->run_stats.resolved++;
-        const int32_t *small = (const int32_t *)j->res->big[2].data();
+        const SmallView small{j->res->big[2].data()};
         // scalefactors inherited across frames: the Huffman kernel walks back to the granule that wrote them.  With the
         // file's side records and main data in file-wide arrays it finds them across chunk boundaries (round 4); without them
         // (a file above 1 GB, no memory) the stream goes through the stages once more, in one piece
-        if (j->walked && !j->file_wide && (small[4] & kParseInherits) && chunks.size() + (wv.ended ? 0 : 1) > 1) return kRunWhole;
+        if (j->walked && !j->file_wide && small.head().inherits_across_frames() && chunks.size() + (w.ended ? 0 : 1) > 1) return kRunWhole;
         if (!decode) {
-            EncSeg &sg = j->segs[0];
-            if (resolved) {
-                std::memcpy(j->ck.dst, j->res->mp3 + sg.mp3_off, sg.mp3_len);
-                rc.out = sg.carry_out; rc.carry_used = sg.carry_used;
-            } else {
-                const mp3s_chain_seg_out *so = (const mp3s_chain_seg_out *)(j->res->big[2].data() + kSmallHead);
-                rc.out.cursor = so[0].cursor - sg.hide_base;
-                std::memcpy(rc.out.chain, so[0].chain, sizeof rc.out.chain);
-                rc.carry_used = so[0].carry_used != 0;
-            }
+            const EncSeg &sg = j->segs[0];
+            if (resolved) std::memcpy(j->ck.dst, j->res->mp3 + sg.mp3_off, sg.mp3_len);
+            const SegEnd e = seg_end(sg, small.seg_out(0), resolved);
+            rc.out = e.out; rc.carry_used = e.carry_used;
             rc.out_len = (int64_t)sg.mp3_len;
         }
         rc.done = true;
@@ -257,25 +250,20 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         Slot &s = P->slots[(size_t)j.slot];
         if (!pipe_slot_ready(P, s)) return kRunFallback;
         Chunk &ck = j.ck;
-        ck.on = true; ck.decode = decode; ck.refs = refs.data(); ck.first = rc.first; ck.count = rc.count; ck.last = rc.last;
-        ck.lead = !decode && rc.first > 0 ? 1 : 0;
-        ck.halo = rc.first - ck.lead > 0 ? 1 : 0;
-        ck.w0 = rc.first - ck.lead - ck.halo; ck.n_win = rc.count + ck.lead + ck.halo;
-        ck.out_format = out_format; ck.file = mp3; ck.file_len = len; ck.rate = rate; ck.kbps = kbps; ck.nch = nch;
-        const uint32_t lo = refs[(size_t)ck.w0].file_off;
-        ck.image_lo = rc.first == 0 ? 0 : (lo > kImageLead ? lo - kImageLead : 0);
-        const FrameRef &lr = refs[(size_t)(rc.first + rc.count - 1)];
-        ck.image_hi = (uint32_t)std::min<uint64_t>(len, (uint64_t)lr.file_off + lr.frame_size + 64);
-        ck.fix = rc.last && have_fix ? fix : nullptr;
+        ck.decode = decode;
+        chunk_window(ck, refs.data(), rc.first, rc.count, rc.last, mp3, len);
+        ck.out_format = out_format; ck.rate = rate; ck.kbps = kbps; ck.nch = nch;
+        ck.fix = rc.last && have_fix ? &fix : nullptr;
         ck.hide = bits.data(); ck.n_hide = (int)n_hide;
+        j.clear_all = n_hide == 0;
         ck.has_carry = rc.first > 0;
         if (ck.has_carry) ck.carry_in = carry ? *carry : rc.guess;
         ck.tables = rc.first == 0 && n_hide ? tables.data() : nullptr;
-        ck.n_tables = (int)std::min<long>(wv.tables_frames, rc.count) * 4;
-        ck.any_silent = wv.any_silent ? 1 : 0;   // (of the frames walked so far: at worst the re-run launches are issued without need)
+        ck.n_tables = (int)std::min<long>(w.tables_frames, rc.count) * 4;
+        ck.any_silent = w.any_silent ? 1 : 0;   // (of the frames walked so far: at worst the re-run launches are issued without need)
         if (decode) ck.dst = res->big[0].data() + 64 + (size_t)rc.first * 1152 * (size_t)nch * esz;
-        if (!prepare_chunk(P, j, s, wv.max_p23)) return kRunFallback;
-        if (issue_front(P, j, s, 0, wv.max_p23, true)) return kRunFallback;
+        if (!prepare_chunk(P, j, s, w.max_p23)) return kRunFallback;
+        if (issue_front(P, j, s, 0, w.max_p23, true)) return kRunFallback;
         if (c->opt[MP3S_OPT_FAIL_CHUNK] == (int64_t)k + 1) {      // (test aid: a hard error with this chunk's front end and the chunks in front of it in flight)
             c->opt[MP3S_OPT_FAIL_CHUNK] = 0;
             return fail(MP3S_E_HIP, "chunk %zu: failure injected by MP3S_OPT_FAIL_CHUNK", k);
@@ -307,7 +295,7 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
     long want = first_chunk;
     // (a helper thread that walks the chunks behind the first while this one queues was tried: it wakes up later than the walk takes --
     // 1.56 instead of 1.38 ms per 10 000-frame file)
-    for (size_t k = 0; !wv.ended; k++) {
+    for (size_t k = 0; k == 0 || !w.ended; k++) {
         const double t_walk0 = trace_on() ? now_ms() : 0;
         long got = 0;
         const long room = (long)refs.size() - n_walked - 8;
@@ -315,25 +303,18 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         want = std::min(want, room);
         uint8_t *tb = k == 0 && n_hide ? tables.data() : nullptr;
         while (got < want && !w.ended && !w.irregular) got += w.next(refs.data() + n_walked + got, want - got, tb ? tb + (size_t)got * 4 : nullptr, 0, 0);
-        wv.got = got; wv.ended = w.ended; wv.irregular = w.irregular || got <= 0; wv.dup_last = w.dup_last; wv.any_silent = w.any_silent;
-        wv.nch = w.nch; wv.sampling_rate = w.sampling_rate; wv.bit_rate = w.bit_rate; wv.max_p23 = w.max_p23; wv.tables_frames = w.tables_frames;
-        if (wv.ended && !wv.irregular && !wv.dup_last) {
-            bool alone = false;
-            wv.have_fix = w.decode_last(reinterpret_cast<int16_t *>(fix + 16), reinterpret_cast<mp3s_granule_si *>(fix + 16 + 4608), &alone) == 0 && alone;
-            std::memset(fix, 0, 16);
-        }
-        if (wv.irregular || got <= 0) return fallback("the walk does not take this stream");
+        if (w.irregular || got <= 0) return fallback("the walk does not take this stream");
         if (k == 0) {
-            nch = wv.nch; rate = wv.sampling_rate;
+            nch = w.nch; rate = w.sampling_rate;
             if (nch < 1 || nch > 2) return fallback("channel count");
-            if (!decode && reencode_params(wv.sampling_rate, wv.bit_rate, wv.nch, got, 0, &kbps)) return fallback("not a stream the encoder takes");
+            if (!decode && reencode_params(w.sampling_rate, w.bit_rate, w.nch, got, 0, &kbps)) return fallback("not a stream the encoder takes");
             // the result block: the frames the file can hold at its first frame's size
             res_cap = decode ? 64 + (size_t)(n_est + 64) * 1152 * (size_t)nch * esz : (size_t)(n_est + 64) * (size_t)(fs0 + 2);
             if (!res->big[0].reserve(res_cap)) return fallback("no memory for the result");
-        } else if (wv.nch != nch) return fallback("channel count changes");
-        if (wv.ended) {
-            if (wv.dup_last) return fallback("a repeated last frame");
-            have_fix = wv.have_fix;
+        } else if (w.nch != nch) return fallback("channel count changes");
+        if (w.ended) {
+            if (w.dup_last) return fallback("a repeated last frame");
+            have_fix = fill_place_entry(fix, 0, [&](int16_t *is, mp3s_granule_si *si) { bool alone = false; return w.decode_last(is, si, &alone) == 0 && alone; });
         }
         const double t_walk1 = trace_on() ? now_ms() : 0;
         if (k >= (size_t)P->depth) {               // the slot's previous chunk first
@@ -344,7 +325,7 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         const double t_ret = trace_on() ? now_ms() : 0;
         chunks.emplace_back();
         RunChunk &rc = chunks.back();
-        rc.first = n_walked; rc.count = got; rc.last = wv.ended;
+        rc.first = n_walked; rc.count = got; rc.last = w.ended;
         rc.guess.cursor = MP3S_NO_CURSOR;          // "the message is hidden, nothing is inherited"
         n_walked += got;
         if (decode && 64 + (size_t)n_walked * 1152 * (size_t)nch * esz > res_cap) return fallback("more frames than the result block holds");
@@ -360,7 +341,7 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
     }
     if (trace_on()) fprintf(stderr, "mp3s: run_file: all chunks queued %.3f ms after the call's start\n", now_ms() - t_call0);
     // ---- settle the chunks in order: the carries
-    if (!decode && (wv.sampling_rate != rate || wv.bit_rate / 1000 != kbps)) return fallback("the last header names another rate");
+    if (!decode && (w.sampling_rate != rate || w.bit_rate / 1000 != kbps)) return fallback("the last header names another rate");
     // (first everything that needs a chunk's device buffers -- its verdict, a resolve -- then the carries: a chunk that is run
     // again takes a slot, and with it the buffers of the chunk that had it last)
     for (size_t k = 0; k < chunks.size(); k++) {
@@ -397,7 +378,7 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
     }
     // ---- the result
     std::memset(out, 0, sizeof *out);
-    out->n_frames = n_walked; out->nch = nch; out->sampling_rate = wv.sampling_rate; out->bit_rate = wv.bit_rate;
+    out->n_frames = n_walked; out->nch = nch; out->sampling_rate = w.sampling_rate; out->bit_rate = w.bit_rate;
     if (decode) {
         // stego bits: the serial pass over the table-index words of all chunks (their halo frames left out)
         uint8_t carry[4] = {0, 0, 0, 0};

@@ -113,6 +113,72 @@ def test_pipe_matches_the_synchronous_calls_and_the_oracle(mlib, orc, golden_dir
     finally:
         ctx.close()
 
+
+# jobs of test_scanned_staging_gives_the_list_calls_results that are final after the first pass, measured on the commit in front of the
+# SmallHead / StagePacker refactor (MI355X, docs/LOG.md): all but the stream with the cut last frame
+PARENT_FAST_SCANNED = 5
+
+
+def test_scanned_staging_gives_the_list_calls_results(mlib, golden_dir):
+    """device_parse = 0: every job is staged by the byte-level scan (the slot's fixed areas: blob, side records, decoder headers + encoder
+    inputs, host-decoded last frames), which the default suite reaches nowhere else.  Byte for byte and status for status what
+    hide_messages / decode_streams give on the same context."""
+    from synth_pcm import synth_pcm
+    ctx = mlib.Context(0)
+    try:
+        ctx.set_option("device_parse", 0)
+        streams = []
+        for i, n in enumerate((300, 41, 120)):
+            pcm = synth_pcm(n, rate=44100, seed=177 + i)
+            if i == 2:
+                pcm[: 30 * 1152] = 0
+                pcm[60 * 1152:80 * 1152] = 0
+            streams.append(bytes(ctx.encode_pcm(pcm, 44100, 128, None)["mp3"]))
+        g = np.load(os.path.join(golden_dir, "g7_decode_corpus.npz"))
+        corpus = [g[n + "__mp3"].tobytes() for n in sorted({k.split("__")[0] for k in g.files})]
+        test_mp3 = open(os.path.join(golden_dir, "test.mp3"), "rb").read()
+        jobs = [("h", [test_mp3], ["ddd"]),
+                ("h", [streams[1]], None),                                      # clear
+                ("h", streams, ["one", None, "three"]),                         # one device batch of three streams
+                ("h", corpus, ["m%d" % i for i in range(len(corpus))]),         # per-file status
+                ("d", corpus[:2]),
+                ("h", [streams[0][:-700]], ["cut"])]                            # truncated last frame
+        want = [ctx.decode_streams(j[1], per_file=True) if j[0] == "d" else ctx.hide_messages(j[1], [None] * len(j[1]) if j[2] is None else j[2])
+                for j in jobs]
+        pipe = mlib.Pipe(ctx, depth=3, max_job_bytes=1 << 20, scan_threads=2)
+        try:
+            got, nxt = [], 0
+            while len(got) < len(jobs):
+                while nxt < len(jobs):
+                    j = jobs[nxt]
+                    if (pipe.submit_decode(j[1]) if j[0] == "d" else pipe.submit(j[1], j[2])) is None:
+                        break
+                    nxt += 1
+                got.append(pipe.collect()[1])
+            st = pipe.stats()
+        finally:
+            pipe.close()
+        for k, (job, res, w) in enumerate(zip(jobs, got, want)):
+            assert len(res) == len(w), k
+            for x, y in zip(res, w):
+                if isinstance(y, Exception):
+                    assert isinstance(x, mlib.Mp3sError) and x.code == y.code, (k, x, y)
+                    continue
+                assert not isinstance(x, Exception), (k, x)
+                assert (x["sampling_rate"], x["channels"], x["n_frames"]) == (y["sampling_rate"], y["channels"], y["n_frames"]), k
+                if job[0] == "d":
+                    assert bytes(x["data"])[44:] == y["pcm"].tobytes() and np.array_equal(x["bits"], y["bits"]), k
+                    assert x["kbps"] == y["bit_rate"] // 1000, k
+                else:
+                    assert bytes(x["data"]) == bytes(y["data"]), k
+                    assert (x["kbps"], x["too_long"], x["hide_offset"]) == (y["kbps"], y["too_long"], y["hide_offset"]), k
+        print("scanned staging:", st)
+        assert st["collected"] == len(jobs) and st["fast"] + st["resolved"] + st["slow"] == st["collected"], st
+        assert st["fast"] >= PARENT_FAST_SCANNED, st
+    finally:
+        ctx.close()
+
+
 def test_a_file_that_starts_in_silence_is_final_after_the_first_pass(mlib, orc):
     """the plan's reach follows the tables the input stream itself offers (silent units offer none): three seconds of
     silence in front of the music, a message that only starts behind them, several rounds of the selection; silences
