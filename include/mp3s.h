@@ -1104,6 +1104,71 @@ int mp3s_table_audit_dev(mp3s_ctx *ctx, const int16_t *d_is, const mp3s_frame_si
 int mp3s_table_audit_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int want_profile, mp3s_buf **owner,
                            mp3s_table_audit *out, int32_t *status);
 
+/* ---------------------------------------------------------------- (vi-f) PCM batches in the caller's device memory
+ * replaces: none -- the reference writes a WAV file (decoder/decoder.py) and reads one (encoder/WAV_Reader.py)
+ * Every other call that produces or consumes audio moves the PCM across PCIe.  The calls below leave a decoded list of MP3 files in
+ * device memory the CALLER owns (in practice a tensor) as one batch, and encode such a batch, for a caller whose next or previous step
+ * runs on the same GPU.  The batch is [B][C][T], channels first, planar, row-major: element (b, c, t) at ((b * C) + c) * T + t; C is 1
+ * or 2.  Two element formats, both made from the int16 decode (MP3S_PCM_I16, the reference's sample for sample):
+ *   MP3S_BATCH_I16: int16.   MP3S_BATCH_F32: float32 = int16 / 32768 (exact; the convention of WAV loaders).
+ * Nothing is resampled: rows are rows, and the records say which rate they run at. */
+#define MP3S_BATCH_I16 0
+#define MP3S_BATCH_F32 1
+typedef struct {
+    int64_t src_row;    /* first row of the stream in d_pcm, in rows of nch int16 (streams start on frame boundaries) */
+    int64_t n_rows;     /* rows the stream has there (>= 0) */
+    int64_t first_row;  /* where the window starts inside the stream (>= 0; may lie at or behind n_rows) */
+    int32_t slot;       /* b: the item's rows go to d_out[b][.][0..T) */
+    int32_t reserved;
+} mp3s_pcm_batch_item; /* 32 bytes */
+/* k_pcm_batch alone (k_pcmbatch.hpp), asynchronous on the context's stream: interleaved rows -> planar batch.  With
+ * valid = clamp(n_rows - first_row, 0, T), element (slot, c, t) for t < valid comes from row src_row + first_row + t of d_pcm (int16,
+ * nch = 1 or 2 samples a row, aligned to a row); on the row's int16 values l and r:
+ *   nch == out_channels: copy.   nch == 1, out_channels == 2: the sample into both planes.
+ *   nch == 2, out_channels == 1: int16 (l + r) >> 1 in int32 (arithmetic shift, so floor: -1, 0 gives -1);
+ *                                float32 (l + r) / 65536 (exact, and NOT the floored int16 / 32768).
+ * For t >= valid the element is written as zero.  Every element of an item's slot has exactly one writer, nothing has to be cleared
+ * beforehand and nothing outside [slot][0..C)[0..T) is touched; the slots of different items must differ.  Any T, any first_row and any
+ * d_out aligned to an element are taken: 16-byte stores are used wherever a plane allows them, narrower ones at its ends.  h_items is
+ * the same table on the host, read before the call returns; the launch geometry made from it travels on the stream from a buffer the
+ * context keeps, by the rule of mp3s_pcm_diff_dev.  Null pointers, n_items <= 0, nch or out_channels outside {1, 2}, an unknown format,
+ * T <= 0, a misaligned pointer or a negative field of an item: MP3S_E_ARG (checked without a device). */
+int mp3s_pcm_batch_dev(mp3s_ctx *ctx, const int16_t *d_pcm, int nch, const mp3s_pcm_batch_item *d_items,
+                       const mp3s_pcm_batch_item *h_items, int n_items, int out_channels, int out_format, int64_t T, void *d_out);
+typedef struct { int64_t dst_frame, n_rows; int32_t slot, reserved; } mp3s_pcm_unbatch_item; /* 24 bytes */
+/* k_pcm_unbatch alone, asynchronous on the context's stream: planar batch -> the encoder's frames.  d_pcm is [frames][1152][2] int16
+ * (16-byte aligned); item k fills ceil(n_rows / 1152) frames from dst_frame on with rows [0, n_rows) of d_in[slot], 1 <= n_rows <= T.
+ * Rows at and behind n_rows in the item's last frame are zero, whatever the tensor holds there.  A mono input goes into both channels
+ * (as the WAV import does with a mono file: the encoder has no mono path).  float32 becomes clamp(rint(x * 32768), -32768, 32767),
+ * rounding half to even, NaN -> 0 (the rule of mp3s_wav_import_info's float files).  The frames of different items must not overlap.
+ * Argument checks as above, n_rows outside [1, T] included. */
+int mp3s_pcm_unbatch_dev(mp3s_ctx *ctx, const void *d_in, int in_channels, int in_format, int64_t T,
+                         const mp3s_pcm_unbatch_item *d_items, const mp3s_pcm_unbatch_item *h_items, int n_items, int16_t *d_pcm);
+typedef struct { int32_t n_frames, nch, sampling_rate, bit_rate; int64_t n_rows, first_row, valid_rows; } mp3s_pcm_batch_info; /* 40 bytes */
+/* A list of MP3 files into the caller's batch d_out [n_files][out_channels][T] (device memory, out_bytes of it): the files go through
+ * the front of mp3s_decode_streams, per channel count ONE decode batch (int16) leaves the PCM in a device buffer of the context, and
+ * one k_pcm_batch launch per batch writes file i's window [first_rows[i], first_rows[i] + T) into slot i (first_rows NULL: 0).  No PCM
+ * comes down.  info[i]: the stream's header fields, n_rows as mp3s_decoded.n_rows counts them (the repeated last frame of a stream that
+ * ends in a bad header included), first_row as given and valid_rows = clamp(n_rows - first_row, 0, T), the rows of slot i that are
+ * samples; behind them the slot is zero.  status[i] by the rule of mp3s_decode_streams: with status a file that fails alone does not
+ * spoil the others (a failing batch is run again file by file), without it the first failing file fails the call.  A failed file has a
+ * zeroed info[i], a failed or frameless file valid_rows 0 and a zeroed slot.  Files of different sampling rates may share a batch.
+ * out_bytes < n_files * out_channels * T * element size, a negative first_row: MP3S_E_ARG before anything is touched.
+ * d_out == NULL is the sizing call: only the front end runs, info is filled (valid_rows 0), nothing is decoded; T and out_bytes are
+ * ignored.  The call returns behind a synchronise of the context's stream: the batch is complete for any other stream. */
+int mp3s_pcm_batch_decode_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, const int64_t *first_rows /* NULL: 0 */,
+                                int64_t T, int out_channels, int out_format, void *d_out, size_t out_bytes, mp3s_pcm_batch_info *info, int32_t *status);
+/* The items of a batch d_in [n_items][in_channels][T] in device memory as MP3 files: item i is rows [0, n_rows[i]) of slot i, its last
+ * frame zero-filled (k_pcm_unbatch), all items at one sampling rate (32 000, 44 100 or 48 000) and one bitrate, refused as
+ * mp3s_encode_pcm refuses them; hide_bits / n_hide as for mp3s_encode_files (NULL: nothing is hidden).  ONE encode batch; out[i] is
+ * what mp3s_encode_pcm gives for the item's frames (stereo, channels = 2), owned by *owner.  An item with n_rows outside [1, T] gets
+ * MP3S_E_ARG in its status and is left out of the batch; status / mp3s_last_error() by the rule of mp3s_encode_files.  The caller
+ * guarantees that the work which produced d_in has finished before the call; the call returns when the MP3 bytes are on the host, so
+ * d_in may be reused at once. */
+int mp3s_pcm_batch_encode(mp3s_ctx *ctx, const void *d_in, int n_items, int in_channels, int in_format, int64_t T, const int64_t *n_rows,
+                          int samplerate, int bitrate_kbps, const uint8_t *const *hide_bits, const int32_t *n_hide,
+                          mp3s_buf **owner, mp3s_file *out, int32_t *status);
+
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference
  *           steganography.py:133-182, whose two serial frame loops (decoder/MP3_Parser.py:68-80, encoder/MP3_Encoder.py:

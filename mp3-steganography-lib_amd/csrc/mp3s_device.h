@@ -167,6 +167,60 @@ void pcm_align_bound_pairs(const mp3s_pcm_run_pair *runs, int n_pairs, Pairs &pa
     }
 }
 
+// PCM batches in the caller's device memory (k_pcmbatch.hpp; the rules: include/mp3s.h, vi-f).  Both kernels take kPcmBatchThreads lanes
+// to a workgroup and find their item and their tile inside it in d_tiles, which the host makes (n_tiles = the grid).
+//   k_pcm_batch:   a lane owns 8 elements of a plane, counted from the 16-byte boundary in front of the plane's first element: an item
+//                  has up to ceil((T + 7) / 8) such groups a plane, whatever its n_rows is (the padding is written too)
+//   k_pcm_unbatch: a lane owns 4 rows of an item's ceil(n_rows / 1152) frames
+constexpr int kPcmBatchThreads = 256;
+struct PcmBatchTile { uint32_t item, first; };   // 8 bytes: lanes [first * kPcmBatchThreads, + kPcmBatchThreads) of item `item`
+// appends the tiles of n_items items of a batch of T elements a plane (anything with push_back); false: more tiles than a grid takes
+template <class Tiles>
+bool pcm_batch_tiles(int n_items, int64_t T, Tiles &tiles)
+{
+    if (n_items <= 0 || T <= 0 || T > ((int64_t)1 << 40)) return false;
+    const uint64_t groups = ((uint64_t)T + 6) / 8 + 1, per = (groups + kPcmBatchThreads - 1) / kPcmBatchThreads;
+    if ((uint64_t)tiles.size() + per * (uint64_t)n_items > 0x7fffffffu) return false;
+    for (int i = 0; i < n_items; i++)
+        for (uint64_t f = 0; f < per; f++) tiles.push_back(PcmBatchTile{(uint32_t)i, (uint32_t)f});
+    return true;
+}
+// ... of the items of an unbatch launch, from their row counts (each >= 1)
+template <class Tiles>
+bool pcm_unbatch_tiles(const mp3s_pcm_unbatch_item *items, int n_items, Tiles &tiles)
+{
+    uint64_t n = tiles.size();
+    for (int i = 0; i < n_items; i++) {
+        if (items[i].n_rows < 1 || items[i].n_rows > ((int64_t)1 << 40)) return false;
+        n += (((uint64_t)items[i].n_rows + 1151) / 1152 * 288 + kPcmBatchThreads - 1) / kPcmBatchThreads;
+    }
+    if (n > 0x7fffffffu) return false;
+    for (int i = 0; i < n_items; i++) {
+        const uint64_t per = (((uint64_t)items[i].n_rows + 1151) / 1152 * 288 + kPcmBatchThreads - 1) / kPcmBatchThreads;
+        for (uint64_t f = 0; f < per; f++) tiles.push_back(PcmBatchTile{(uint32_t)i, (uint32_t)f});
+    }
+    return true;
+}
+// what a launch needs of its items beside the tiles: true when every record is one the kernels may follow
+inline bool pcm_batch_items_ok(const mp3s_pcm_batch_item *items, int n_items)
+{
+    for (int i = 0; i < n_items; i++)
+        if (items[i].src_row < 0 || items[i].n_rows < 0 || items[i].first_row < 0 || items[i].slot < 0 || items[i].src_row > INT64_MAX / 4 - items[i].first_row) return false;
+    return true;
+}
+inline bool pcm_unbatch_items_ok(const mp3s_pcm_unbatch_item *items, int n_items, int64_t T)
+{
+    for (int i = 0; i < n_items; i++)
+        if (items[i].dst_frame < 0 || items[i].dst_frame > 0x7fffffff || items[i].n_rows < 1 || items[i].n_rows > T || items[i].slot < 0) return false;
+    return true;
+}
+// d_pcm: int16 rows of nch samples, aligned to a row; d_out: [slots][out_channels][T] int16 or float32, aligned to an element
+int launch_pcm_batch(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_batch_item *d_items, const PcmBatchTile *d_tiles, int n_tiles,
+                     int out_channels, int out_format, int64_t T, void *d_out);
+// d_in: [slots][in_channels][T], aligned to an element; d_pcm: [frames][1152][2] int16, 16-byte aligned
+int launch_pcm_unbatch(hipStream_t stream, const void *d_in, int in_channels, int in_format, int64_t T, const mp3s_pcm_unbatch_item *d_items,
+                       const PcmBatchTile *d_tiles, int n_tiles, int16_t *d_pcm);
+
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes

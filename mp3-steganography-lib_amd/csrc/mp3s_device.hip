@@ -32,6 +32,7 @@ __constant__ __attribute__((aligned(64))) int32_t c_fl_sign[ANALYSIS_SIGN_STREAM
 #include "k_table_audit.hpp"
 #include "k_pcmdiff.hpp"
 #include "k_pcmalign.hpp"
+#include "k_pcmbatch.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
@@ -450,6 +451,45 @@ int launch_pcm_align(hipStream_t stream, const int16_t *d_pcm, int nch, const mp
         if (const hipError_t e = hipGetLastError()) return (int)e;
     }
     hipLaunchKernelGGL(k_pcm_diff_pairs, dim3((unsigned)n_pairs), dim3(PCMDIFF_TILE), 0, stream, d_geo, d_frames, nch, d_out);
+    return (int)hipGetLastError();
+}
+
+// k_pcm_batch / k_pcm_unbatch: one workgroup per tile of d_tiles; channel counts and format are the launch's (template arguments)
+int launch_pcm_batch(hipStream_t stream, const int16_t *d_pcm, int nch, const mp3s_pcm_batch_item *d_items, const PcmBatchTile *d_tiles, int n_tiles,
+                     int out_channels, int out_format, int64_t T, void *d_out)
+{
+    if (n_tiles <= 0) return 0;
+    const bool f32 = out_format == MP3S_BATCH_F32;
+    if ((nch != 1 && nch != 2) || (out_channels != 1 && out_channels != 2) || (!f32 && out_format != MP3S_BATCH_I16) || T <= 0 ||
+        ((uintptr_t)d_pcm & (uintptr_t)(2 * nch - 1)) || ((uintptr_t)d_out & (uintptr_t)(f32 ? 3 : 1)))
+        return (int)hipErrorInvalidValue;
+#define PCM_BATCH_LAUNCH(N, C, F) hipLaunchKernelGGL((k_pcm_batch<N, C, F>), dim3((unsigned)n_tiles), dim3(PCMBATCH_THREADS), 0, stream, d_pcm, d_items, d_tiles, T, (uint8_t *)d_out)
+    switch ((nch - 1) * 4 + (out_channels - 1) * 2 + (f32 ? 1 : 0)) {
+    case 0: PCM_BATCH_LAUNCH(1, 1, false); break;
+    case 1: PCM_BATCH_LAUNCH(1, 1, true); break;
+    case 2: PCM_BATCH_LAUNCH(1, 2, false); break;
+    case 3: PCM_BATCH_LAUNCH(1, 2, true); break;
+    case 4: PCM_BATCH_LAUNCH(2, 1, false); break;
+    case 5: PCM_BATCH_LAUNCH(2, 1, true); break;
+    case 6: PCM_BATCH_LAUNCH(2, 2, false); break;
+    default: PCM_BATCH_LAUNCH(2, 2, true); break;
+    }
+#undef PCM_BATCH_LAUNCH
+    return (int)hipGetLastError();
+}
+
+int launch_pcm_unbatch(hipStream_t stream, const void *d_in, int in_channels, int in_format, int64_t T, const mp3s_pcm_unbatch_item *d_items,
+                       const PcmBatchTile *d_tiles, int n_tiles, int16_t *d_pcm)
+{
+    if (n_tiles <= 0) return 0;
+    const bool f32 = in_format == MP3S_BATCH_F32;
+    if ((in_channels != 1 && in_channels != 2) || (!f32 && in_format != MP3S_BATCH_I16) || T <= 0 || ((uintptr_t)d_pcm & 15) ||
+        ((uintptr_t)d_in & (uintptr_t)(f32 ? 3 : 1)))
+        return (int)hipErrorInvalidValue;
+#define PCM_UNBATCH_LAUNCH(C, F) hipLaunchKernelGGL((k_pcm_unbatch<C, F>), dim3((unsigned)n_tiles), dim3(PCMBATCH_THREADS), 0, stream, (const uint8_t *)d_in, d_items, d_tiles, T, d_pcm)
+    if (in_channels == 1) { if (f32) PCM_UNBATCH_LAUNCH(1, true); else PCM_UNBATCH_LAUNCH(1, false); }
+    else { if (f32) PCM_UNBATCH_LAUNCH(2, true); else PCM_UNBATCH_LAUNCH(2, false); }
+#undef PCM_UNBATCH_LAUNCH
     return (int)hipGetLastError();
 }
 

@@ -50,9 +50,9 @@ using namespace mp3s;
 enum PoolSlot : int {
     kPoolIs0, kPoolSi0,     // Huffman output of a decode batch (decode_front) or of set 0 of a pipe: samples [frames][2][2][576] int16, granule records
     kPoolFrameHdr, kPoolPcmChunk, kPoolHufStatus, kPoolMainData, kPoolSideInfo,   // decode_front: headers, a chunk of PCM on its way down, Huffman status, main data, side records
-    kPoolPcm0,              // int16 PCM that stays on the device: reencode_decode, the pair calls, wav_to_device, set 0 of a pipe; the table audit, which decodes no PCM, keeps its unit records here
+    kPoolPcm0,              // int16 PCM that stays on the device: reencode_decode, the pair calls, wav_to_device, the PCM batch calls (mp3s_pcm_batch.cpp), set 0 of a pipe; the table audit, which decodes no PCM, keeps its unit records here
     kPoolPcmUp,             // the PCM an encode brings from the host (encode_batch without pcm_dev)
-    kPoolInputs,            // the host-made input block of the call: the encoder's (EncLayout), the pair calls', the audit's stream table, the workgroup tables of mp3s_pcm_diff_dev / mp3s_pcm_align_dev
+    kPoolInputs,            // the host-made input block of the call: the encoder's (EncLayout), the pair calls', the audit's stream table, the workgroup tables of mp3s_pcm_diff_dev / mp3s_pcm_align_dev, [items | workgroup table] of the PCM batch launches
     kPoolMdct,              // encode_batch, capacity_batch: MDCT lines [n_all][2][2][576]
     kPoolRedo,              // enc_resolve: entries of the exact re-runs
     kPoolIx, kPoolGrOut, kPoolEnergy,   // encode_batch, capacity_batch: quantised lines, GrInfo records, band energies
@@ -126,6 +126,8 @@ struct mp3s_ctx {
     hipEvent_t ev_pcm_tiles = nullptr;
     // ... and the block [workgroup table | given lags] of the last mp3s_pcm_align_dev, by the same rule and behind the same event
     std::vector<uint8_t> h_pcm_align;
+    // ... and the block [items | workgroup table] of the last PCM batch launch (mp3s_pcm_batch.cpp), by the same rule and behind the same event
+    std::vector<uint8_t> h_pcm_batch;
     static int ensure(void *&buf, size_t &have, size_t bytes)
     {
         if (bytes <= have) return 0;

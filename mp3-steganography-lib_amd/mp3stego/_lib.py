@@ -220,6 +220,35 @@ PCM_LAG_DTYPE = np.dtype([("lag", "<i4"), ("n_best", "<u4"), ("err2_best", "<u8"
 PCM_MAX_LAG = 4608           # MP3S_PCM_MAX_LAG
 
 
+class PcmBatchItem(C.Structure):
+    _fields_ = [("src_row", C.c_int64), ("n_rows", C.c_int64), ("first_row", C.c_int64), ("slot", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PcmUnbatchItem(C.Structure):
+    _fields_ = [("dst_frame", C.c_int64), ("n_rows", C.c_int64), ("slot", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PcmBatchInfo(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
+                ("n_rows", C.c_int64), ("first_row", C.c_int64), ("valid_rows", C.c_int64)]
+
+
+PCM_BATCH_ITEM_DTYPE = np.dtype([("src_row", "<i8"), ("n_rows", "<i8"), ("first_row", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
+PCM_UNBATCH_ITEM_DTYPE = np.dtype([("dst_frame", "<i8"), ("n_rows", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
+PCM_BATCH_INFO_DTYPE = np.dtype([("n_frames", "<i4"), ("nch", "<i4"), ("sampling_rate", "<i4"), ("bit_rate", "<i4"),
+                                 ("n_rows", "<i8"), ("first_row", "<i8"), ("valid_rows", "<i8")])
+BATCH_I16, BATCH_F32 = 0, 1  # MP3S_BATCH_*: int16, float32 = int16 / 32768
+BATCH_FORMATS = {"i16": BATCH_I16, "f32": BATCH_F32, BATCH_I16: BATCH_I16, BATCH_F32: BATCH_F32}
+BATCH_DTYPES = {BATCH_I16: np.dtype(np.int16), BATCH_F32: np.dtype(np.float32)}
+
+
+def _addr(p):
+    """a device address as ctypes takes it: a c_void_p (Context.alloc), an int (an address with an offset, a tensor's data_ptr()) or None"""
+    if p is None:
+        return None
+    return C.c_void_p(p.value if isinstance(p, C.c_void_p) else int(p))
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_frames", C.c_int64), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
                 ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("reserved", C.c_int32)]
@@ -275,7 +304,8 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages",
            "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes",
            "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files", "mp3s_pcm_align_dev", "mp3s_pcm_alignment_files",
-           "mp3s_table_audit_dev", "mp3s_table_audit_files"]
+           "mp3s_table_audit_dev", "mp3s_table_audit_files",
+           "mp3s_pcm_batch_dev", "mp3s_pcm_unbatch_dev", "mp3s_pcm_batch_decode_files", "mp3s_pcm_batch_encode"]
 
 REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
 RV_BAD_REF = 1
@@ -399,6 +429,10 @@ def lib():
         L.mp3s_pcm_distortion_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, pvp, vp, vp]
         L.mp3s_pcm_align_dev.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
         L.mp3s_pcm_alignment_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, pvp, vp, vp]
+        L.mp3s_pcm_batch_dev.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i64, vp]
+        L.mp3s_pcm_unbatch_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp]
+        L.mp3s_pcm_batch_decode_files.argtypes = [vp, vp, vp, i32, vp, i64, i32, i32, vp, sz, vp, vp]
+        L.mp3s_pcm_batch_encode.argtypes = [vp, vp, i32, i32, i32, i64, vp, i32, i32, vp, vp, pvp, vp, vp]
         L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
@@ -1217,6 +1251,83 @@ class Context:
             for p in (d_pcm, d_runs, d_scores, d_lags, d_frames, d_out):
                 if p is not None:
                     self.free(p)
+
+    # ---- PCM batches in the caller's device memory (include/mp3s.h section vi-f)
+    def pcm_batch_dev(self, d_pcm, nch, d_items, items, channels, fmt, rows, d_out):
+        """test aid: k_pcm_batch alone (mp3s_pcm_batch_dev), asynchronous on the context's stream.  d_pcm, d_items and d_out are device
+        addresses (Context.alloc / to_device, or an int: an address with an offset), `items` the PCM_BATCH_ITEM_DTYPE records d_items
+        holds; interleaved int16 rows of nch samples -> planar [slots][channels][rows] of fmt ("i16" / "f32")"""
+        items = np.ascontiguousarray(items, dtype=PCM_BATCH_ITEM_DTYPE)
+        check(lib().mp3s_pcm_batch_dev(self.handle, _addr(d_pcm), int(nch), _addr(d_items), items.ctypes.data, len(items), int(channels),
+                                       BATCH_FORMATS[fmt], int(rows), _addr(d_out)))
+
+    def pcm_unbatch_dev(self, d_in, channels, fmt, rows, d_items, items, d_pcm):
+        """test aid: k_pcm_unbatch alone (mp3s_pcm_unbatch_dev), asynchronous on the context's stream: planar [slots][channels][rows] at
+        d_in -> int16 frames [frames][1152][2] at d_pcm, by the PCM_UNBATCH_ITEM_DTYPE records `items` (d_items: the same on the device)"""
+        items = np.ascontiguousarray(items, dtype=PCM_UNBATCH_ITEM_DTYPE)
+        check(lib().mp3s_pcm_unbatch_dev(self.handle, _addr(d_in), int(channels), BATCH_FORMATS[fmt], int(rows), _addr(d_items),
+                                         items.ctypes.data, len(items), _addr(d_pcm)))
+
+    def decode_batch(self, mp3s, d_out, out_bytes, rows, first_rows=None, channels=2, fmt="f32", per_file=False):
+        """Decode a list of MP3 files into the caller's device memory as ONE planar batch [len(mp3s)][channels][rows] of fmt ("f32":
+        int16 / 32768, or "i16") at the device address d_out (mp3s_pcm_batch_decode_files): file i's rows from first_rows[i] (0) on
+        into slot i, zeros behind its last row; no PCM comes down.  Returns one dict per file: n_frames, channels, sampling_rate,
+        bit_rate, n_rows, first_row, valid_rows (the rows of the slot that are samples).  per_file=True: a file that cannot be
+        decoded (None included) yields the Mp3sError it alone would raise and a zeroed slot, the others are unaffected; otherwise
+        the first such file fails the call.  d_out=None: the sizing call -- only the front end runs, valid_rows is 0."""
+        n = len(mp3s)
+        if n == 0:
+            return []
+        _, _keep, ptrs, lens = _file_list([b"" if f is None else f for f in mp3s])
+        for i, f in enumerate(mp3s):
+            if f is None:
+                ptrs[i] = None
+        first = None
+        if first_rows is not None:
+            if len(first_rows) != n:
+                raise ValueError("one first row per file")
+            first = (C.c_int64 * n)(*[int(x) for x in first_rows])
+        info, status = (PcmBatchInfo * n)(), (C.c_int32 * n)()
+        check(lib().mp3s_pcm_batch_decode_files(self.handle, ptrs, lens, n, first, int(rows), int(channels), BATCH_FORMATS[fmt], _addr(d_out),
+                                                int(out_bytes), info, status if per_file else None))
+        return _per_file(info, status, lambda x: {
+            "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate, "n_rows": x.n_rows,
+            "first_row": x.first_row, "valid_rows": x.valid_rows})
+
+    def batch_rows(self, mp3s, per_file=False):
+        """the sizing call of decode_batch: the dicts it returns ("n_rows" = the rows file i decodes to), from the host front end alone"""
+        return self.decode_batch(mp3s, None, 0, 0, per_file=per_file)
+
+    def encode_batch(self, d_in, n_items, channels, fmt, rows, lengths, samplerate, bitrate=320, hide_bits=None, messages=None, per_file=False):
+        """Encode the items of a planar batch [n_items][channels][rows] of fmt at the device address d_in as ONE device batch
+        (mp3s_pcm_batch_encode): item i is its first lengths[i] rows (1 .. rows), the last frame zero-filled, mono into both channels,
+        float32 rounded to int16 half-even.  hide_bits / messages as for encode_files.  Whatever wrote d_in must have finished.
+        Returns the dicts encode_files returns; per_file=True: an item that fails (a length outside 1 .. rows) yields its Mp3sError,
+        otherwise the first such item fails the call."""
+        n = int(n_items)
+        if len(lengths) != n:
+            raise ValueError("one length per item")
+        if hide_bits is not None and messages is not None:
+            raise ValueError("hide_bits or messages, not both")
+        if messages is not None:
+            hide_bits = [None if m is None else np.array(message_frame(m), dtype=np.uint8) for m in messages]
+        hbs = hptr = hlen = None
+        if hide_bits is not None:
+            if len(hide_bits) != n:
+                raise ValueError("one bit string (or None) per item")
+            hbs = [None if h is None or not len(h) else np.ascontiguousarray(h, dtype=np.uint8) for h in hide_bits]
+            hptr = (C.c_void_p * n)(*[None if h is None else h.ctypes.data for h in hbs])
+            hlen = (C.c_int32 * n)(*[0 if h is None else len(h) for h in hbs])
+        nr = (C.c_int64 * max(n, 1))(*[int(x) for x in lengths])
+        out, status, owner = (File * max(n, 1))(), (C.c_int32 * max(n, 1))(), C.c_void_p()
+        check(lib().mp3s_pcm_batch_encode(self.handle, _addr(d_in), n, int(channels), BATCH_FORMATS[fmt], int(rows), nr, int(samplerate),
+                                          int(bitrate), hptr, hlen, C.byref(owner), out, status if per_file else None))
+        own = _Owner(owner)
+        del hbs
+        return _per_file(out, status, lambda f: {
+            "data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
+            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
+            "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)}, n=n)
 
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""

@@ -1,0 +1,87 @@
+"""MP3 lists as torch tensors that never leave the GPU (include/mp3s.h section vi-f).
+
+decode() leaves a list of MP3 files in a device tensor [B, C, T] -- channels first, planar, float32 = int16 / 32768 or int16 -- and
+encode() makes MP3 files (with hidden messages, if asked) of such a tensor.  The samples do not cross PCIe in either direction: the
+library's kernels read and write the tensor's memory.
+
+This is the only module of the package that imports torch, and it does so when a function is first called: the C library and
+mp3stego._lib stay torch-free.  The library works on its context's own stream; both functions synchronise torch's current stream of
+the device before the call, and the library's stream has been synchronised when they return.
+"""
+from mp3stego import _lib
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _formats(torch):
+    return {torch.int16: "i16", torch.float32: "f32"}
+
+
+def _check(torch, t, ctx, what):
+    """the tensor the library is handed: [B, C, T], int16 or float32, contiguous, on the context's device"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError(f"{what}: a tensor [B, C, T] is expected")
+    if t.dtype not in _formats(torch):
+        raise ValueError(f"{what}: dtype {t.dtype}, int16 or float32 is expected")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: the tensor is not contiguous")
+    if t.device.type != "cuda" or t.device.index != ctx.device:
+        raise ValueError(f"{what}: the tensor is on {t.device}, the context works on cuda:{ctx.device}")
+    if t.shape[1] not in (1, 2):
+        raise ValueError(f"{what}: {t.shape[1]} channels, 1 or 2 are expected")
+
+
+def decode(mp3s, rows=None, first_rows=None, channels=2, dtype=None, ctx=None, out=None, per_file=False):
+    """Decode the MP3 files `mp3s` (byte strings; None: a missing file) into one device tensor.
+
+    Returns (batch, lengths, infos): batch [len(mp3s), channels, T] of dtype (torch.float32, the default: int16 / 32768, or torch.int16)
+    on the context's device, file i's rows from first_rows[i] (0) on in batch[i], zeros behind them; lengths: an int64 CPU tensor of
+    the rows of each slot that are samples; infos: the dicts of Context.decode_batch (per_file=True: the Mp3sError of a file that
+    cannot be decoded, whose slot is zero and whose length is 0; otherwise such a file fails the call).
+    rows=None sizes T as the largest n_rows - first_row of the list, which costs one more run of the host front end over the files
+    (Context.batch_rows); say rows when you know it.  A stereo file into channels=1 is (l + r) / 2, a mono file into channels=2 goes
+    into both planes.  Nothing is resampled: infos[i]["sampling_rate"] says what the rows of a slot are.
+    out= reuses a tensor of the caller's ([len(mp3s), C, T]: channels, dtype and rows are taken from it); the work torch's current
+    stream has pending on it is waited for first."""
+    torch = _torch()
+    ctx = ctx or _lib.default_context()
+    n = len(mp3s)
+    if n == 0:
+        raise ValueError("an empty list")
+    device = torch.device("cuda", ctx.device)
+    if out is not None:
+        _check(torch, out, ctx, "out")
+        if out.shape[0] != n:
+            raise ValueError(f"out: {out.shape[0]} slots for {n} files")
+        channels, dtype, rows = int(out.shape[1]), out.dtype, int(out.shape[2])
+    else:
+        dtype = dtype or torch.float32
+        if dtype not in _formats(torch):
+            raise ValueError(f"dtype {dtype}, int16 or float32 is expected")
+        if rows is None:
+            firsts = first_rows if first_rows is not None else [0] * n
+            sized = ctx.batch_rows(mp3s, per_file=per_file)
+            rows = max([1] + [s["n_rows"] - int(f) for s, f in zip(sized, firsts) if not isinstance(s, Exception)])
+        out = torch.empty((n, int(channels), int(rows)), dtype=dtype, device=device)
+    torch.cuda.current_stream(device).synchronize()       # (the memory may be a block torch's stream has not finished with)
+    infos = ctx.decode_batch(mp3s, out.data_ptr(), out.numel() * out.element_size(), int(rows), first_rows, int(channels),
+                             _formats(torch)[dtype], per_file)
+    lengths = torch.tensor([0 if isinstance(i, Exception) else i["valid_rows"] for i in infos], dtype=torch.int64)
+    return out, lengths, infos
+
+
+def encode(batch, lengths, samplerate, bitrate=320, messages=None, hide_bits=None, ctx=None, per_file=False):
+    """Encode the items of the device tensor `batch` [B, C, T] (int16, or float32 in [-1, 1): clamp(rint(x * 32768))) as MP3 files:
+    item i is batch[i, :, :lengths[i]], its last frame zero-filled, a mono item in both channels of the (stereo) file.  messages /
+    hide_bits as for Context.encode_files.  torch's current stream is synchronised before the call, so what wrote the batch there has
+    finished; the batch may be reused when the call returns.  Returns the dicts of Context.encode_batch."""
+    torch = _torch()
+    ctx = ctx or _lib.default_context()
+    _check(torch, batch, ctx, "batch")
+    lengths = [int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    torch.cuda.current_stream(batch.device).synchronize()
+    return ctx.encode_batch(batch.data_ptr(), batch.shape[0], batch.shape[1], _formats(torch)[batch.dtype], batch.shape[2], lengths,
+                            samplerate, bitrate, hide_bits, messages, per_file)
