@@ -1,7 +1,7 @@
 // C-ABI of the library (include/mp3s.h), part 1: context, device memory, timers, the resident-batch entry points and the
 // host stages.  The stream / file pipelines live in mp3s_decode_pipeline.cpp and mp3s_encode_pipeline.cpp.  No CPU
 // fallback exists for the transforms: every path that needs them goes through launch_* in mp3s_device.hip.
-#include "mp3s_internal.h"
+#include "chain_resolve.h"
 
 namespace {
 thread_local std::string g_err;
@@ -160,6 +160,7 @@ int mp3s_ctx_create(int device, mp3s_ctx **out)
     e = hipSetDevice(device);
     if (e != hipSuccess) return fail(MP3S_E_NO_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
     mp3s_ctx *c = new mp3s_ctx();
+    c->chain = new ChainResolver();
     c->device = device;
     for (const OptRow &o : kOptions) c->opt[o.id] = option_from_env(o);   // the environment provides the defaults, once
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -200,6 +201,7 @@ void mp3s_ctx_destroy(mp3s_ctx *c)
     if (c->ev_sel) hipEventDestroy(c->ev_sel);
     if (c->ev_pcm_tiles) hipEventDestroy(c->ev_pcm_tiles);
     if (c->stream) hipStreamDestroy(c->stream);
+    delete c->chain;
     delete c;
 }
 

@@ -3,12 +3,21 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <cerrno>
-#include "mp3s_internal.h"
+#include "chain_resolve.h"
 
-// message bits the frames in front of a block have taken
-static int64_t cursor0(const EncSeg &s)
+// the stream as the device's chain check and selection see it (chain_in stays zero: enc_fill's to add)
+static mp3s_chain_seg chain_seg_of(const EncSeg &s)
 {
-    return s.carry_in ? std::min<int64_t>(std::max<int64_t>(s.carry_in->cursor, 0), kNoCursor) : 0;
+    mp3s_chain_seg cs = mp3s_chain_seg();
+    cs.first_frame = s.first; cs.n_frames = s.n_frames; cs.hide_base = s.hide_base;
+    cs.hide_begin = (int32_t)((int64_t)s.hide_base + cursor0(s)); cs.hide_end = s.hide_base + s.n_hide;   // (both below 2^30)
+    return cs;
+}
+
+// units of the stream that tables_guess covers
+static int64_t guess_units(const EncSeg &s)
+{
+    return s.n_guess < 0 ? (int64_t)s.n_frames * 4 : std::min<int64_t>(s.n_guess, (int64_t)s.n_frames * 4);
 }
 
 int enc_layout(std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncLayout &L, bool select)
@@ -40,12 +49,7 @@ int enc_layout(std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncL
     // ---- the streams whose message cursor the device decides (mp3s_select_plan's rule)
     std::vector<mp3s_chain_seg> cs(segs.size());
     std::vector<mp3s_select_span> spans(segs.size());
-    for (size_t si = 0; si < segs.size(); si++) {
-        const EncSeg &s = segs[si];
-        cs[si] = mp3s_chain_seg();
-        cs[si].first_frame = s.first; cs[si].n_frames = s.n_frames; cs[si].hide_base = s.hide_base;
-        cs[si].hide_begin = (int32_t)((int64_t)s.hide_base + cursor0(s)); cs[si].hide_end = s.hide_base + s.n_hide;
-    }
+    for (size_t si = 0; si < segs.size(); si++) cs[si] = chain_seg_of(segs[si]);
     // every unit a message can reach costs 8 to MP3S_SELECT_VARIANTS entries (1.3 KB each in HBM, one more wave of the
     // rate loop); the alternative for a stream left out is the host resolving its chains, which runs 8 variants per unit
     // as well and needs the host in the middle of the job (a 14 KB message in 10 000 frames: 5.7 ms here, 5.6 ms and more
@@ -62,7 +66,7 @@ int enc_layout(std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncL
     // guess costs time only: the check's verdict then sends the job to the host as before.
     L.redo = false;
     for (const EncSeg &s : segs) {
-        const size_t known = s.n_guess < 0 ? (size_t)s.n_frames * 4 : (size_t)std::min(s.n_guess, s.n_frames * 4);
+        const size_t known = (size_t)guess_units(s);
         if (s.any_silent >= 0 ? s.any_silent != 0 : (!s.tables_guess || known < (size_t)s.n_frames * 4 || std::memchr(s.tables_guess, 0, known))) L.redo = true;
     }
     std::vector<int32_t> min_reach(segs.size(), 0);
@@ -72,7 +76,7 @@ int enc_layout(std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncL
         if (!s.tables_guess || left <= 0) continue;
         const int64_t need = left + left / 16 + 48;
         int64_t offered = 0, j = 0;
-        const int64_t known = s.n_guess < 0 ? (int64_t)s.n_frames * 4 : std::min<int64_t>(s.n_guess, (int64_t)s.n_frames * 4);
+        const int64_t known = guess_units(s);
         while (j < known && offered < need) offered += s.tables_guess[j++];
         if (offered < need) j += (need - offered) * 5 / 14;   // behind what is known of the stream: 2.8 tables per unit
         min_reach[si] = (int32_t)std::min<int64_t>((int64_t)s.n_frames * 4, j + 32);
@@ -115,60 +119,50 @@ static bool enc_pool_buffers(mp3s_ctx *c, const EncLayout &L, bool want_pcm, boo
 int enc_fill(std::vector<EncSeg> &segs, EncLayout &L, uint8_t *dst)
 {
     std::memset(dst, 0, L.bytes);
-    mp3s_frame_hdr *hdr = (mp3s_frame_hdr *)dst;
-    mp3s_rate_frame *rf = (mp3s_rate_frame *)(dst + L.o_rf);
-    int32_t *cursor = (int32_t *)(dst + L.o_cur);
-    uint8_t *hide_all = dst + L.o_hide;          // [patterns | message of stream 0 | message of stream 1 ...]
-    mp3s_chain_seg *cs = (mp3s_chain_seg *)(dst + L.o_segs);
-    uint32_t *off = (uint32_t *)(dst + L.o_off);
-    uint8_t *pad8 = dst + L.o_pad;
-    mp3s_select_span *spans = (mp3s_select_span *)(dst + L.o_spans);
-    mp3s_select_patterns(hide_all);
+    const EncBlock<uint8_t> blk = enc_block(L, dst);
+    mp3s_select_patterns(blk.hide);
     std::vector<int32_t> padding;
     L.bytes_before = 0;
     for (size_t si = 0; si < segs.size(); si++) {
         EncSeg &s = segs[si];
         // padding / slot lag restart with every stream (MP3_Encoder.py:623-636)
         padding.resize((size_t)s.n_frames);
-        const int rc = rate_frames(L.samplerate, L.kbps, 2, s.n_frames, rf + s.first, padding.data(), s.first_frame, &L.bytes_before);
+        const int rc = rate_frames(L.samplerate, L.kbps, 2, s.n_frames, blk.rf + s.first, padding.data(), s.first_frame, &L.bytes_before);
         if (rc) return fail(rc, "unsupported samplerate/bitrate %d/%d", L.samplerate, L.kbps);
         for (int f = s.first; f < s.first + s.n_frames; f++) {
-            rf[f].hide_end = s.hide_base + s.n_hide;
-            rf[f].stream = (int32_t)si;
-            pad8[f] = (uint8_t)padding[(size_t)(f - s.first)];
+            blk.rf[f].hide_end = s.hide_base + s.n_hide;
+            blk.rf[f].stream = (int32_t)si;
+            blk.pad[f] = (uint8_t)padding[(size_t)(f - s.first)];
         }
         for (int f = s.first; f < s.first + s.n_frames + L.lead; f++) {
-            hdr[f].sr_idx = (uint8_t)L.sri; hdr[f].nch = 2; hdr[f].ms_stereo = 0; hdr[f].flags = 0; hdr[f].stream_first = (uint32_t)s.first;
+            mp3s_frame_hdr &h = blk.hdr[f];
+            h.sr_idx = (uint8_t)L.sri; h.nch = 2; h.ms_stereo = 0; h.flags = 0; h.stream_first = (uint32_t)s.first;
         }
-        if (s.n_hide) std::memcpy(hide_all + s.hide_base, s.hide, (size_t)s.n_hide);
+        if (s.n_hide) std::memcpy(blk.hide + s.hide_base, s.hide, (size_t)s.n_hide);
         // A unit sees the message only through the <= 3 bits at its cursor.  First pass: guess three tables per unit (for
         // a short message in a long stream that is almost always right); a long message is left to the variants.
         // A stream with a plan (reach > 0) needs no guess: its units run "behind every message" and the variants, in the
         // same launch, cover what the message can reach; the selection writes the cursors the units really saw.
-        const int64_t c0 = cursor0(s);
+        const int64_t c0 = cursor0(s), known = s.tables_guess ? guess_units(s) : 0;
         const bool long_msg = s.reach > 0 || s.n_hide - c0 > kLongMessageBits;
         int64_t ahead = 0;               // tables the units in front are expected to take
         for (int j = 0; j < s.n_frames * 4; j++) {
-            cursor[(size_t)s.first * 4 + j] = long_msg ? kNoCursor : (int32_t)std::min<int64_t>((int64_t)s.hide_base + c0 + ahead, kNoCursor);
-            ahead += s.tables_guess && (s.n_guess < 0 || j < s.n_guess) ? s.tables_guess[j] : 3;
+            blk.cursor[(size_t)s.first * 4 + j] = long_msg ? kNoCursor : (int32_t)std::min<int64_t>((int64_t)s.hide_base + c0 + ahead, kNoCursor);
+            ahead += j < known ? s.tables_guess[j] : 3;
         }
-        spans[si].first_entry = s.first_entry; spans[si].reach = s.reach;
-        cs[si].first_frame = s.first; cs[si].n_frames = s.n_frames;
-        cs[si].hide_base = s.hide_base; cs[si].hide_begin = (int32_t)((int64_t)s.hide_base + c0);   // (both below 2^30)
-        cs[si].hide_end = s.hide_base + s.n_hide;
-        if (s.carry_in) std::memcpy(cs[si].chain_in, s.carry_in->chain, sizeof cs[si].chain_in);
+        blk.spans[si].first_entry = s.first_entry; blk.spans[si].reach = s.reach;
+        blk.segs[si] = chain_seg_of(s);
+        if (s.carry_in) std::memcpy(blk.segs[si].chain_in, s.carry_in->chain, sizeof blk.segs[si].chain_in);
     }
-    if (L.n_entries > 0) {
-        int32_t *ent = (int32_t *)(dst + L.o_ent);
+    if (L.n_entries > 0)
         for (const auto &s : segs)
-            if (s.reach > 0) select_entries(s.first * 4, s.reach, s.first_entry, s.hide_base + s.n_hide, (int64_t)s.n_hide - cursor0(s), ent, ent + L.n_entries);
-    }
-    off[0] = 0;
-    for (int f = 0; f < L.n; f++) off[f + 1] = off[f] + (uint32_t)(L.whole + pad8[f]);
-    L.mp3_bytes = off[L.n];
+            if (s.reach > 0) select_entries(s.first * 4, s.reach, s.first_entry, s.hide_base + s.n_hide, (int64_t)s.n_hide - cursor0(s), blk.ent_unit, blk.ent_cursor);
+    blk.off[0] = 0;
+    for (int f = 0; f < L.n; f++) blk.off[f + 1] = blk.off[f] + (uint32_t)(L.whole + blk.pad[f]);
+    L.mp3_bytes = blk.off[L.n];
     for (auto &s : segs) {
-        s.mp3_off = off[s.first];
-        s.mp3_len = off[s.first + s.n_frames] - off[s.first];
+        s.mp3_off = blk.off[s.first];
+        s.mp3_len = blk.off[s.first + s.n_frames] - blk.off[s.first];
         // the reference drops the cached tail (< 32 bits) at the end of the stream: E14
         if (s.last) s.mp3_len -= std::min<size_t>(s.mp3_len, (size_t)((L.bytes_before + (int64_t)s.mp3_len) % 4));
     }
@@ -194,20 +188,18 @@ void tables_guess_of(const mp3s_frame_side *side, long n_frames, int extra, std:
 
 int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail, hipEvent_t tail_from, hipEvent_t pcm_read)
 {
-    const mp3s_frame_hdr *d_hdr = (const mp3s_frame_hdr *)d.d_in;
-    const mp3s_rate_frame *d_rf = (const mp3s_rate_frame *)(d.d_in + L.o_rf);
-    int32_t *d_cur = const_cast<int32_t *>((const int32_t *)(d.d_in + L.o_cur));   // (written by the selection and the chain check's re-runs)
-    const uint8_t *d_hide = d.d_in + L.o_hide;
-    const mp3s_chain_seg *d_segs = (const mp3s_chain_seg *)(d.d_in + L.o_segs);
-    const mp3s_select_span *d_spans = (const mp3s_select_span *)(d.d_in + L.o_spans);
-    const int32_t *d_ent = (const int32_t *)(d.d_in + L.o_ent);
+    const EncBlock<const uint8_t> in = enc_block(L, d.d_in);
+    const mp3s_rate_frame *d_rf = in.rf;
+    int32_t *d_cur = const_cast<int32_t *>(in.cursor);   // (written by the selection and the chain check's re-runs)
+    const uint8_t *d_hide = in.hide;
+    const mp3s_chain_seg *d_segs = in.segs;
     const int32_t *d_mdct = d.d_mdct_all + (size_t)L.lead * 2304;   // the block's own frames
-    int rc = encode_transform_step(c, c->stream, d.d_pcm, d_hdr, L.n_all, d.d_mdct_all);
+    int rc = encode_transform_step(c, c->stream, d.d_pcm, in.hdr, L.n_all, d.d_mdct_all);
     if (!rc && pcm_read && hipEventRecord(pcm_read, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "event record failed");   // the PCM buffer may be written again
     // short messages (L.n_entries > 0): their variants run in the rate loop's launch and the device decides the cursor chain (no guess).  With a
     // tail stream the selection (two small launches) belongs to the tail: the compute stream is free for the next job's decode transforms 25 us
     // earlier.  The variant buffers are the context's: a rate loop that writes them waits for the selection in front of it (rate_step).
-    const RateVariantArgs va = variant_args(d_ent, d_ent + L.n_entries, L.n_entries, d.d_ixv, d.d_outv, d.d_env);
+    const RateVariantArgs va = variant_args(in.ent_unit, in.ent_cursor, L.n_entries, d.d_ixv, d.d_outv, d.d_env);
     // with a tail stream the rate loop is the compute stream's last launch of the job and the tail waits for IT: its dispatch carries
     // tail_from as its own completion signal (a record would be a packet of its own in the queue: 7-8 us of nothing in front of the
     // next job's decode, tools/timeline.sh)
@@ -221,7 +213,7 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
     const hipStream_t ts = tail ? tail : c->stream;
     if (!rc && tail && ((!rate_signals && hipEventRecord(tail_from, c->stream) != hipSuccess) || hipStreamWaitEvent(tail, tail_from, 0) != hipSuccess))
         rc = fail(MP3S_E_HIP, "ordering the tail stream failed");
-    if (!rc && L.n_entries > 0) rc = select_step(c, ts, d_hide, d_cur, d_segs, d_spans, L.n_segs, L.max_reach, va, d.d_ix, d.d_out, d.d_en);
+    if (!rc && L.n_entries > 0) rc = select_step(c, ts, d_hide, d_cur, d_segs, in.spans, L.n_segs, L.max_reach, va, d.d_ix, d.d_out, d.d_en);
     if (!rc) {
         // (with the device's own re-runs of the units that inherited other addresses than the zeros they were given)
         const ChainRedoArgs redo = {d_mdct, d_hide, L.n_hide, d.d_ix, d.d_en};
@@ -238,7 +230,7 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
     if (!rc) {
         const bool halves = d.direct_status && d.pack_half && d.pack_split > 0 && d.pack_split < L.n;
         auto pack = [&](int32_t *d_sync, int f_begin, int f_end) {
-            return launch_pack(ts, d.d_ix, d.d_out, d.d_en, L.n, L.sri, L.bri, L.whole, (const uint32_t *)(d.d_in + L.o_off), d.d_in + L.o_pad, d.d_mp3, d.d_sc,
+            return launch_pack(ts, d.d_ix, d.d_out, d.d_en, L.n, L.sri, L.bri, L.whole, in.off, in.pad, d.d_mp3, d.d_sc,
                                &d.d_small->pack_status, d_sync, &c->prof, f_begin, f_end);
         };
         int e = pack(d.direct_status ? nullptr : c->d_sync, 0, halves ? d.pack_split : -1);
@@ -249,20 +241,18 @@ int enc_issue(mp3s_ctx *c, const EncLayout &L, const EncDev &d, hipStream_t tail
 }
 
 // The guesses of the first pass did not hold (verdict != 0): resolve the serial chains on the host -- the GrInfo of the
-// first pass comes down, walk() finds the units that ran on wrong inputs, message variants and exact re-runs replace them,
-// and the frames are packed again.  `in` = the host copy of the input block enc_fill wrote, `d` = the device buffers of
+// first pass comes down, the context's ChainResolver (chain_resolve.h) finds the units that ran on wrong inputs, message
+// variants and exact re-runs replace them, and the frames are packed again.  Every decision is the resolver's; here are the
+// buffers, the copies and the launches.  `in` = the host copy of the input block enc_fill wrote, `d` = the device buffers of
 // the first pass (its mdct / ix / GrInfo / energies must still be there).  Results as encode_batch's.
 int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, const uint8_t *in, const EncDev &d, mp3s_buf *b, bool have_gr,
                 int *passes_out)
 {
     const int n = L.n, units = L.units, n_hide = L.n_hide;
-    const uint8_t *hide_all = in + L.o_hide;
-    const uint8_t *const d_in = d.d_in;
+    const EncBlock<const uint8_t> host = enc_block(L, in), dev = enc_block(L, d.d_in);
     int16_t *const d_ix = d.d_ix; mp3s_gr_out *const d_out = d.d_out; int32_t *const d_en = d.d_en; uint8_t *const d_mp3 = d.d_mp3;
     int32_t *const d_sc = d.d_sc, *const d_pack_status = &d.d_small->pack_status;
     const int32_t *d_mdct = d.d_mdct_all + (size_t)L.lead * 2304;   // the block's own frames
-    const mp3s_rate_frame *d_rf = (const mp3s_rate_frame *)(d_in + L.o_rf);
-    const uint8_t *d_hide = d_in + L.o_hide;
     const size_t total = segs.back().mp3_off + segs.back().mp3_len;
     void *d_redo = c->grab(kPoolRedo, (size_t)units * 24);
     if (!d_redo || !b->big[0].reserve(L.mp3_bytes)) return fail(MP3S_E_NOMEM, "memory for resolving %d units", units);
@@ -279,89 +269,25 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     mp3s_gr_out *const gr = b->gr_out = (mp3s_gr_out *)b->big[1].data();
     if (!have_gr) rc = mp3s_dev_download(c, gr, d_out, (size_t)units * sizeof(mp3s_gr_out));
     b->scfsi.assign((size_t)n * 8, 0);
-    std::vector<int32_t> &cursor = c->h_cursor, &state = c->h_state;
-    cursor.assign((const int32_t *)(in + L.o_cur), (const int32_t *)(in + L.o_cur) + units);
+    ChainResolver &R = *c->chain;
+    R.begin(L, segs, in);
     // (the selection on the device has written the cursors of the units it replaced, and the chain check's re-runs those
     // of the units they ran again -- also in a batch without a plan)
-    if (!rc && (L.n_entries > 0 || (L.redo && c->opt[MP3S_OPT_REDO]))) rc = mp3s_dev_download(c, cursor.data(), d_in + L.o_cur, (size_t)units * 4);
-    state.assign((size_t)units * 4, 0);
+    if (!rc && (L.n_entries > 0 || (L.redo && c->opt[MP3S_OPT_REDO]))) rc = mp3s_dev_download(c, R.cursor.data(), dev.cursor, (size_t)units * 4);
     int passes = 1;
-    // ---- resolve the serial chains, stream by stream: hide cursor (MP3_Encoder.py:808-809) and the per-(gr,ch) inherited
-    //      address1/2/3 + quantizerStepSize (E7).  walk() lists the units whose assumed inputs were wrong and, per stream,
-    //      where the cursor first went wrong.
-    std::vector<int32_t> list, redo_in;
-    std::vector<mp3s_gr_out> tmp;
-    struct Pending { int unit; int64_t cur; };   // first unit of a stream that ran on a wrong cursor, the right cursor there
-    std::vector<Pending> pend(segs.size());
-    // cursor / state: what each unit's current result was computed with; want / state_want: what the walk says it should be
-    std::vector<int32_t> &want = c->h_want, &state_want = c->h_state_want;
-    want.assign(units, 0); state_want.assign((size_t)units * 4, 0);
-    auto walk = [&]() {
-        list.clear();
-        for (size_t si = 0; si < segs.size(); si++) {
-            EncSeg &s = segs[si];
-            pend[si] = {-1, 0};
-            int64_t cur = s.hide_base + cursor0(s);
-            const int64_t end = (int64_t)s.hide_base + s.n_hide;
-            int32_t chain[4][4] = {};   // [(ch*2+gr)][a1,a2,a3,step]
-            if (s.carry_in) std::memcpy(chain, s.carry_in->chain, sizeof chain);
-            bool own[4] = {false, false, false, false};   // the block has set chain[k] itself
-            s.carry_used = cur < end;                     // the message is still being hidden when the block starts
-            for (int u = s.first * 4; u < (s.first + s.n_frames) * 4; u++) {
-                const int k = u & 3;
-                mp3s_gr_out &g = gr[u];
-                bool redo = false;
-                const bool active = g.flags & MP3S_RF_ACTIVE;
-                if (!own[k] && (!active || (g.flags & MP3S_RF_USED_ADDR_IN))) s.carry_used = true;
-                if (active) own[k] = true;
-                if (s.n_hide > 0 && active) {
-                    const int64_t used = cursor[u];
-                    if (used != cur && std::min<int64_t>(used, cur) < end) {
-                        redo = true;
-                        if (pend[si].unit < 0) pend[si] = {u, cur};
-                    }
-                }
-                if ((g.flags & MP3S_RF_USED_ADDR_IN) &&
-                    (state[(size_t)u * 4] != chain[k][0] || state[(size_t)u * 4 + 1] != chain[k][1] ||
-                     state[(size_t)u * 4 + 2] != chain[k][2]))
-                    redo = true;
-                if (redo) list.push_back(u);
-                want[u] = (int32_t)std::min<int64_t>(cur, kNoCursor);
-                for (int j = 0; j < 4; j++) state_want[(size_t)u * 4 + j] = chain[k][j];
-                if (active) {
-                    cur += g.n_tables;
-                    chain[k][0] = g.address[0]; chain[k][1] = g.address[1]; chain[k][2] = g.address[2];
-                    chain[k][3] = g.quantizer_step;
-                } else {   // silent unit: everything is inherited (quantizerStepSize and addresses pass through)
-                    g.address[0] = chain[k][0]; g.address[1] = chain[k][1]; g.address[2] = chain[k][2];
-                    g.quantizer_step = chain[k][3];
-                }
-                if (g.flags & MP3S_RF_STEP_RANGE) return fail(MP3S_E_STEP_RANGE, "quantizer step left the table in unit %d", u);
-            }
-            s.hide_offset = cur - s.hide_base;
-            s.carry_out.cursor = s.hide_offset;
-            std::memcpy(s.carry_out.chain, chain, sizeof chain);
-        }
-        return (int)MP3S_OK;
-    };
-    // one launch over a list of (unit, cursor, inherited state) entries: 24 bytes per entry up -- [units | cursors | states]
-    // -- and the entries' GrInfo down (into tmp); compact = 1: ix / energies in place, 2: by entry into d_ixv / d_env, and only
+    // one launch over a list of (unit, cursor, inherited state) entries: 24 bytes per entry up (ChainResolver::stage_entries)
+    // and the entries' GrInfo down (into tmp); compact = 1: ix / energies in place, 2: by entry into d_ixv / d_env, and only
     // the table count of every entry comes down (one byte each, into tables_of, through d_tables)
+    std::vector<mp3s_gr_out> tmp;
     std::vector<uint8_t> tables_of;
     auto run_entries = [&](const std::vector<int32_t> &units_of, const std::vector<int32_t> &cursor_of, void *d_entries, int compact,
                            int16_t *ix_to, mp3s_gr_out *out_to, int32_t *en_to, uint8_t *d_tables) {
         const size_t nl = units_of.size();
-        redo_in.resize(nl * 6);
-        for (size_t i = 0; i < nl; i++) {
-            const int u = units_of[i];
-            redo_in[i] = u;
-            redo_in[nl + i] = cursor_of[i];
-            for (int j = 0; j < 4; j++) redo_in[2 * nl + 4 * i + j] = state_want[(size_t)u * 4 + j];
-        }
-        int r = mp3s_dev_upload(c, d_entries, redo_in.data(), nl * 24);
+        R.stage_entries(units_of, cursor_of);
+        int r = mp3s_dev_upload(c, d_entries, R.redo_in.data(), nl * 24);
         if (!r) {
             const int32_t *dr = (const int32_t *)d_entries;
-            const int e = launch_rate(c->stream, d_mdct, d_rf, n, d_hide, n_hide, dr + nl, dr + 2 * nl, dr, (int)nl, ix_to, out_to, en_to,
+            const int e = launch_rate(c->stream, d_mdct, dev.rf, n, dev.hide, n_hide, dr + nl, dr + 2 * nl, dr, (int)nl, ix_to, out_to, en_to,
                                       &c->prof, 0, compact);
             if (e) r = fail(MP3S_E_HIP, "rate launch: %s", hipGetErrorString((hipError_t)e));
         }
@@ -377,67 +303,28 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
         return r;
     };
     mark("GrInfo down");
-    if (!rc) rc = walk();
+    if (!rc) rc = R.walk(gr, segs);
     mark("walk");
-    if (!rc && list.size() > kFewUnits) {
+    if (!rc && R.list.size() > kFewUnits) {
         // ---- message variants
-        struct Span { size_t seg; int unit, count; int64_t cur; size_t entry; };
-        std::vector<Span> spans;
-        std::vector<int32_t> ent_unit, ent_cursor, pairs;
         void *d_ent = nullptr, *d_ixv = nullptr, *d_outv = nullptr, *d_env = nullptr, *d_pairs = nullptr;
         for (bool more = true; more && !rc;) {
-            spans.clear(); ent_unit.clear(); ent_cursor.clear(); pairs.clear();
-            for (size_t si = 0; si < segs.size(); si++) {
-                if (pend[si].unit < 0) continue;
-                const EncSeg &s = segs[si];
-                const int64_t end = (int64_t)s.hide_base + s.n_hide;
-                if (pend[si].cur + 3 > end) { pend[si].unit = -1; continue; }   // only the message's last unit is left
-                // as many units as the rest of the message can reach at 2.8 tables per unit (measured on music: 2.96; a stream
-                // that takes fewer -- silent units take none -- simply comes round again), as many as still fit into this launch
-                const int room = (kVariantEntries - (int)ent_unit.size()) / 8;
-                const int count = (int)std::min<int64_t>({(int64_t)(s.first + s.n_frames) * 4 - pend[si].unit, (end - pend[si].cur) * 5 / 14 + 32, (int64_t)room});
-                if (count <= 0) continue;                                       // next launch
-                spans.push_back({si, pend[si].unit, count, pend[si].cur, ent_unit.size()});
-                for (int v = 0; v < 8; v++)
-                    for (int j = 0; j < count; j++) { ent_unit.push_back(pend[si].unit + j); ent_cursor.push_back(4 * v); }
-            }
-            if (spans.empty()) break;
-            const size_t ne = ent_unit.size();
+            if (!R.plan_variants(segs, kVariantEntries)) break;
+            const size_t ne = R.ent_unit.size();
             if (!(d_ent = c->grab(kPoolVarEntries, ne * 24)) || !(d_ixv = c->grab(kPoolVarIx, ne * 1152)) || !(d_outv = c->grab(kPoolVarOut, ne * sizeof(mp3s_gr_out))) ||
                 !(d_env = c->grab(kPoolVarEnergy, ne * 88)) || !(d_pairs = c->grab(kPoolVarPairs, ne)))   // at most one pair per unit = ne / 8 pairs of 8 bytes
                 rc = fail(MP3S_E_NOMEM, "hipMalloc failed for the message variants");
             mark("variant entries listed");
             // (d_pairs holds the table counts first, the chosen pairs afterwards: ne bytes either way)
-            if (!rc) rc = run_entries(ent_unit, ent_cursor, d_ent, 2, (int16_t *)d_ixv, (mp3s_gr_out *)d_outv, (int32_t *)d_env, (uint8_t *)d_pairs);
+            if (!rc) rc = run_entries(R.ent_unit, R.ent_cursor, d_ent, 2, (int16_t *)d_ixv, (mp3s_gr_out *)d_outv, (int32_t *)d_env, (uint8_t *)d_pairs);
             mark("variants: up, launch, down");
-            more = false;
-            for (const Span &sp : spans) {
-                if (rc) break;
-                const EncSeg &s = segs[sp.seg];
-                const int64_t end = (int64_t)s.hide_base + s.n_hide;
-                int64_t cur = sp.cur;
-                int j = 0;
-                for (; j < sp.count && cur + 3 <= end; j++) {     // all three bits the unit can ask for exist
-                    const int u = sp.unit + j;
-                    const int v = (hide_all[cur] & 1) * 4 + (hide_all[cur + 1] & 1) * 2 + (hide_all[cur + 2] & 1);
-                    const size_t e = sp.entry + (size_t)v * sp.count + j;
-                    cursor[u] = (int32_t)cur;
-                    for (int q = 0; q < 4; q++) state[(size_t)u * 4 + q] = state_want[(size_t)u * 4 + q];
-                    pairs.push_back((int32_t)e); pairs.push_back(u);
-                    cur += tables_of[e];                           // (the entry's GrInfo goes to the unit's place on the device)
-                }
-                // span used up with message left: the stream goes on in the next launch; otherwise the message's last unit
-                // (fewer than three bits left) and whatever lies behind it are the exact re-run's
-                if (j == sp.count && cur < end && sp.unit + sp.count < (s.first + s.n_frames) * 4) { pend[sp.seg] = {sp.unit + sp.count, cur}; more = true; }
-                else pend[sp.seg].unit = -1;
-            }
-            for (size_t si = 0; si < segs.size(); si++) more |= pend[si].unit >= 0;
+            if (!rc) more = R.choose_variants(segs, host.hide, tables_of.data());
             mark("variants: select");
-            if (!rc && !pairs.empty()) {
-                rc = mp3s_dev_upload(c, d_pairs, pairs.data(), pairs.size() * 4);
+            if (!rc && !R.pairs.empty()) {
+                rc = mp3s_dev_upload(c, d_pairs, R.pairs.data(), R.pairs.size() * 4);
                 mark("variants: pairs up");
                 if (!rc) {
-                    const int e = launch_scatter(c->stream, (const int32_t *)d_pairs, (int)(pairs.size() / 2), (const int16_t *)d_ixv,
+                    const int e = launch_scatter(c->stream, (const int32_t *)d_pairs, (int)(R.pairs.size() / 2), (const int16_t *)d_ixv,
                                                  (const int32_t *)d_env, (const mp3s_gr_out *)d_outv, (int16_t *)d_ix, (int32_t *)d_en, d_out);
                     if (e) rc = fail(MP3S_E_HIP, "scatter: %s", hipGetErrorString((hipError_t)e));
                 }
@@ -448,31 +335,25 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
         // the GrInfo with the chosen entries in place
         if (!rc) rc = mp3s_dev_download(c, gr, d_out, (size_t)units * sizeof(mp3s_gr_out));
         mark("GrInfo down");
-        if (!rc) rc = walk();
+        if (!rc) rc = R.walk(gr, segs);
         mark("walk");
     }
     // ---- exact re-runs of what is left, until nothing changes
     std::vector<int32_t> cur_of;
-    while (!rc && !list.empty()) {
+    while (!rc && !R.list.empty()) {
         if (passes > units + 16) { rc = fail(MP3S_E_HIP, "rate-loop chain did not converge"); break; }
-        cur_of.resize(list.size());
-        for (size_t i = 0; i < list.size(); i++) cur_of[i] = want[list[i]];
-        const std::vector<int32_t> units_of = list;
+        cur_of.resize(R.list.size());
+        for (size_t i = 0; i < R.list.size(); i++) cur_of[i] = R.want[R.list[i]];
+        const std::vector<int32_t> units_of = R.list;
         rc = run_entries(units_of, cur_of, d_redo, 1, (int16_t *)d_ix, (mp3s_gr_out *)d_out, (int32_t *)d_en, nullptr);
-        if (!rc)
-            for (size_t i = 0; i < units_of.size(); i++) {
-                const int u = units_of[i];
-                gr[u] = tmp[i];
-                cursor[u] = cur_of[i];
-                for (int q = 0; q < 4; q++) state[(size_t)u * 4 + q] = state_want[(size_t)u * 4 + q];
-            }
-        if (!rc) rc = walk();
+        if (!rc) R.accept_reruns(units_of, cur_of, tmp, gr);
+        if (!rc) rc = R.walk(gr, segs);
     }
     mark("exact re-runs");
     if (!rc) {
         // ---- bit packing again, on the final GrInfo
         rc = mp3s_dev_upload(c, d_out, gr, (size_t)units * sizeof(mp3s_gr_out));
-        if (!rc) rc = pack_step(c, c->stream, d_ix, d_out, d_en, n, L.sri, L.bri, L.whole, (const uint32_t *)(d_in + L.o_off), d_in + L.o_pad, d_mp3, d_sc, d_pack_status);
+        if (!rc) rc = pack_step(c, c->stream, d_ix, d_out, d_en, n, L.sri, L.bri, L.whole, dev.off, dev.pad, d_mp3, d_sc, d_pack_status);
         int32_t st = 0;
         if (!rc) rc = mp3s_dev_download(c, &st, d_pack_status, sizeof st);
         if (!rc && st) rc = fail(MP3S_E_HIP, "bit packer reported status %d", st);
@@ -484,6 +365,29 @@ int enc_resolve(mp3s_ctx *c, const EncLayout &L, std::vector<EncSeg> &segs, cons
     return rc;
 }
 
+// The front of encode_batch and capacity_batch: the streams laid out (L), the context's device made current, the input block written
+// into the context's h_in.
+static int enc_begin(mp3s_ctx *c, std::vector<EncSeg> &segs, int samplerate, int bitrate_kbps, EncLayout &L)
+{
+    const int rc = enc_layout(segs, samplerate, bitrate_kbps, L, c->opt[MP3S_OPT_SELECT] != 0);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    c->h_in.resize(L.bytes);
+    return enc_fill(segs, L, c->h_in.data());
+}
+
+// ... and what follows their buffers, nothing waited for: the PCM up (pcm != nullptr: it comes from the host), the block up, the variant
+// buffers (behind the uploads: enc_pool_buffers), the job issued
+static int enc_upload_issue(mp3s_ctx *c, const EncLayout &L, EncDev &dev, const int16_t *pcm)
+{
+    int rc = MP3S_OK;
+    if (pcm && hipMemcpyAsync(const_cast<int16_t *>(dev.d_pcm), pcm, (size_t)L.n_all * 2304 * 2, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "PCM upload failed");
+    if (!rc && hipMemcpyAsync(const_cast<uint8_t *>(dev.d_in), c->h_in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
+    if (!rc && !enc_variant_buffers(c, L, dev)) rc = fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
+    if (!rc) rc = enc_issue(c, L, dev);
+    return rc;
+}
+
 // Encode the streams of `segs` (stereo, one sampling rate and bitrate) as ONE batch: transforms, rate loop, bit packing.
 // pcm_dev != nullptr: the int16 PCM is already in HBM (re-encode after a device decode) and pcm is ignored.
 // Results: b->mp3 = the streams' MP3 bytes (segs[i].mp3_off / mp3_len); with want_gr also b->gr_out and b->scfsi in
@@ -492,14 +396,9 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
                  mp3s_buf *b, int *passes_out, bool want_gr)
 {
     EncLayout L;
-    int rc = enc_layout(segs, samplerate, bitrate_kbps, L, c->opt[MP3S_OPT_SELECT] != 0);
+    int rc = enc_begin(c, segs, samplerate, bitrate_kbps, L);
     if (rc) return rc;
-    const int n = L.n, units = L.units, n_all = L.n_all;
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<uint8_t> &in = c->h_in;
-    in.resize(L.bytes);
-    rc = enc_fill(segs, L, in.data());
-    if (rc) return rc;
+    const int n = L.n, units = L.units;
     auto cleanup = [&]() { hipStreamSynchronize(c->stream); };   // the buffers stay in the context's pool
     EncDev dev;
     if (!enc_pool_buffers(c, L, !pcm_dev, true, small_bytes(L.n_segs), dev)) {
@@ -518,10 +417,7 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     if (want_gr) b->scfsi.assign((size_t)n * 8, 0);
     // ---- one pass, nothing waited for in between: inputs up, transforms, rate loop on the guessed cursors, the chain
     //      check on the device, bit packing, results down.  The verdict says whether the guesses held.
-    if (!pcm_dev && hipMemcpyAsync(const_cast<int16_t *>(dev.d_pcm), pcm, (size_t)n_all * 2304 * 2, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "PCM upload failed");
-    if (!rc && hipMemcpyAsync(const_cast<uint8_t *>(dev.d_in), in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
-    if (!rc && !enc_variant_buffers(c, L, dev)) rc = fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
-    if (!rc) rc = enc_issue(c, L, dev);
+    rc = enc_upload_issue(c, L, dev, pcm_dev ? nullptr : pcm);
     auto down = [&](void *dst, const void *src, size_t bytes) {
         if (!rc && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
     };
@@ -546,7 +442,7 @@ int encode_batch(mp3s_ctx *c, const int16_t *pcm, const int16_t *pcm_dev, std::v
     }
     // ---- the guesses did not hold: resolve the chains on the host, as round 1 did
     if (trace_on()) fprintf(stderr, "mp3s: encode of %d frames: %d units still to redo behind the device's re-runs (step range %d), %d variant entries, redo launches %d -> the host resolves\n", n, head.redo_units, head.step_range, L.n_entries, (int)L.redo);
-    rc = enc_resolve(c, L, segs, in.data(), dev, b, want_gr, passes_out);
+    rc = enc_resolve(c, L, segs, c->h_in.data(), dev, b, want_gr, passes_out);
     cleanup();
     return rc;
 }
@@ -558,14 +454,9 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
 {
     *out = CapacityBatch();
     EncLayout L;
-    int rc = enc_layout(segs, samplerate, bitrate_kbps, L, c->opt[MP3S_OPT_SELECT] != 0);
+    int rc = enc_begin(c, segs, samplerate, bitrate_kbps, L);
     if (rc) return rc;
     const int n = L.n;
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<uint8_t> &in = c->h_in;
-    in.resize(L.bytes);
-    rc = enc_fill(segs, L, in.data());
-    if (rc) return rc;
     const size_t o_cap = up16(small_bytes(L.n_segs)), o_prof = o_cap + (size_t)L.n_segs * sizeof(mp3s_capacity_seg),
                  down_bytes = o_prof + (want_profile ? (size_t)n * 4 : 0);
     auto cleanup = [&]() { hipStreamSynchronize(c->stream); };   // the buffers stay in the context's pool
@@ -580,12 +471,10 @@ int capacity_batch(mp3s_ctx *c, const int16_t *pcm_dev, std::vector<EncSeg> &seg
     }
     uint8_t *const small8 = b->big[2].data();
     const SmallView small{small8};
-    if (hipMemcpyAsync(const_cast<uint8_t *>(dev.d_in), in.data(), L.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "input upload failed");
     dev.d_pcm = pcm_dev;
     dev.d_cap = (mp3s_capacity_seg *)((uint8_t *)dev.d_small + o_cap);
     dev.d_profile = want_profile ? (uint32_t *)((uint8_t *)dev.d_small + o_prof) : nullptr;
-    if (!rc && !enc_variant_buffers(c, L, dev)) rc = fail(MP3S_E_NOMEM, "hipMalloc failed for %d variant entries", L.n_entries);
-    if (!rc) rc = enc_issue(c, L, dev);
+    rc = enc_upload_issue(c, L, dev, nullptr);
     if (!rc && hipMemcpyAsync(small8, dev.d_small, down_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "download failed");
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(MP3S_E_HIP, "sync failed");
     if (rc) { cleanup(); return rc; }

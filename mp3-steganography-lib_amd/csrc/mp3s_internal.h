@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mp3s.h"
@@ -72,6 +73,7 @@ enum PoolSlot : int {
 constexpr PoolSlot kPoolIs[2] = {kPoolIs0, kPoolIs1}, kPoolSi[2] = {kPoolSi0, kPoolSi1}, kPoolPcm[2] = {kPoolPcm0, kPoolPcm1};   // by Job::set
 
 struct mp3s_pipe;
+struct ChainResolver;
 struct mp3s_ctx {
     int device = 0;
     int64_t opt[MP3S_OPT_COUNT] = {0};   // MP3S_OPT_*: defaults from the environment at creation, then mp3s_ctx_set_option
@@ -108,8 +110,9 @@ struct mp3s_ctx {
         return pool[slot];
     }
     // host-side work arrays of the encoder, kept between calls: beyond a few MB a fresh vector means fresh pages from
-    // the kernel on every call (page faults cost more than the work done in them)
-    std::vector<int32_t> h_cursor, h_state, h_want, h_state_want;
+    // the kernel on every call (page faults cost more than the work done in them).  Those of the host's chain resolver are its own
+    // (chain_resolve.h, which needs the encoder's types below: made and freed with the context, mp3s_api.cpp)
+    ChainResolver *chain = nullptr;
     std::vector<uint8_t> h_in;
     // ... and of the decoder: the concatenated batch
     std::vector<mp3s_frame_hdr> h_hdr;
@@ -487,6 +490,11 @@ struct EncSeg {             // one stream of an encode batch: frames back to bac
     mp3s_carry carry_out = {};
     bool carry_used = false;         // the block's bytes depend on carry_in
 };
+// message bits the frames in front of a block have taken
+inline int64_t cursor0(const EncSeg &s)
+{
+    return s.carry_in ? std::min<int64_t>(std::max<int64_t>(s.carry_in->cursor, 0), kNoCursor) : 0;
+}
 // The host-made inputs of an encode batch travel as ONE block (one copy):
 //   [frame headers (n_all) | rate frames (n) | assumed cursors (units) | message bits | chain segments | frame offsets (n+1) | padding (n)
 //    | selection spans (n_segs) | variant entries: units (n_entries), cursors (n_entries)]
@@ -499,6 +507,22 @@ struct EncLayout {
     size_t mp3_bytes = 0;          // all frames of the batch
     int64_t bytes_before = 0;      // size of the frames in front of a block (E14: the tail cut depends on it)
 };
+// The parts of such a block at `base`, typed: B = uint8_t for enc_fill, which writes them, const uint8_t for everybody who reads them -- on the
+// host (the copy enc_fill wrote) or as device addresses (EncDev::d_in).  hide = [patterns | message of stream 0 | message of stream 1 ...]
+template <class B, class T> using BlockPart = typename std::conditional<std::is_const<B>::value, const T, T>::type;
+template <class B>
+struct EncBlock {
+    BlockPart<B, mp3s_frame_hdr> *hdr; BlockPart<B, mp3s_rate_frame> *rf; BlockPart<B, int32_t> *cursor; B *hide; BlockPart<B, mp3s_chain_seg> *segs;
+    BlockPart<B, uint32_t> *off; B *pad; BlockPart<B, mp3s_select_span> *spans; BlockPart<B, int32_t> *ent_unit, *ent_cursor;
+};
+template <class B>
+inline EncBlock<B> enc_block(const EncLayout &L, B *base)
+{
+    BlockPart<B, int32_t> *const ent = (BlockPart<B, int32_t> *)(base + L.o_ent);
+    return {(BlockPart<B, mp3s_frame_hdr> *)base, (BlockPart<B, mp3s_rate_frame> *)(base + L.o_rf), (BlockPart<B, int32_t> *)(base + L.o_cur), base + L.o_hide,
+            (BlockPart<B, mp3s_chain_seg> *)(base + L.o_segs), (BlockPart<B, uint32_t> *)(base + L.o_off), base + L.o_pad, (BlockPart<B, mp3s_select_span> *)(base + L.o_spans),
+            ent, ent + L.n_entries};
+}
 // small results of a batch, in one block: this head, then mp3s_chain_seg_out[n_segs].  Every word is zero when all went well; the kernels
 // that own a word write or OR into it, the host only reads.
 struct SmallHead {

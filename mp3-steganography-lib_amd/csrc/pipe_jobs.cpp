@@ -526,7 +526,7 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
     j.down_split = 0;
     if (ck.on && ck.last && j.walked && L.n >= 1024 && s.e_half && P->internal) {
         dev.pack_split = L.n / 2; dev.pack_half = s.e_half;
-        j.down_split = reinterpret_cast<const uint32_t *>(s.h_stage + j.o_encblk + L.o_off)[dev.pack_split];
+        j.down_split = enc_block<const uint8_t>(L, s.h_stage + j.o_encblk).off[dev.pack_split];
     }
     const int rc = enc_issue(c, L, dev, P->s_tail, s.e_rate, P->s_dec ? P->e_enc[set] : nullptr);
     if (rc) return rc;

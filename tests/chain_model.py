@@ -1,8 +1,9 @@
 """The serial chains of the rate loop, restated on the host for the tests of the device's chain check and re-runs (csrc/k_chain.hpp,
 k_rate_redo of csrc/k_rate.hpp).  Two things, kept apart:
 
-  walk()          what the CHECK does with records somebody else computed: csrc/mp3s_encode_pipeline.cpp's walk(), which k_chain_sum /
-                  k_chain_apply do as a scan.  It judges records, it computes none.
+  walk()          what the CHECK does with records somebody else computed: ChainResolver::walk of csrc/chain_resolve.h (the host's, compared
+                  with this one in tests/test_chain_resolve.py), which k_chain_sum / k_chain_apply do as a scan.  It judges records, it
+                  computes none.
   serial_truth()  what the records SHOULD be: the reference's order (ch outer, gr inner, frame by frame) with the oracle hook
                   oracle_lib.rate_units_from, one call per unit, the state of the unit's chain and the running cursor handed on.
   first_pass()    the same hook on what mp3s_rate_loop_dev is given without d_state_in: zero state, the caller's cursor guesses.

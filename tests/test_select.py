@@ -166,6 +166,66 @@ def test_silence_inside_the_reach_and_uncovered_start(ctx, mlib, orc):
     assert r["mp3"] == o["mp3"] and r["too_long"] and bool(o["too_long"]) and r["hide_offset"] == o["hide_offset"]
 
 
+# ------------------------------------------------------------------------------------------------ the host's resolver on short inputs
+def host_path_cases():
+    """60 frames at 44.1 kHz / 128 kbit/s for a context with `select` and `redo` off, so that every failed guess is the host's
+    (enc_resolve with csrc/chain_resolve.h).  The synthetic signal takes three tables in every unit, which is the first pass's guess:
+    what makes the guess fail is silence, whose units take none.  -> [(name, pcm, message bits)]"""
+    from synth_pcm import synth_pcm
+    pcm = synth_pcm(60, seed=38)
+    bits = np.random.default_rng(15).integers(0, 2, size=500).astype(np.uint8)
+    quiet_first, quiet_20 = pcm.copy(), pcm.copy()
+    quiet_first[:1152] = 0                                            # every cursor behind the first frame is guessed 12 bits too far
+    quiet_20[:20 * 1152] = 0
+    return [("a few bits behind a silent frame", quiet_first, bits[:10]),
+            ("a few hundred bits", pcm, bits[:300]),
+            ("a few hundred bits behind a silent frame", quiet_first, bits[:300]),
+            ("a few hundred bits behind 20 silent frames", quiet_20, bits[:300])]
+
+
+def host_path_blocks():
+    """the 60 frames as two blocks of 30, each beginning in silence (frame 0; frames 30 to 32, of which the first still carries the tail of
+    the filters and the overlap of the frame in front of it); the message runs into the second -> (pcm, message bits)"""
+    pcm, msg = host_path_cases()[2][1].copy(), np.random.default_rng(15).integers(0, 2, size=500).astype(np.uint8)
+    pcm[30 * 1152:33 * 1152] = 0
+    return pcm, msg
+
+
+# rate_passes of the parent commit's library (enc_resolve before ChainResolver) for the cases above, taken on the MI355X with the trace on:
+# 4 wrong cursors -> the direct re-runs (one launch); the guess holds; 100 wrong cursors -> one variant launch, nothing left to re-run (x 2).
+# The blocks: 116 wrong cursors -> one variant launch; 47 -> one variant launch and one exact re-run (the message's end is the re-runs')
+HOST_PATH_PASSES = {"a few bits behind a silent frame": 2, "a few hundred bits": 1, "a few hundred bits behind a silent frame": 2,
+                    "a few hundred bits behind 20 silent frames": 2}
+HOST_PATH_BLOCK_PASSES = [2, 3]
+
+
+@pytest.mark.gpu
+def test_host_resolver_on_short_inputs(ctx, mlib, orc):
+    """both branches of enc_resolve -- at most kFewUnits wrong cursors: exact re-runs at once; more: message variants first -- and a block
+    that continues a message, on 60 frames: the oracle's bytes, and as many rate-loop launches as before the resolver moved"""
+    keep = ctx.set_option("select", 0), ctx.set_option("redo", 0)
+    try:
+        for name, pcm, msg in host_path_cases():
+            r, o = ctx.encode_pcm(pcm, 44100, 128, msg), orc.encode(pcm, 44100, 128, msg)
+            assert o["rc"] == 0 and r["mp3"] == o["mp3"], name
+            assert r["hide_offset"] == o["hide_offset"] and r["too_long"] == bool(o["too_long"]), name
+            assert r["rate_passes"] == HOST_PATH_PASSES[name], name
+        pcm, msg = host_path_blocks()
+        o = orc.encode(pcm, 44100, 128, msg)
+        out, carry, passes = b"", None, []
+        for b in range(2):
+            lead = 0 if b == 0 else 2
+            blk = ctx.encode_block(pcm[(b * 30 - lead) * 1152:(b + 1) * 30 * 1152], lead, b * 30, b == 1, 44100, 128, msg, carry)
+            out, carry = out + bytes(blk["mp3"]), blk["carry_out"]
+            passes.append(blk["rate_passes"])
+        assert o["rc"] == 0 and out == o["mp3"] == ctx.encode_pcm(pcm, 44100, 128, msg)["mp3"]
+        assert blk["hide_offset"] == o["hide_offset"] and blk["too_long"] == bool(o["too_long"])
+        assert passes == HOST_PATH_BLOCK_PASSES
+    finally:
+        ctx.set_option("select", keep[0])
+        ctx.set_option("redo", keep[1])
+
+
 @pytest.mark.gpu
 def test_batch_of_streams_and_blocks(ctx, mlib, orc):
     """several streams with their own plans in one batch (one workgroup per stream), and a message carried across blocks
