@@ -6,6 +6,12 @@
 //                slack becomes stuffing, E6), a granule*channel starts after the part2_3_lengths before it, and inside
 //                it the offset of a pair is the prefix sum of the code lengths.  One workgroup per frame, one
 //                wavefront per granule*channel, lane = 5 consecutive pairs, bits OR-ed into an LDS image of the frame.
+//                A pair stays the dword x | y << 16 it is loaded as: |x|, |y|, the clamp to 15, the escape and sign fields and
+//                their widths are packed 16-bit instructions on both halves at once.  What a pair is compared with (the region
+//                starts, big_values, the end of count1) is wave-uniform, so a lane takes its distance to each bound once, as a
+//                mask of six bits per pair below it, and picks the regions' words for its five pairs with two v_bfi; a pair that
+//                emits nothing is cleared as a dword and needs no further case.  A lane's words are pushed into a 64-bit register
+//                from below, one shift each, and leave as whole dwords of the image.
 #pragma once
 
 namespace mp3s {
@@ -23,6 +29,19 @@ __device__ __forceinline__ void lds_put(uint32_t *fb, uint32_t pos, uint32_t val
     const uint64_t w = (uint64_t)val << (64 - o - n);
     atomicOr(&fb[d], (uint32_t)(w >> 32));
     if ((uint32_t)w) atomicOr(&fb[d + 1], (uint32_t)w);
+}
+
+// (mask & a) | (~mask & b): v_bfi_b32
+__device__ __forceinline__ uint32_t pack_bfi(uint32_t mask, uint32_t a, uint32_t b) { return (mask & a) | (~mask & b); }
+
+typedef uint16_t pk_u16 __attribute__((ext_vector_type(2)));
+typedef int16_t pk_i16 __attribute__((ext_vector_type(2)));
+// min(x, 1), min(y, 1) of a packed pair (written as a minimum the compiler turns it into two compares, two selects and a permute)
+__device__ __forceinline__ pk_u16 pack_pk_min1(pk_u16 a)
+{
+    pk_u16 r;
+    asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(r) : "v"(a));
+    return r;
 }
 
 // wave sum of a small non-negative value over the lanes selected by `on`
@@ -102,6 +121,7 @@ __global__ __launch_bounds__(256) void k_enc_pack(
     const int e = wave, grn = e >> 1, ch = e & 1;
     const long u = ((long)f * 2 + ch) * 2 + grn;
     const mp3s_gr_out &g = gr[u];
+    const int p23 = __builtin_amdgcn_readfirstlane(e == 0 ? p23v[0] : (e == 1 ? p23v[1] : (e == 2 ? p23v[2] : p23v[3])));   // this unit's, stuffing included
     if (wave < 2) {
         // ---- scfsi of channel `wave` (:861-892) from the band energies of its two granules: lane s holds band s
         const long u0 = ((long)f * 2 + wave) * 2, u1 = u0 + 1;
@@ -144,17 +164,20 @@ __global__ __launch_bounds__(256) void k_enc_pack(
             }
         }
     }
-    if (lane_p < 4) {
-        // ---- side info of this wave's granule*channel (:1305-1337), 59 bits at 52 + 59 e: its four fields by four lanes, one put each
-        //      (one lane putting them one after the other had the whole wave step through four times the instructions)
-        const uint32_t f0 = ((uint32_t)p23v[e] << 9) | (uint32_t)g.big_values;                                            // 21 bits
+    {
+        // ---- side info of this wave's granule*channel (:1305-1337), 59 bits at 52 + 59 e.  Its four fields are wave-uniform: the wave joins
+        //      them to one string in scalar registers and cuts it into the three image dwords it can touch; lanes 0 .. 2 OR one each (four lanes
+        //      used to pick a field, a width and a place by selects and put it with a 64-bit shift and two ORs)
+        const uint32_t f0 = ((uint32_t)p23 << 9) | (uint32_t)g.big_values;                                            // 21 bits
         const uint32_t f1 = (((uint32_t)(g.quantizer_step + 210) & 0xff) << 5);                                           // 13: global_gain 8, scalefac_compress 4, window_switching 1
         const uint32_t f2 = ((uint32_t)g.table_select[0] << 10) | ((uint32_t)g.table_select[1] << 5) | (uint32_t)g.table_select[2];   // 15
         const uint32_t f3 = ((uint32_t)g.region0_count << 6) | ((uint32_t)g.region1_count << 3) | (uint32_t)g.count1table_select;     // 10: + preflag, scalefac_scale = 0
-        const uint32_t v = lane_p == 0 ? f0 : (lane_p == 1 ? f1 : (lane_p == 2 ? f2 : f3));
-        const int n = lane_p == 0 ? 21 : (lane_p == 1 ? 13 : (lane_p == 2 ? 15 : 10));
-        const uint32_t at = lane_p == 0 ? 0u : (lane_p == 1 ? 21u : (lane_p == 2 ? 34u : 49u));
-        lds_put(fb, 52 + 59 * (uint32_t)e + at, v, n);
+        const uint64_t top = ((((uint64_t)f0 << 38) | ((uint64_t)f1 << 25) | ((uint64_t)f2 << 10) | f3)) << 5;   // the string's first bit in bit 63
+        const uint32_t at = 52 + 59 * (uint32_t)e, o = at & 31u;
+        const uint64_t d01 = top >> o;
+        const uint32_t d2 = (uint32_t)(((uint64_t)(uint32_t)top << 32) >> o);
+        const uint32_t v = lane_p == 0 ? (uint32_t)(d01 >> 32) : (lane_p == 1 ? (uint32_t)d01 : d2);
+        if (lane_p < 3) atomicOr(&fb[(at >> 5) + (uint32_t)lane], v);
     }
 
     // ---- main data of this wave's granule*channel (:1394-1446)
@@ -162,112 +185,126 @@ __global__ __launch_bounds__(256) void k_enc_pack(
     uint32_t ustart = 288;
 #pragma unroll
     for (int k = 0; k < 3; k++) ustart += k < e ? (uint32_t)p23v[k] : 0u;
-    const int bv = g.big_values, c1 = g.count1;
+    const int bvr = g.big_values, bv = bvr < 288 ? bvr : 288, c1 = g.count1;
     const int32_t *sfb = c_tab.sfb_long[sri];
     const int r1s = sfb[g.region0_count + 1], r2s = sfb[g.region0_count + 1 + g.region1_count + 1];
-    int xv[10];
+    // The lane's five pairs, two dwords x | y << 16 at a time: the addresses of lanes 57 (its last two pairs) to 63 lie behind the unit and
+    // are pulled back into it; what such a lane reads there is no pair of its own and is cleared with the pairs behind count1 below.
+    uint32_t w[5];
     {
-        const uint32_t *xp = reinterpret_cast<const uint32_t *>(ix + u * 576 + lane * 10);
-#pragma unroll
-        for (int k = 0; k < 5; k++) {
-            const uint32_t w = (lane_p * 5 + k) < 288 ? xp[k] : 0u;
-            xv[2 * k] = (int)(int16_t)(w & 0xffff); xv[2 * k + 1] = (int)(int16_t)(w >> 16);
-        }
+        const char *xb0 = reinterpret_cast<const char *>(ix + u * 576);
+        const int oa = lane * 20 < 1140 ? lane * 20 : 1140, ob = lane * 20 + 12 < 1144 ? lane * 20 + 12 : 1144;
+        const uint32_t *xa = reinterpret_cast<const uint32_t *>(xb0 + oa), *xc = reinterpret_cast<const uint32_t *>(xb0 + ob);
+        w[0] = xa[0]; w[1] = xa[1]; w[2] = xa[2]; w[3] = xc[0]; w[4] = xc[1];
     }
-    // the low bits of the lane's pairs and of the pair behind them (the first pair of the lane above): a count1 quadruple
-    // is this pair + the next one
-    uint32_t c2[6];
-#pragma unroll
-    for (int k = 0; k < 5; k++) c2[k] = (uint32_t)((xv[2 * k] & 1) | ((xv[2 * k + 1] & 1) << 1));   // (two's complement: the low bit of |v| is the low bit of v)
-    c2[5] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c2[0], 0x130, 0xf, 0xf, false);              // wave_shl:1
-    uint32_t code0[5], code1[5]; int n0[5], n1[5];
-    int tot = 0;
-    // What differs between the regions is wave-uniform: one scalar word per region -- Huffman-length family (books 13, 15,
-    // 16.., 24..) | linbits << 2 | "book in use" << 6 -- picked per lane; everything else is the same arithmetic for every
-    // pair, without a branch and (round 4) nearly without selects: the escape and sign bits (MP3_Encoder.py:1452-1500;
-    // books 13 and 15 have no linbits, so their value 15 emits none) are field extractions of a width that is zero where
-    // nothing is emitted, and the pair's own code word -- its book's, or the quadruple's with the first pair of a quad (E13;
-    // :1502-1547), or none -- is one read of `pt`.
-    uint32_t Kr[3];
+    // What differs between the regions is wave-uniform: six bits per region -- Huffman-length family (books 13, 15, 16.., 24..) |
+    // linbits << 2 -- and "book in use".  Every bound a pair is compared with (region 1, region 2, big_values, the end of count1) is
+    // wave-uniform too and the lane's pairs are consecutive, so the lane takes its DISTANCE to each bound once, as a mask of six bits
+    // per pair below it (0 .. 5 pairs: a v_med3 and a shift), and picks the six bits of all five pairs with two v_bfi of the regions' words
+    // repeated five times; "in use" likewise.  Per pair that leaves field extractions at compile-time positions where there were a
+    // compare and a select per pair and bound.
     bool any_bad = false;
+    uint32_t Wr[3], Ur[3];
     {
         const int tsr[3] = {ts0, ts1, ts2};
 #pragma unroll
         for (int r = 0; r < 3; r++) {
             const int ti = tsr[r];
-            const int fam = ti == 13 ? 0 : (ti == 15 ? 1 : (ti < 24 ? 2 : 3));
-            Kr[r] = ti ? (uint32_t)fam | ((uint32_t)lin_bits_of(ti) << 2) | (1u << 6) : 0u;
+            // family 0 for book 13, 1 for 15, 2 for every other book below 24, 3 from 24 on: two bits per book, read from a constant
+            const uint32_t fam = (uint32_t)(0xffffaaaa62aaaaaaull >> (2 * (ti & 31))) & 3u;
+            Wr[r] = (fam | ((uint32_t)lin_bits_of(ti) << 2)) * 0x01041041u;
+            Ur[r] = ti ? 0x3fffffffu : 0u;
             // a book this encoder never selects, in a region that holds pairs
             const int lo = r == 0 ? 0 : (r == 1 ? r1s : r2s), hi = r == 0 ? r1s : (r == 1 ? r2s : 576);
-            any_bad |= ti != 0 && ti != 13 && ti != 15 && ti < 16 && lo < 2 * bv && lo < hi;
+            any_bad |= ti != 0 && ti != 13 && ti != 15 && ti < 16 && lo < 2 * bvr && lo < hi;
         }
     }
+    const int l30 = lane * 30;
+    auto below = [&](int bound) -> uint32_t {      // six bits for each of the lane's pairs in front of pair `bound`
+        const int s = min(max(6 * bound - l30, 0), 30);
+        return (1u << s) - 1u;
+    };
+    const int cend = bv + 2 * c1 < 288 ? bv + 2 * c1 : 288;
+    const uint32_t M1 = below((r1s + 1) >> 1), M2 = below((r2s + 1) >> 1), MB = below(bv), ME = below(cend);
+    const uint32_t P = pack_bfi(M1, Wr[0], pack_bfi(M2, Wr[1], Wr[2]));
+    const uint32_t MU = pack_bfi(M1, Ur[0], pack_bfi(M2, Ur[1], Ur[2]));
+    const uint32_t INS = pack_bfi(MB, MU, ME);      // pairs that emit anything: big values of a book in use, count1 pairs
+    // a count1 quadruple starts at every second pair from big_values on: the lane's even or its odd pairs
+    const uint32_t odd = 0u - (uint32_t)((lane ^ bv) & 1);
     const uint32_t quad_base = (uint32_t)(PACK_PT_QUAD + (c1sel ? 16 : 0));
+    const int nb5 = bv - lane * 5;                   // pairs of the lane that are big values (compared with 0 .. 4)
+#pragma unroll
+    for (int k = 0; k < 5; k++) w[k] &= (uint32_t)__builtin_amdgcn_sbfe((int)INS, 6 * k, 1);
+    // the low bits of the pairs' two values (two's complement: the low bit of |v| is the low bit of v), and of the pair behind the lane's
+    // (the first pair of the lane above): a count1 quadruple is this pair + the next one
+    uint32_t lowb[6];
+#pragma unroll
+    for (int k = 0; k < 5; k++) lowb[k] = w[k] & 0x00010001u;
+    lowb[5] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lowb[0], 0x130, 0xf, 0xf, false);           // wave_shl:1
+    uint32_t code0[5], code1[5]; int n0[5], n1[5];
+    int tot = 0;
+    // Both halves of a pair at once (packed 16-bit): |x|, |y| <= 8191 + 15.  The escape and sign bits (MP3_Encoder.py:1452-1500; books 13
+    // and 15 have no linbits, so their value 15 emits none) are [x - 15 in lb bits][sign of x][y - 15 in lb bits][sign of y]; a value of 0
+    // has no sign bit, one below 15 no escape bits: x - 15 saturates to 0, the width lb - 16 (15 - min(x, 15)) to 0.  The pair's own code
+    // word -- its book's, or the quadruple's with the first pair of a quad (E13; :1502-1547), or none -- is one read of `pt`.
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-        const int p = lane * 5 + k;
-        const int vx = xv[2 * k], vy = xv[2 * k + 1];
-        const uint32_t x = (uint32_t)(vx < 0 ? -vx : vx), y = (uint32_t)(vy < 0 ? -vy : vy);
-        const int i = 2 * p;
-        const uint32_t K = i >= r2s ? Kr[2] : (i >= r1s ? Kr[1] : Kr[0]);
-        const uint32_t Ke = p < bv ? K : 0u;                              // != 0: a big-value pair of a book in use
-        const bool in_c1 = (uint32_t)(p - bv) < (uint32_t)(2 * c1);
-        const uint32_t lb = __builtin_amdgcn_ubfe(Ke, 2, 4);
-        // escape and sign bits: [x - 15 in lb bits] [sign of x] [y - 15 in lb bits] [sign of y]; a value of 0 has no sign bit,
-        // a value below 15 (or a book without linbits) no escape bits: fields of width 0
-        const uint32_t lbx = x > 14 ? lb : 0u, lby = y > 14 ? lb : 0u;
-        const uint32_t nzx = x < 1 ? x : 1u, nzy = y < 1 ? y : 1u;
-        uint32_t ext = __builtin_amdgcn_ubfe(x - 15u, 0, lbx);
-        ext = (ext << nzx) | ((uint32_t)vx >> 31);
-        ext = (ext << lby) | __builtin_amdgcn_ubfe(y - 15u, 0, lby);
-        ext = (ext << nzy) | ((uint32_t)vy >> 31);
-        const uint32_t xb = lbx + nzx + lby + nzy;
-        const bool inside = Ke != 0 || in_c1;
-        // the pair's own code word
-        const uint32_t xx = x > 14 ? 15u : x, yy = y > 14 ? 15u : y;
-        const uint32_t q = (c2[k] | (c2[k + 1] << 2)) & 15u;
-        const bool quad = in_c1 && !((p - bv) & 1);
-        const uint32_t tix = Ke != 0 ? (Ke & 3u) * (uint32_t)PACK_FAM + xx * 16u + yy : (quad ? quad_base + q : (uint32_t)PACK_PT_NONE);
-        const uint32_t word = pt[tix];
+        const uint32_t lb = __builtin_amdgcn_ubfe(P, 6 * k + 2, 4), fam = __builtin_amdgcn_ubfe(P, 6 * k, 2);
+        const pk_u16 c15 = {15, 15};
+        const pk_u16 a = __builtin_bit_cast(pk_u16, __builtin_elementwise_abs(__builtin_bit_cast(pk_i16, w[k])));
+        const pk_u16 cl = __builtin_elementwise_min(a, c15);
+        const pk_u16 nz = pack_pk_min1(a);
+        const pk_u16 lbs = {(uint16_t)lb, (uint16_t)lb};
+        const pk_u16 wid = __builtin_elementwise_sub_sat(lbs, (c15 - cl) * (pk_u16){16, 16}) + nz;       // bits of x's and of y's field
+        const pk_u16 fld = __builtin_elementwise_sub_sat(a, c15) * (pk_u16){2, 2} + (__builtin_bit_cast(pk_u16, w[k]) >> (pk_u16){15, 15});
+        const uint32_t wu = __builtin_bit_cast(uint32_t, wid), fu = __builtin_bit_cast(uint32_t, fld);
+        code1[k] = ((fu & 0xffffu) << (wu >> 16)) | (fu >> 16);
+        n1[k] = (int)((wu & 0xffffu) + (wu >> 16));
+        const uint32_t big = __builtin_amdgcn_udot2(cl, (pk_u16){16, 1}, fam * (uint32_t)PACK_FAM, false);
+        const uint32_t q = __builtin_amdgcn_udot2(__builtin_bit_cast(pk_u16, lowb[k + 1]), (pk_u16){4, 8},
+                                                  __builtin_amdgcn_udot2(__builtin_bit_cast(pk_u16, lowb[k]), (pk_u16){1, 2}, quad_base, false), false);
+        const uint32_t qn = pack_bfi((k & 1) ? ~odd : odd, (uint32_t)PACK_PT_NONE, q);
+        const uint32_t word = pt[k < nb5 ? big : qn] & (uint32_t)__builtin_amdgcn_sbfe((int)INS, 6 * k, 1);
         code0[k] = word & 0xffffffu;
         n0[k] = (int)(word >> 24);
-        code1[k] = inside ? ext : 0u;
-        n1[k] = inside ? (int)xb : 0;
         tot += n0[k] + n1[k];
     }
     // exclusive prefix of the lanes' bit counts
     const int incl = (int)wave_scan_u32((uint32_t)tot);
     const int huff_bits = __builtin_amdgcn_readlane(incl, 63);
-    // The lane's code words are consecutive in the stream: they are gathered in a 64-bit register (in front of them as many
-    // zero bits as the lane's start lies behind a dword boundary) and leave as dwords of the frame image.  A word has at most
-    // 28 bits and fewer than 32 are pending in front of it.  Round 4: after EVERY word the dword the pending bits begin in is
-    // OR-ed into the image, finished or not (an unfinished one is OR-ed again, with more bits, by the next word: the same
-    // bits twice do no harm), and position and count move on by arithmetic -- the flush used to be a per-lane branch, ten
-    // of them per frame.
+    // The lane's code words are consecutive in the stream: they are gathered at the low end of a 64-bit register, each pushed in from
+    // below with ONE 64-bit shift, and leave as dwords of the frame image.  A word has at most 28 bits and fewer than 32 are pending, so
+    // the register never loses a bit that has not left; what has left stays above the pending bits and is never read again.  After every
+    // word one OR goes to the image, without a branch: the dword the word completed (a funnel shift takes it from the register), or
+    // zero where the word did not reach a boundary; position and count move on by arithmetic.
     if (tot) {   // (the lanes behind the last value hold nothing and all stand on ONE dword: 64 ORs of zero into one address, eleven times)
-        const uint32_t pos0 = ustart + (uint32_t)(incl - tot);
-        uint32_t d = pos0 >> 5;
-        uint32_t cnt = pos0 & 31u;
-        uint64_t top = 0;                                                       // the pending bits, from bit 63 down: cnt of them behind the dword boundary
+        uint32_t pos = ustart + (uint32_t)(incl - tot);                         // the lane's place in the frame, in bits: pos & 31 bits are pending
+        uint32_t d = pos >> 5;                                                  // (bits of another lane in front of the lane's first: zero here)
+        uint64_t acc = 0;
         auto append = [&](uint32_t v, int n) {
-            top |= (uint64_t)v << ((64u - cnt - (uint32_t)n) & 63u);             // cnt + n <= 59; (n == 0: v == 0)
-            cnt += (uint32_t)n;
-            atomicOr(&fb[d], (uint32_t)(top >> 32));
-            const uint32_t adv = cnt >> 5;                                      // 0 or 1
-            top <<= 32u * adv; d += adv; cnt &= 31u;
+            acc = (acc << (uint32_t)n) | v;
+            pos += (uint32_t)n;
+            const uint32_t full = __builtin_amdgcn_alignbit((uint32_t)(acc >> 32), (uint32_t)acc, pos);   // (the shift is pos & 31: those stay pending)
+            const uint32_t dn = pos >> 5;                                       // d or d + 1
+            atomicOr(&fb[d], dn != d ? full : 0u);
+            d = dn;
         };
 #pragma unroll
         for (int k = 0; k < 5; k++) { append(code0[k], n0[k]); append(code1[k], n1[k]); }
-        atomicOr(&fb[d], (uint32_t)(top >> 32));                                // what the last word left behind a dword boundary
+        atomicOr(&fb[d], __builtin_amdgcn_alignbit((uint32_t)acc, 0u, pos));     // what the last word left behind a dword boundary
     }
     // stuffing with ones up to part2_3_length (:1433-1446)
-    const int p23 = e == 0 ? p23v[0] : (e == 1 ? p23v[1] : (e == 2 ? p23v[2] : p23v[3]));
     if (huff_bits > p23 || any_bad) { if (lane_p == 0) atomicOr(&wg_err, any_bad ? MP3S_PS_BAD_TABLE : MP3S_PS_OVERFLOW); }   // (LDS)
-    else
-        for (uint32_t s = ustart + huff_bits + 32u * lane; s < ustart + (uint32_t)p23; s += 64u * 32u) {
-            const uint32_t n = (ustart + p23 - s) < 32u ? (ustart + p23 - s) : 32u;
-            lds_put(fb, s, n == 32 ? 0xffffffffu : ((1u << n) - 1), (int)n);
+    else {
+        // the ones are bits [s0, s1) of the image: a lane takes a DWORD of it and ORs the ones that fall into that dword, one OR and no 64-bit
+        // shift (a lane used to take 32 bits from wherever the codes ended: two dwords each)
+        const uint32_t s0 = ustart + (uint32_t)huff_bits, s1 = ustart + (uint32_t)p23;
+        for (uint32_t j = (s0 >> 5) + (uint32_t)lane; 32u * j < s1; j += 64u) {
+            const uint32_t a = s0 > 32u * j ? s0 - 32u * j : 0u;                        // 0 .. 31: the first one of the dword, counted from its top
+            const uint32_t b = s1 - 32u * j < 32u ? s1 - 32u * j : 32u;                 // 1 .. 32: behind the last one
+            atomicOr(&fb[j], (0xffffffffu >> a) & ~(0x7fffffffu >> (b - 1u)));
         }
+    }
     __syncthreads();
     // ---- LDS image -> global bytes: unaligned head / tail as bytes, the aligned interior as dwords
     const int nbytes = whole_slots + pad;
