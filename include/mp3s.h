@@ -1111,7 +1111,8 @@ int mp3s_table_audit_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size
  * runs on the same GPU.  The batch is [B][C][T], channels first, planar, row-major: element (b, c, t) at ((b * C) + c) * T + t; C is 1
  * or 2.  Two element formats, both made from the int16 decode (MP3S_PCM_I16, the reference's sample for sample):
  *   MP3S_BATCH_I16: int16.   MP3S_BATCH_F32: float32 = int16 / 32768 (exact; the convention of WAV loaders).
- * Nothing is resampled: rows are rows, and the records say which rate they run at. */
+ * Nothing is resampled: rows are rows, and the records say which rate they run at -- but for the calls that take a rate, at the
+ * section's end (mp3s_pcm_batch_decode_files_at, mp3s_pcm_batch_encode_at). */
 #define MP3S_BATCH_I16 0
 #define MP3S_BATCH_F32 1
 typedef struct {
@@ -1168,6 +1169,62 @@ int mp3s_pcm_batch_decode_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const
 int mp3s_pcm_batch_encode(mp3s_ctx *ctx, const void *d_in, int n_items, int in_channels, int in_format, int64_t T, const int64_t *n_rows,
                           int samplerate, int bitrate_kbps, const uint8_t *const *hide_bits, const int32_t *n_hide,
                           mp3s_buf **owner, mp3s_file *out, int32_t *status);
+/* The same calls with a sampling rate: decoding writes every slot at ONE rate of the caller's choosing, encoding reads a batch at any
+ * rate.  The calls above are unchanged ("nothing is resampled" holds for them); the filter, the tap table and the output rule are those
+ * of mp3s_wav_resample_info, exactly.  An extension beyond the reference.
+ *  - ratio.  For in_rate > 0 and out_rate > 0: g = gcd, L = out / g, M = in / g, H = 16 if L >= M, else ceil(16 M / L), T = 2 H taps per
+ *    phase.  L > 1280, T > 256 or no table from mp3s_wav_resample_taps(L, M): MP3S_E_UNSUPPORTED.  L = M = 1: not resampled (a copy).
+ *  - decode direction.  A stream of n_in decoded rows (int16, 1 or 2 channels) becomes n_out = ceil(n_in L / M) rows: every channel is
+ *    resampled on its own by the output rule (x = 0 outside [0, n_in), the result clamped to int16).  The resampled int16 rows then go
+ *    through exactly the rules of mp3s_pcm_batch_dev with n_rows := n_out and first_row counted in OUTPUT rows: copy, mono into both
+ *    planes, (l + r) >> 1 / (l + r) / 65536, zeros from valid = clamp(n_out - first_row, 0, T) on.  A stereo stream into one plane is
+ *    resampled per channel FIRST and mixed afterwards (the other order would round differently).
+ *  - encode direction.  An item's int16 rows are what mp3s_pcm_unbatch_dev makes of it (float32 rounded half to even, mono into both
+ *    channels); they are resampled to the target mp3s_wav_resample_info's rule picks for `mode` at the item's rate, the last frame
+ *    is zero-filled and the frames are encoded as mp3s_encode_pcm encodes them at the target rate. */
+typedef struct { int32_t L, M, taps, half; } mp3s_pcm_resample_ratio; /* 16 bytes: out / in = L / M in lowest terms, T = 2 H, H */
+/* no device, no context.  A rate <= 0 or a null pointer: MP3S_E_ARG; a refused ratio: MP3S_E_UNSUPPORTED.  The table is
+ * mp3s_wav_resample_taps(L, M, ...). */
+int mp3s_pcm_resample_plan(int in_rate, int out_rate, mp3s_pcm_resample_ratio *out);
+typedef struct {
+    int64_t src_row;    /* first row of the stream in d_pcm, in rows of nch int16 */
+    int64_t n_rows;     /* INPUT rows the stream has there (>= 0) */
+    int64_t first_row;  /* where the window starts, in OUTPUT rows (>= 0; may lie at or behind ceil(n_rows L / M)) */
+    int32_t slot;       /* b: the item's rows go to d_out[b][.][0..T) */
+    int32_t L, M;       /* the item's own ratio, in lowest terms; 1 / 1: a copy */
+    int32_t reserved;
+} mp3s_pcm_resample_item; /* 40 bytes */
+/* k_pcm_batch_resample alone (k_pcmresample.hpp), asynchronous on the context's stream: mp3s_pcm_batch_dev with the resampler in front,
+ * ONE launch for all items whatever their ratios are.  The items are given on the host only and read before the call returns; what
+ * the kernel needs of them travels on the stream with the launch geometry.  Every element of an item's slot has exactly one writer,
+ * nothing outside it is touched, any T, first_row and element-aligned d_out are taken.  Argument checks as mp3s_pcm_batch_dev's (fields
+ * above 2^40 are refused like negative ones); an item whose ratio the plan refuses or whose L, M are not in lowest terms:
+ * MP3S_E_UNSUPPORTED.  All are answered without a device. */
+int mp3s_pcm_batch_resample_dev(mp3s_ctx *ctx, const int16_t *d_pcm, int nch, const mp3s_pcm_resample_item *h_items, int n_items,
+                                int out_channels, int out_format, int64_t T, void *d_out);
+typedef struct {
+    int32_t n_frames, nch, sampling_rate /* the file's own */, bit_rate;
+    int64_t n_rows;             /* OUTPUT rows: ceil(in_rows L / M) */
+    int64_t first_row, valid_rows, in_rows /* what mp3s_pcm_batch_info.n_rows counts */;
+    int32_t out_rate, L, M, reserved;
+} mp3s_pcm_batch_info_at; /* 64 bytes */
+/* mp3s_pcm_batch_decode_files with every slot at out_rate: the same front end, the same decode batch per channel count, and one
+ * k_pcm_batch_resample launch per batch in the place of k_pcm_batch -- files of 32, 44.1 and 48 kHz share it, each with its own ratio; a
+ * file at out_rate is copied.  first_rows, n_rows and valid_rows count OUTPUT rows.  Status rules, the sizing call (d_out == NULL: n_rows
+ * at the output rate, valid_rows 0) and the zeroing of failed or frameless slots are unchanged.  A file whose rate the plan refuses for
+ * out_rate gets MP3S_E_UNSUPPORTED by the per-file rule of any failing file.  out_rate <= 0: MP3S_E_ARG. */
+int mp3s_pcm_batch_decode_files_at(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int out_rate,
+                                   const int64_t *first_rows /* NULL: 0 */, int64_t T, int out_channels, int out_format, void *d_out,
+                                   size_t out_bytes, mp3s_pcm_batch_info_at *info, int32_t *status);
+/* mp3s_pcm_batch_encode of a batch at ANY sampling rate in_rate.  `mode` takes the non-zero values of MP3S_OPT_WAV_RESAMPLE (1: the auto
+ * rule, or 32000 / 44100 / 48000 forced; anything else MP3S_E_ARG).  Target == in_rate: the call IS mp3s_pcm_batch_encode at that rate,
+ * byte for byte.  Otherwise k_pcm_unbatch lays the items at the source rate into a scratch of frames, the unchanged k_wav_resample
+ * computes them into the encode batch's PCM and the batch is encoded at the target rate: out[i].sampling_rate is the target, n_frames
+ * ceil(ceil(n_rows L / M) / 1152).  A rate the resampler refuses fails the call with MP3S_E_EXIT "Unsupported sampling frequency.";
+ * the bitrate is checked against the target rate.  Items and status as for mp3s_pcm_batch_encode. */
+int mp3s_pcm_batch_encode_at(mp3s_ctx *ctx, const void *d_in, int n_items, int in_channels, int in_format, int64_t T, const int64_t *n_rows,
+                             int in_rate, int mode, int bitrate_kbps, const uint8_t *const *hide_bits, const int32_t *n_hide,
+                             mp3s_buf **owner, mp3s_file *out, int32_t *status);
 
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference

@@ -237,6 +237,30 @@ constexpr uint32_t kResTapsLds = 2048;  // tap pairs (dwords) of a table that is
 inline uint32_t resample_span(uint32_t L, uint32_t M, uint32_t T) { return (uint32_t)(((uint64_t)(kResTile - 1) * M + L - 1) / L) + T; }
 int launch_wav_resample(hipStream_t stream, const uint32_t *d_rows, const WavResampleRun *d_runs, int n_runs, int max_frames /* of one run */,
                         size_t lds_bytes /* the largest (span + staged tap pairs) * 4 of the runs */, int16_t *d_pcm, Profiler *prof);
+// ... and of k_pcm_batch_resample (k_pcmresample.hpp; the rules: include/mp3s.h, mp3s_pcm_batch_resample_dev): k_pcm_batch with that FIR in
+// front.  An item's n_in rows (nch int16 each) from row src_row of the decode's PCM become n_out rows at L / M, of which the window from
+// first_row on goes into the item's slot.  T = 0 (L = M = 1): a copy, taps unused.  span: the input rows a tile stages.  One workgroup per
+// PcmBatchTile; a tile owns kPcmResGroups groups of 8 elements of each output plane (lanes [0, 128) store plane 0, the others plane 1)
+// and computes the kPcmResRows window rows they can lie in.
+struct PcmResampleRun { const uint32_t *taps; int64_t src_row, n_in, n_out, first_row; uint32_t L, M, T, span, taps_lds, mono; int32_t slot; uint32_t pad; };   // 72 bytes
+constexpr int kPcmResGroups = 128, kPcmResRows = 8 * kPcmResGroups + 8;
+inline uint32_t pcm_resample_span(uint32_t L, uint32_t M, uint32_t T) { return T ? (uint32_t)(((uint64_t)(kPcmResRows - 1) * M + L - 1) / L) + T : (uint32_t)kPcmResRows; }
+// dynamic LDS of a launch that holds this run: the computed rows, the staged span and the staged tap pairs
+inline size_t pcm_resample_lds(const PcmResampleRun &r) { return ((size_t)kPcmResRows + r.span + (r.taps_lds ? (size_t)r.L * (r.T / 2) : 0)) * 4; }
+// appends the tiles of n_items items of a batch of T elements a plane; false: more tiles than a grid takes
+template <class Tiles>
+bool pcm_resample_tiles(int n_items, int64_t T, Tiles &tiles)
+{
+    if (n_items <= 0 || T <= 0 || T > ((int64_t)1 << 40)) return false;
+    const uint64_t groups = ((uint64_t)T + 6) / 8 + 1, per = (groups + kPcmResGroups - 1) / kPcmResGroups;
+    if ((uint64_t)tiles.size() + per * (uint64_t)n_items > 0x7fffffffu) return false;
+    for (int i = 0; i < n_items; i++)
+        for (uint64_t f = 0; f < per; f++) tiles.push_back(PcmBatchTile{(uint32_t)i, (uint32_t)f});
+    return true;
+}
+// lds_bytes: the largest pcm_resample_lds of the runs
+int launch_pcm_batch_resample(hipStream_t stream, const int16_t *d_pcm, int nch, const PcmResampleRun *d_runs, const PcmBatchTile *d_tiles, int n_tiles,
+                              size_t lds_bytes, int out_channels, int out_format, int64_t T, void *d_out);
 int launch_wav_import(hipStream_t stream, const uint8_t *d_image, const WavImportRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 int launch_wav_gather(hipStream_t stream, const uint8_t *d_image, const WavRun *d_runs, int n_runs, int max_frames /* of one run */, int16_t *d_pcm);
 

@@ -37,6 +37,7 @@ __constant__ __attribute__((aligned(64))) int32_t c_fl_sign[ANALYSIS_SIGN_STREAM
 #include "k_chain.hpp"
 #include "k_wav.hpp"
 #include "k_resample.hpp"
+#include "k_pcmresample.hpp"
 
 namespace mp3s {
 
@@ -580,6 +581,30 @@ int launch_wav_resample(hipStream_t stream, const uint32_t *d_rows, const WavRes
     for (int r0 = 0; r0 < n_runs; r0 += 32768)
         hipLaunchKernelGGL(k_wav_resample, dim3(gx, (unsigned)std::min(n_runs - r0, 32768)), dim3(256), lds_bytes, stream, d_rows, d_runs, r0, d_pcm);
     if (prof) prof->end(stream, pp);
+    return (int)hipGetLastError();
+}
+
+// k_pcm_batch_resample: one workgroup per tile of d_tiles, the items' ratios in their records; channel counts and format are the launch's
+int launch_pcm_batch_resample(hipStream_t stream, const int16_t *d_pcm, int nch, const PcmResampleRun *d_runs, const PcmBatchTile *d_tiles, int n_tiles,
+                              size_t lds_bytes, int out_channels, int out_format, int64_t T, void *d_out)
+{
+    if (n_tiles <= 0) return 0;
+    const bool f32 = out_format == MP3S_BATCH_F32;
+    if ((nch != 1 && nch != 2) || (out_channels != 1 && out_channels != 2) || (!f32 && out_format != MP3S_BATCH_I16) || T <= 0 || lds_bytes > 64 * 1024 ||
+        ((uintptr_t)d_pcm & (uintptr_t)(2 * nch - 1)) || ((uintptr_t)d_out & (uintptr_t)(f32 ? 3 : 1)))
+        return (int)hipErrorInvalidValue;
+#define PCM_RESAMPLE_LAUNCH(N, C, F) hipLaunchKernelGGL((k_pcm_batch_resample<N, C, F>), dim3((unsigned)n_tiles), dim3(PCMBATCH_THREADS), lds_bytes, stream, d_pcm, d_runs, d_tiles, T, (uint8_t *)d_out)
+    switch ((nch - 1) * 4 + (out_channels - 1) * 2 + (f32 ? 1 : 0)) {
+    case 0: PCM_RESAMPLE_LAUNCH(1, 1, false); break;
+    case 1: PCM_RESAMPLE_LAUNCH(1, 1, true); break;
+    case 2: PCM_RESAMPLE_LAUNCH(1, 2, false); break;
+    case 3: PCM_RESAMPLE_LAUNCH(1, 2, true); break;
+    case 4: PCM_RESAMPLE_LAUNCH(2, 1, false); break;
+    case 5: PCM_RESAMPLE_LAUNCH(2, 1, true); break;
+    case 6: PCM_RESAMPLE_LAUNCH(2, 2, false); break;
+    default: PCM_RESAMPLE_LAUNCH(2, 2, true); break;
+    }
+#undef PCM_RESAMPLE_LAUNCH
     return (int)hipGetLastError();
 }
 

@@ -62,7 +62,7 @@ int wav_encode_plan(WavRead how, const uint8_t *wav, size_t len, int bitrate_kbp
 }
 
 // the packed tap table of a ratio on the device: made and uploaded when the context meets the ratio first, kept until it goes
-static int resample_taps_dev(mp3s_ctx *c, int L, int M, const uint32_t **d_out)
+int resample_taps_dev(mp3s_ctx *c, int L, int M, const uint32_t **d_out)
 {
     for (const mp3s_ctx::ResampleTaps &t : c->res_taps)
         if (t.L == L && t.M == M) { *d_out = t.d; return MP3S_OK; }

@@ -165,6 +165,10 @@ int wav_frame_count(const mp3s_wav_info &w, int64_t *count, const char **msg);
 int wav_import_parse(const uint8_t *file, size_t len, int bitrate_kbps, mp3s_wav_import *out, const char **msg, int resample = 0, mp3s_wav_resample *rs = nullptr);
 // target rate, ratio L / M in lowest terms and filter size (T = 2 H taps per phase) of the resampler; non-zero: the rate is refused
 int wav_resample_plan(int in_rate, int mode, int *out_rate, int *L, int *M, int *T, int *H);
+// the same ratio rules for ANY pair of rates (mp3s_pcm_resample_plan); _plan also asks wav_resample_taps for the table's own bound.
+// L = M = 1: not resampled
+int pcm_resample_ratio(int in_rate, int out_rate, int *L, int *M, int *T, int *H);
+int pcm_resample_plan(int in_rate, int out_rate, int *L, int *M, int *T, int *H);
 // its integer tap table c[L][T] (2^15 scale, every phase sums to 32768, sum |c| <= 65535 over the taps below 2 (H / 2) and over the rest); non-zero: no table for this ratio
 int wav_resample_taps(int L, int M, std::vector<int32_t> &c, int *T);
 // the 44-byte header scipy.io.wavfile.write emits for int16 data

@@ -3,6 +3,8 @@
 #include <stdio.h>
 #include <math.h>
 #include <string.h>
+#include <map>
+#include <mutex>
 
 #include "mp3s_host.h"
 
@@ -240,13 +242,40 @@ int wav_resample_plan(int in_rate, int mode, int *out_rate, int *L, int *M, int 
             if (!target || l <= best) { target = r; best = l; }
         }
     }
-    const int64_t g = gcd(target, in_rate);
-    const int64_t l = target / g, m = in_rate / g;
+    if (pcm_resample_ratio(in_rate, target, L, M, T, H)) return 1;
+    *out_rate = target;
+    return 0;
+}
+
+// the ratio of ANY pair of rates by the same rules (mp3s_pcm_resample_plan: the PCM batch calls that take a rate)
+int pcm_resample_ratio(int in_rate, int out_rate, int *L, int *M, int *T, int *H)
+{
+    if (in_rate <= 0 || out_rate <= 0) return 1;
+    auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
+    const int64_t g = gcd(out_rate, in_rate);
+    const int64_t l = out_rate / g, m = in_rate / g;
     // rho = min(1, L / M); H = ceil(16 / rho)
     const int64_t h = l >= m ? 16 : (16 * m + l - 1) / l;
     if (l > 1280 || 2 * h > 256) return 1;
-    *out_rate = target; *L = (int)l; *M = (int)m; *H = (int)h; *T = (int)(2 * h);
+    *L = (int)l; *M = (int)m; *H = (int)h; *T = (int)(2 * h);
     return 0;
+}
+
+int pcm_resample_plan(int in_rate, int out_rate, int *L, int *M, int *T, int *H)
+{
+    if (pcm_resample_ratio(in_rate, out_rate, L, M, T, H)) return 1;
+    if (*L == 1 && *M == 1) return 0;                  // (not resampled: no table is asked for)
+    // the table's own bound (sum |c| of either half of a phase): a ratio is met again and again, so what it gave is kept
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, bool> known;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = known.find({*L, *M});
+    if (it != known.end()) return it->second ? 0 : 1;
+    std::vector<int32_t> taps;
+    int t = 0;
+    const bool ok = wav_resample_taps(*L, *M, taps, &t) == 0 && t == *T;
+    known[{*L, *M}] = ok;
+    return ok ? 0 : 1;
 }
 
 int wav_resample_taps(int L, int M, std::vector<int32_t> &c, int *T_out)

@@ -63,7 +63,7 @@ enum PoolSlot : int {
     kPoolVarEntries, kPoolVarIx, kPoolVarOut, kPoolVarEnergy, kPoolVarPairs,   // message variants: enc_resolve's launches take all five, the entries inside the first rate-loop launch
                             // (enc_variant_buffers) Ix, Out and Energy -- their selection is through before a resolve begins
     kPoolIs1, kPoolSi1, kPoolPcm1,      // set 1 of a pipe
-    kPoolWavImage, kPoolResampleRows,   // wav_to_device: the files' bytes with the kernels' records behind them; PCM at the source rate for the resampler
+    kPoolWavImage, kPoolResampleRows,   // wav_to_device: the files' bytes with the kernels' records behind them; PCM at the source rate for the resampler (k_wav_resample's input: wav_to_device's imported files, and the frames k_pcm_unbatch makes for mp3s_pcm_batch_encode_at)
     kPoolSelectDev,         // scratch of select_step, grown behind a synchronise of the stream the step was given alone: its users all run on one stream at a time -- the
                             // context's, or for the jobs of a pipe with a tail stream that tail (from pipe_create, which drains the context's stream, to pipe_quiesce, which drains the pipe's)
     kPoolChainDev,          // scratch of mp3s_chain_resolve_dev and mp3s_chain_redo_dev
@@ -678,6 +678,9 @@ struct WavBatch;
 // the files `idx` to the device: their images up, the batch's kernels (launch_wav_batch) queued on the context's stream -> *d_pcm_out =
 // [b.n_all][1152][2] int16 in the context's PCM buffer, the streams back to back in the order of idx (segs[k] = stream k).  Nothing is
 // waited for; the batch's records and the callers' bytes are read by copies in flight until the stream is synchronised.
+// the packed tap table of the ratio L / M on the context's device (pairs of consecutive taps as int16 halves, [L][T / 2] dwords): made and
+// uploaded when the context meets the ratio first, kept until it goes.  For wav_to_device and the PCM batch calls that take a rate
+int resample_taps_dev(mp3s_ctx *c, int L, int M, const uint32_t **d_out);
 int wav_to_device(mp3s_ctx *c, const std::vector<WavIn> &in, const std::vector<int> &idx, std::vector<EncSeg> &segs, WavBatch &b, void **d_pcm_out);
 // mp3s_encode_files with the reader named by the caller
 int encode_files_as(mp3s_ctx *c, WavRead how, const uint8_t *const *wavs, const size_t *lens, int n_files, const int32_t *bitrate_kbps,

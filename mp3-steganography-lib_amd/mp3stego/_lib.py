@@ -233,6 +233,24 @@ class PcmBatchInfo(C.Structure):
                 ("n_rows", C.c_int64), ("first_row", C.c_int64), ("valid_rows", C.c_int64)]
 
 
+class PcmResampleRatio(C.Structure):
+    _fields_ = [("L", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("half", C.c_int32)]
+
+
+class PcmResampleItem(C.Structure):
+    _fields_ = [("src_row", C.c_int64), ("n_rows", C.c_int64), ("first_row", C.c_int64), ("slot", C.c_int32), ("L", C.c_int32), ("M", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class PcmBatchInfoAt(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
+                ("n_rows", C.c_int64), ("first_row", C.c_int64), ("valid_rows", C.c_int64), ("in_rows", C.c_int64),
+                ("out_rate", C.c_int32), ("L", C.c_int32), ("M", C.c_int32), ("reserved", C.c_int32)]
+
+
+PCM_RESAMPLE_ITEM_DTYPE = np.dtype([("src_row", "<i8"), ("n_rows", "<i8"), ("first_row", "<i8"), ("slot", "<i4"), ("L", "<i4"), ("M", "<i4"), ("reserved", "<i4")])
+PCM_BATCH_INFO_AT_DTYPE = np.dtype([("n_frames", "<i4"), ("nch", "<i4"), ("sampling_rate", "<i4"), ("bit_rate", "<i4"), ("n_rows", "<i8"), ("first_row", "<i8"),
+                                    ("valid_rows", "<i8"), ("in_rows", "<i8"), ("out_rate", "<i4"), ("L", "<i4"), ("M", "<i4"), ("reserved", "<i4")])
 PCM_BATCH_ITEM_DTYPE = np.dtype([("src_row", "<i8"), ("n_rows", "<i8"), ("first_row", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
 PCM_UNBATCH_ITEM_DTYPE = np.dtype([("dst_frame", "<i8"), ("n_rows", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
 PCM_BATCH_INFO_DTYPE = np.dtype([("n_frames", "<i4"), ("nch", "<i4"), ("sampling_rate", "<i4"), ("bit_rate", "<i4"),
@@ -305,7 +323,8 @@ SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wai
            "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes",
            "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files", "mp3s_pcm_align_dev", "mp3s_pcm_alignment_files",
            "mp3s_table_audit_dev", "mp3s_table_audit_files",
-           "mp3s_pcm_batch_dev", "mp3s_pcm_unbatch_dev", "mp3s_pcm_batch_decode_files", "mp3s_pcm_batch_encode"]
+           "mp3s_pcm_batch_dev", "mp3s_pcm_unbatch_dev", "mp3s_pcm_batch_decode_files", "mp3s_pcm_batch_encode",
+           "mp3s_pcm_resample_plan", "mp3s_pcm_batch_resample_dev", "mp3s_pcm_batch_decode_files_at", "mp3s_pcm_batch_encode_at"]
 
 REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
 RV_BAD_REF = 1
@@ -433,6 +452,10 @@ def lib():
         L.mp3s_pcm_unbatch_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp]
         L.mp3s_pcm_batch_decode_files.argtypes = [vp, vp, vp, i32, vp, i64, i32, i32, vp, sz, vp, vp]
         L.mp3s_pcm_batch_encode.argtypes = [vp, vp, i32, i32, i32, i64, vp, i32, i32, vp, vp, pvp, vp, vp]
+        L.mp3s_pcm_resample_plan.argtypes = [i32, i32, vp]
+        L.mp3s_pcm_batch_resample_dev.argtypes = [vp, vp, i32, vp, i32, i32, i32, i64, vp]
+        L.mp3s_pcm_batch_decode_files_at.argtypes = [vp, vp, vp, i32, i32, vp, i64, i32, i32, vp, sz, vp, vp]
+        L.mp3s_pcm_batch_encode_at.argtypes = [vp, vp, i32, i32, i32, i64, vp, i32, i32, i32, vp, vp, pvp, vp, vp]
         L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
         L.mp3s_pipe_destroy.argtypes = [vp]
         L.mp3s_pipe_destroy.restype = None
@@ -1268,13 +1291,25 @@ class Context:
         check(lib().mp3s_pcm_unbatch_dev(self.handle, _addr(d_in), int(channels), BATCH_FORMATS[fmt], int(rows), _addr(d_items),
                                          items.ctypes.data, len(items), _addr(d_pcm)))
 
-    def decode_batch(self, mp3s, d_out, out_bytes, rows, first_rows=None, channels=2, fmt="f32", per_file=False):
+    def pcm_batch_resample_dev(self, d_pcm, nch, items, channels, fmt, rows, d_out):
+        """test aid: k_pcm_batch_resample alone (mp3s_pcm_batch_resample_dev), asynchronous on the context's stream: pcm_batch_dev with
+        the resampler in front.  `items`: PCM_RESAMPLE_ITEM_DTYPE records on the host (n_rows in input rows, first_row in output rows,
+        every item with its own ratio L / M in lowest terms; 1 / 1 is a copy), all of them in ONE launch"""
+        items = np.ascontiguousarray(items, dtype=PCM_RESAMPLE_ITEM_DTYPE)
+        check(lib().mp3s_pcm_batch_resample_dev(self.handle, _addr(d_pcm), int(nch), items.ctypes.data, len(items), int(channels),
+                                                BATCH_FORMATS[fmt], int(rows), _addr(d_out)))
+
+    def decode_batch(self, mp3s, d_out, out_bytes, rows, first_rows=None, channels=2, fmt="f32", per_file=False, samplerate=None):
         """Decode a list of MP3 files into the caller's device memory as ONE planar batch [len(mp3s)][channels][rows] of fmt ("f32":
         int16 / 32768, or "i16") at the device address d_out (mp3s_pcm_batch_decode_files): file i's rows from first_rows[i] (0) on
         into slot i, zeros behind its last row; no PCM comes down.  Returns one dict per file: n_frames, channels, sampling_rate,
         bit_rate, n_rows, first_row, valid_rows (the rows of the slot that are samples).  per_file=True: a file that cannot be
         decoded (None included) yields the Mp3sError it alone would raise and a zeroed slot, the others are unaffected; otherwise
-        the first such file fails the call.  d_out=None: the sizing call -- only the front end runs, valid_rows is 0."""
+        the first such file fails the call.  d_out=None: the sizing call -- only the front end runs, valid_rows is 0.
+        samplerate (None: nothing is resampled, the call and the dicts above): every slot at that sampling rate, each file resampled
+        by its own ratio on the device (mp3s_pcm_batch_decode_files_at); first_rows, n_rows and valid_rows then count rows at
+        `samplerate`, sampling_rate stays the file's own and the dicts gain in_rows (the rows the file decodes to), out_rate, L and M
+        (out_rate / sampling_rate in lowest terms).  A file whose rate the resampler refuses for `samplerate` fails like any other."""
         n = len(mp3s)
         if n == 0:
             return []
@@ -1287,23 +1322,37 @@ class Context:
             if len(first_rows) != n:
                 raise ValueError("one first row per file")
             first = (C.c_int64 * n)(*[int(x) for x in first_rows])
-        info, status = (PcmBatchInfo * n)(), (C.c_int32 * n)()
+        status = (C.c_int32 * n)()
+        if samplerate is not None:
+            info = (PcmBatchInfoAt * n)()
+            check(lib().mp3s_pcm_batch_decode_files_at(self.handle, ptrs, lens, n, int(samplerate), first, int(rows), int(channels), BATCH_FORMATS[fmt],
+                                                       _addr(d_out), int(out_bytes), info, status if per_file else None))
+            return _per_file(info, status, lambda x: {
+                "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate, "n_rows": x.n_rows,
+                "first_row": x.first_row, "valid_rows": x.valid_rows, "in_rows": x.in_rows, "out_rate": x.out_rate, "L": x.L, "M": x.M})
+        info = (PcmBatchInfo * n)()
         check(lib().mp3s_pcm_batch_decode_files(self.handle, ptrs, lens, n, first, int(rows), int(channels), BATCH_FORMATS[fmt], _addr(d_out),
                                                 int(out_bytes), info, status if per_file else None))
         return _per_file(info, status, lambda x: {
             "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate, "n_rows": x.n_rows,
             "first_row": x.first_row, "valid_rows": x.valid_rows})
 
-    def batch_rows(self, mp3s, per_file=False):
-        """the sizing call of decode_batch: the dicts it returns ("n_rows" = the rows file i decodes to), from the host front end alone"""
-        return self.decode_batch(mp3s, None, 0, 0, per_file=per_file)
+    def batch_rows(self, mp3s, per_file=False, samplerate=None):
+        """the sizing call of decode_batch: the dicts it returns ("n_rows" = the rows file i decodes to, at `samplerate` when one is
+        given), from the host front end alone"""
+        return self.decode_batch(mp3s, None, 0, 0, per_file=per_file, samplerate=samplerate)
 
-    def encode_batch(self, d_in, n_items, channels, fmt, rows, lengths, samplerate, bitrate=320, hide_bits=None, messages=None, per_file=False):
+    def encode_batch(self, d_in, n_items, channels, fmt, rows, lengths, samplerate, bitrate=320, hide_bits=None, messages=None, per_file=False,
+                     resample=0):
         """Encode the items of a planar batch [n_items][channels][rows] of fmt at the device address d_in as ONE device batch
         (mp3s_pcm_batch_encode): item i is its first lengths[i] rows (1 .. rows), the last frame zero-filled, mono into both channels,
         float32 rounded to int16 half-even.  hide_bits / messages as for encode_files.  Whatever wrote d_in must have finished.
         Returns the dicts encode_files returns; per_file=True: an item that fails (a length outside 1 .. rows) yields its Mp3sError,
-        otherwise the first such item fails the call."""
+        otherwise the first such item fails the call.
+        resample (0: the batch must be at 32 000 / 44 100 / 48 000 Hz, today's call): the batch is at ANY rate `samplerate` and is
+        resampled on the device to the rate the "wav_resample" option's value would pick for it -- 1: the auto rule (a supported
+        rate stays, 16 000 -> 32 000, 22 050 -> 44 100 ...), or 32000 / 44100 / 48000 forced (mp3s_pcm_batch_encode_at); the dicts'
+        sampling_rate is that target and the bitrate is checked against it."""
         n = int(n_items)
         if len(lengths) != n:
             raise ValueError("one length per item")
@@ -1320,8 +1369,12 @@ class Context:
             hlen = (C.c_int32 * n)(*[0 if h is None else len(h) for h in hbs])
         nr = (C.c_int64 * max(n, 1))(*[int(x) for x in lengths])
         out, status, owner = (File * max(n, 1))(), (C.c_int32 * max(n, 1))(), C.c_void_p()
-        check(lib().mp3s_pcm_batch_encode(self.handle, _addr(d_in), n, int(channels), BATCH_FORMATS[fmt], int(rows), nr, int(samplerate),
-                                          int(bitrate), hptr, hlen, C.byref(owner), out, status if per_file else None))
+        if resample:
+            check(lib().mp3s_pcm_batch_encode_at(self.handle, _addr(d_in), n, int(channels), BATCH_FORMATS[fmt], int(rows), nr, int(samplerate),
+                                                 int(resample), int(bitrate), hptr, hlen, C.byref(owner), out, status if per_file else None))
+        else:
+            check(lib().mp3s_pcm_batch_encode(self.handle, _addr(d_in), n, int(channels), BATCH_FORMATS[fmt], int(rows), nr, int(samplerate),
+                                              int(bitrate), hptr, hlen, C.byref(owner), out, status if per_file else None))
         own = _Owner(owner)
         del hbs
         return _per_file(out, status, lambda f: {
@@ -1582,6 +1635,15 @@ def wav_resample_info(data: bytes, bitrate=320, mode=1):
     out = {k: getattr(w, k) for k, _ in WavResample._fields_ if k != "in_"}
     out["in"] = {k: getattr(w.in_, k) for k, _ in WavImport._fields_}
     return out
+
+
+def pcm_resample_plan(in_rate, out_rate):
+    """the ratio the PCM batch calls resample in_rate -> out_rate with (include/mp3s.h mp3s_pcm_resample_plan) -> dict(L, M, taps, half):
+    out_rate / in_rate = L / M in lowest terms, taps = 2 * half per phase; L = M = 1: not resampled.  Raises Mp3sError (E_UNSUPPORTED)
+    for a ratio the resampler refuses.  The table is wav_resample_taps(L, M).  No GPU."""
+    r = PcmResampleRatio()
+    check(lib().mp3s_pcm_resample_plan(int(in_rate), int(out_rate), C.byref(r)))
+    return {k: getattr(r, k) for k, _ in PcmResampleRatio._fields_}
 
 
 def wav_resample_taps(L, M):

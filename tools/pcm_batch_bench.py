@@ -6,7 +6,10 @@ Two ways to one planar float32 batch [files][2][rows] in device memory, in one p
 warm-up: Context.decode_batch, and the route there was before it -- Context.decode_streams (int16), numpy's transpose and scale
 into the batch layout, one upload.  250 files of 40 frames, and one file of 10 000 frames, 44.1 kHz / 128 kbit/s; the results are
 compared bit for bit first.  Then k_pcm_batch and k_pcm_unbatch alone on 10 000 stereo frames already in device memory, between
-mp3s_timer_start and mp3s_timer_stop, beside the bytes they move divided by what mp3s_bench_copy reports."""
+mp3s_timer_start and mp3s_timer_stop, beside the bytes they move divided by what mp3s_bench_copy reports.
+Then the calls that take a sampling rate, each beside the same call at the native rate, taken in turn: Context.decode_batch of the two
+lists at 44 100 -> 16 000 Hz, k_pcm_batch_resample alone at that ratio beside k_pcm_batch, and Context.encode_batch of a batch at
+16 000 Hz (resample=1: -> 32 000 Hz) beside the same audio at 32 000 Hz (every row twice: the same number of frames to encode)."""
 import argparse
 import json
 import os
@@ -95,6 +98,57 @@ def kernels_alone(ctx, _lib, frames, repeats, gb_per_s):
     return out
 
 
+def decode_at(ctx, files, rate, repeats):
+    """decode_batch at the files' own rate and at `rate`, float32 stereo, in turn"""
+    rows = max(i["n_rows"] for i in ctx.batch_rows(files))
+    rows_at = max(i["n_rows"] for i in ctx.batch_rows(files, samplerate=rate))
+    d_out = ctx.alloc(len(files) * 2 * rows * 4)
+    t = alternate_ms([lambda: ctx.decode_batch(files, d_out, len(files) * 2 * rows * 4, rows, channels=2, fmt="f32"),
+                      lambda: ctx.decode_batch(files, d_out, len(files) * 2 * rows_at * 4, rows_at, channels=2, fmt="f32", samplerate=rate)], repeats)
+    ctx.free(d_out)
+    return {"files": len(files), "rows": rows, "rows_at_rate": rows_at, "out_rate": rate, "native_wall_ms": t[0], "at_rate_wall_ms": t[1],
+            "at_rate_over_native": round(t[1]["median"] / t[0]["median"], 3)}
+
+
+def resample_kernel_alone(ctx, _lib, frames, L, M, repeats):
+    """k_pcm_batch and k_pcm_batch_resample on the same stereo frames in device memory, float32 stereo out, between the context's timers"""
+    rows = frames * 1152
+    rows_at = -(-rows * L // M)
+    rng = np.random.default_rng(5)
+    d_pcm = ctx.to_device(rng.integers(-32768, 32768, size=(rows, 2), dtype=np.int64).astype(np.int16))
+    items = np.array([(0, rows, 0, 0, 0)], dtype=_lib.PCM_BATCH_ITEM_DTYPE)
+    ritems = np.array([(0, rows, 0, 0, L, M, 0)], dtype=_lib.PCM_RESAMPLE_ITEM_DTYPE)
+    d_items, d_batch = ctx.to_device(items), ctx.alloc(2 * rows * 4)
+    out = {"frames": frames, "L": L, "M": M}
+    for name, call in (("k_pcm_batch f32", lambda: ctx.pcm_batch_dev(d_pcm, 2, d_items, items, 2, "f32", rows, d_batch)),
+                       ("k_pcm_batch_resample f32", lambda: ctx.pcm_batch_resample_dev(d_pcm, 2, ritems, 2, "f32", rows_at, d_batch))):
+        t = []
+        for k in range(repeats + 5):
+            ctx.timer_start()
+            call()
+            ms = ctx.timer_stop()
+            if k >= 5:
+                t.append(ms)
+        out[name] = {"timer_ms": summary(t)}
+    for d in (d_pcm, d_items, d_batch):
+        ctx.free(d)
+    return out
+
+
+def encode_at(ctx, n_items, frames, repeats):
+    """encode_batch of int16 stereo items at 16 000 Hz (resample=1: 32 000 Hz) and of the same audio at 32 000 Hz (every row twice), in turn"""
+    from synth_pcm import synth_pcm
+    rows = frames * 1152
+    x = np.stack([np.ascontiguousarray(synth_pcm(frames, seed=3000 + i).T) for i in range(n_items)])      # [items][2][rows]
+    d_16, d_32 = ctx.to_device(x), ctx.to_device(np.repeat(x, 2, axis=2))
+    t = alternate_ms([lambda: ctx.encode_batch(d_32, n_items, 2, "i16", 2 * rows, [2 * rows] * n_items, 32000, 128),
+                      lambda: ctx.encode_batch(d_16, n_items, 2, "i16", rows, [rows] * n_items, 16000, 128, resample=1)], repeats)
+    for d in (d_16, d_32):
+        ctx.free(d)
+    return {"items": n_items, "frames_in": frames, "frames_out": 2 * frames, "native_32000_wall_ms": t[0], "from_16000_wall_ms": t[1],
+            "resampled_over_native": round(t[1]["median"] / t[0]["median"], 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=30)
@@ -109,6 +163,11 @@ def main():
     for name, files in loads.items():
         out[name] = two_routes(ctx, _lib, files, args.repeats)
     out["kernels alone"] = kernels_alone(ctx, _lib, 10000, args.repeats, ctx.bench_copy())
+    for name, files in loads.items():
+        out[name + " at 16 000 Hz"] = decode_at(ctx, files, 16000, args.repeats)
+    out["resample kernel alone"] = resample_kernel_alone(ctx, _lib, 10000, 160, 441, args.repeats)
+    out["encode 250 items of 40 frames from 16 000 Hz"] = encode_at(ctx, 250, 40, max(3, args.repeats // 3))
+    out["encode one item of 10 000 frames from 16 000 Hz"] = encode_at(ctx, 1, 10000, max(3, args.repeats // 3))
     ctx.close()
     print(json.dumps(out))
 
