@@ -20,6 +20,18 @@
 #include <type_traits>
 #include "analysis_plan.h"
 #include "analysis_sign_plan.h"
+#ifndef MP3S_AN_CLOCKS
+#define MP3S_AN_CLOCKS 0   // 1: the shader clocks a wave of k_enc_analysis spends in staging, window sums, matrixing and write-out, into g_an_clocks, read by
+                           // mp3s_debug_an_clocks (a probe: tools/an_clocks.py; such a build is not the product's)
+#endif
+#if MP3S_AN_CLOCKS
+__device__ uint32_t g_an_clocks[4096 * 8];
+extern "C" __attribute__((visibility("default"))) int mp3s_debug_an_clocks(uint32_t *out)
+{
+    (void)hipDeviceSynchronize();
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_an_clocks), sizeof(uint32_t) * 4096 * 8);
+}
+#endif
 
 namespace mp3s {
 
@@ -74,6 +86,10 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
                                                   uint32_t *lds, int32_t *__restrict__ SB, uint32_t *rows, long tile_t0, long lo, long hi, bool shared, Between between)
 {
     int16_t *tw = reinterpret_cast<int16_t *>(lds);
+#if MP3S_AN_CLOCKS
+    const unsigned long long ck_start = __builtin_readcyclecounter();
+    unsigned long long ck_out = 0;
+#endif
     // stage rows t0-15 .. t0+63 of channel ch (zeros outside the batch): the tile is one contiguous piece of the interleaved PCM,
     // read 16 bytes (four samples of both channels) per lane and trip, the wave's channel picked out by two byte permutes
     // (sample by sample it was forty trips of a dozen instructions: a tenth of the kernel's vector instructions)
@@ -81,15 +97,32 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
         const int c0 = (int)(t0 - 15) * 8, c1 = (int)Ts * 8;     // the tile's first chunk and the batch's end, in 16-byte chunks (Ts < 2^28)
         const uint4 *gp = reinterpret_cast<const uint4 *>(pcm);
         const uint32_t sel = ch ? 0x07060302u : 0x05040100u;
-        for (int c = lane; c < 79 * 8; c += 64) {
-            const int gc = c0 + c;
-            uint4 q = make_uint4(0, 0, 0, 0);
-            if (gc >= 0 && gc < c1) q = gp[gc];
+        // All ten loads of a lane are requested before the first of them is used: every load goes to an address inside the batch (clamped;
+        // a chunk outside the batch becomes zeros behind the load), so there is no branch around a load and nothing to wait for between
+        // them.  (As a loop with a run-time trip count and a load under a branch it was one load at a time: ten memory latencies in a row
+        // at the head of every wave, a third of its life.)  The tenth trip holds 56 chunks: its other eight lanes load a clamped address
+        // again and write nothing.  A wave of k_enc_fused that lies wholly behind the batch loads the batch's last chunk ten times and
+        // writes zeros (it asked for nothing before); every address is inside the batch either way.
+        constexpr int TRIPS = (79 * 8 + 63) / 64, LAST = 79 * 8 - 64 * (TRIPS - 1);
+        uint4 q[TRIPS];
+#pragma unroll
+        for (int i = 0; i < TRIPS; i++) {
+            const int gc = c0 + lane + 64 * i;
+            q[i] = gp[gc < 0 ? 0 : gc < c1 ? gc : c1 - 1];
+        }
+#pragma unroll
+        for (int i = 0; i < TRIPS; i++) {
+            const int c = lane + 64 * i, gc = c0 + c;
+            const bool in = gc >= 0 && gc < c1;
+            // (the whole chunk is used HERE: without the statement half a load was moved under `in`, behind a branch and a wait for all ten;
+            //  volatile, so that the ten stay in this order behind the loads -- not volatile, five of them were hoisted between the loads,
+            //  which then went out in three batches of 6, 2 and 2 with a full wait between them)
+            asm volatile("" : "+v"(q[i].x), "+v"(q[i].y), "+v"(q[i].z), "+v"(q[i].w));
             uint2 o;
-            o.x = __builtin_amdgcn_perm(q.y, q.x, sel);
-            o.y = __builtin_amdgcn_perm(q.w, q.z, sel);
+            o.x = in ? __builtin_amdgcn_perm(q[i].y, q[i].x, sel) : 0u;
+            o.y = in ? __builtin_amdgcn_perm(q[i].w, q[i].z, sel) : 0u;
             uint32_t *dst = reinterpret_cast<uint32_t *>(tw + (c >> 3) * ENC_ROW + (c & 7) * 4);   // (rows are 4-byte aligned)
-            dst[0] = o.x; dst[1] = o.y;
+            if (i < TRIPS - 1 || lane < LAST) { dst[0] = o.x; dst[1] = o.y; }
         }
     } else {                                                    // (a caller's PCM that does not start on a 16-byte boundary)
         for (int e = lane; e < 79 * 32; e += 64) {
@@ -102,6 +135,9 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
+#if MP3S_AN_CLOCKS
+    const unsigned long long ck_staged = __builtin_readcyclecounter();
+#endif
     const long t = t0 + lane;
     const bool valid = t >= 0 && t < Ts;
     long s0 = 0;
@@ -163,6 +199,10 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
     };
     if (starts_inside) window_sums(std::true_type{}); else window_sums(std::false_type{});
 #undef MP3S_LDS_HI16
+#if MP3S_AN_CLOCKS
+    asm volatile("" : "+v"(y[0]), "+v"(y[31]), "+v"(y[32]), "+v"(y[63]));
+    const unsigned long long ck_summed = __builtin_readcyclecounter();
+#endif
     // ---- s[sb] = sum_j mul(fl[sb][j], y[j])   (MP3_Encoder.py:358-368); four bands per pass: {p, 15 - p, 16 + p, 31 - p}.  The filter is
     // cos((2 sb + 1)(16 - j) pi / 64): within such a set the coefficients of a column repeat themselves (16 - j = 2 mod 4: in two pairs; a multiple
     // of 4: all four; j = 48: zeros) wherever the table's rounding has not pulled them two units apart -- and a product with the same coefficient
@@ -256,6 +296,9 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
             if constexpr (q == 3 && !TILE) {
                 // ---- sixteen bands of the 64 slots are complete: out 16 bytes per lane, four lanes (= four pieces) per row, sixteen rows per trip
                 constexpr int g = P >> 2;
+#if MP3S_AN_CLOCKS
+                const unsigned long long ck_o = __builtin_readcyclecounter();
+#endif
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 __builtin_amdgcn_wave_barrier();
                 // (the trip's sixteen bands -- 4g.., 12-4g.., 16+4g.., 28-4g.. -- lie SIDE BY SIDE in the row: sb_pos, below; 64 contiguous bytes per row
@@ -269,6 +312,9 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
                 }
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 __builtin_amdgcn_wave_barrier();         // (the tile is free for the other sixteen bands)
+#if MP3S_AN_CLOCKS
+                ck_out += __builtin_readcyclecounter() - ck_o;
+#endif
             }
     };
     // ---- The same sums with a product computed once wherever coefficients of a pass's column are equal in ABSOLUTE value (analysis_sign_plan.h,
@@ -367,6 +413,14 @@ __device__ __forceinline__ void enc_analysis_wave(const int16_t *__restrict__ pc
         use_signed = __ballot(counts && ymin == 0u) == 0;
     }
     if (use_signed) matrix_signed(); else matrix_equal(finish_pass);
+#if MP3S_AN_CLOCKS
+    if (!TILE && lane == 0) {
+        const unsigned long long ck_end = __builtin_readcyclecounter();
+        uint32_t *d = g_an_clocks + ((size_t)((t0 >> 6) * 2 + ch) & 4095) * 8;
+        d[0] = (uint32_t)(ck_staged - ck_start); d[1] = (uint32_t)(ck_summed - ck_staged); d[2] = (uint32_t)(ck_end - ck_summed - ck_out);
+        d[3] = (uint32_t)ck_out; d[4] = (uint32_t)(ck_end - ck_start); d[5] = (starts_inside ? 1u : 0u) | (use_signed ? 2u : 0u);
+    }
+#endif
 }
 
 // SB layout: int32 [ch][Ts][32] with Ts = n_frames * 36 slots (a 128-byte row per slot); band b of a slot sits at sb_pos(b) of its row -- the order in
