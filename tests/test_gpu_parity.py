@@ -54,6 +54,23 @@ def test_decode_transform_reference_chain(ctx, mlib, golden_dir):
         assert np.array_equal(f32, ref.astype(np.float32)), name
 
 
+@pytest.mark.parametrize("opts", [dict(), dict(fused_decode=0), dict(fast_imdct=0)], ids=["defaults", "fused_decode=0", "fast_imdct=0"])
+def test_decode_transform_reference_chain_int16(ctx, mlib, orc, golden_dir, opts):
+    """the same cases through the int16 kernels (the stream kernel; the two fast kernels; the unmirrored IMDCT): the golden PCM, truncated"""
+    g = np.load(os.path.join(golden_dir, "g4_decode_chain.npz"))
+    old = {k: ctx.get_option(k) for k in opts}
+    try:
+        for k, v in opts.items():
+            ctx.set_option(k, v)
+        for name in sorted({k.split("__")[0] for k in g.files}):
+            isv, si, hdr, nch = _chain_batch(mlib, g, name)
+            i16 = ctx.decode_transform(isv, si, hdr, nch, 0, mlib.MP3S_PCM_I16)
+            assert np.array_equal(i16, orc.pcm_to_i16(g[name + "__pcm"].reshape(-1, nch))), name
+    finally:
+        for k, v in old.items():
+            ctx.set_option(k, v)
+
+
 def test_decode_batch_of_streams_and_halo(ctx, mlib, orc, golden_dir):
     """several streams in one batch (stream_first) and chunked decoding with a 1-frame halo"""
     g = np.load(os.path.join(golden_dir, "g4_decode_chain.npz"))

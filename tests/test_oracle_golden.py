@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+import decode_edges
+
 
 def sha(b):
     return hashlib.sha256(bytes(b)).hexdigest()
@@ -82,46 +84,12 @@ def _chain_cases(golden_dir):
 
 def test_oracle_decode_chain(orc, golden_dir):
     g, names = _chain_cases(golden_dir)
-    L = orc.lib()
     for name in names:
-        hdr, isv, pcm_ref = g[name + "__hdr"], g[name + "__is"], g[name + "__pcm"]
-        sr_idx = int((hdr[2] >> 2) & 3)
-        mode = int(hdr[3] >> 6)
-        ms = mode == 1 and (hdr[3] & 0x20)
-        nch = 1 if mode == 3 else 2
-        prev = np.zeros((2, 32 * 18))
-        fifo = np.zeros((2, 1024))
+        isv, si, hdr, nch = decode_edges.g4_batch(g, name)
+        pcm_ref = g[name + "__pcm"]
+        pcm = decode_edges.oracle_chain(orc, isv, si, hdr, nch)
         for f in range(isv.shape[0]):
-            smp = isv[f].astype(np.float64)
-            for gr in range(2):
-                for ch in range(nch):
-                    s = np.ascontiguousarray(smp[gr, ch])
-                    L.orc_requantize(s, int(g[name + "__gg"][f][gr][ch]), int(g[name + "__sfs"][f][gr][ch]),
-                                     int(g[name + "__bt"][f][gr][ch]), int(g[name + "__mixed"][f][gr][ch]),
-                                     int(g[name + "__pre"][f][gr][ch]),
-                                     np.ascontiguousarray(g[name + "__sbg"][f][gr][ch], dtype=np.int32),
-                                     np.ascontiguousarray(g[name + "__sfl"][f][gr][ch], dtype=np.int32),
-                                     np.ascontiguousarray(g[name + "__sfsh"][f][gr][ch], dtype=np.int32), sr_idx)
-                    smp[gr, ch] = s
-                if ms:
-                    a, b = np.ascontiguousarray(smp[gr, 0]), np.ascontiguousarray(smp[gr, 1])
-                    L.orc_ms_stereo(a, b)
-                    smp[gr, 0], smp[gr, 1] = a, b
-                for ch in range(nch):
-                    s = np.ascontiguousarray(smp[gr, ch])
-                    bt, mx = int(g[name + "__bt"][f][gr][ch]), int(g[name + "__mixed"][f][gr][ch])
-                    if bt == 2 or mx:
-                        L.orc_reorder(s, sr_idx)
-                    else:
-                        L.orc_alias_reduction(s)
-                    L.orc_imdct(s, bt, prev[ch])
-                    L.orc_frequency_inversion(s)
-                    L.orc_synth_filter_bank(s, fifo[ch])
-                    smp[gr, ch] = s
-            out = np.zeros((1152, nch))
-            for gr in range(2):
-                for ch in range(nch):
-                    out[gr * 576:(gr + 1) * 576, ch] = smp[gr, ch]
+            out = pcm[f * 1152:(f + 1) * 1152]
             assert np.array_equal(out, pcm_ref[f]), (name, f)
 
 
