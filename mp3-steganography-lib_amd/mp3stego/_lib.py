@@ -1,263 +1,35 @@
-"""ctypes binding of the C-ABI in include/mp3s.h (libmp3s_hip.so, built in-tree by ../Makefile).
+"""ctypes binding of the C-ABI in include/mp3s.h: the calls.  What mirrors the header -- constants, records, the prototype table, lib()
+and check() -- is mp3stego/_abi.py and is re-exported here; Context, Pipe, StreamIndex and the host helpers below are what calls it.
 
 This is the only place the Python side touches native code.  There is no CPU fallback: if the
 shared library is missing, or no MI355X is visible, the first call that needs the transforms raises.
+
+Lifetimes, the one rule every call here follows:
+  - what a native call reads (byte strings, the numpy views of them, pointer and length arrays) is held in locals of the calling
+    method until the call returns, and in Pipe._keep[ticket] until the job is collected.  The helpers that build such arguments
+    (_file_list, _pair_lists, _message, _message_list, _hide_bits, _hide_bits_list, _encode_args) return what has to stay alive
+    explicitly, beside the pointers; the caller binds it to a name, and that name is the keep-alive.
+  - a result that looks into library memory (_view_owned, _owned_bytes) holds an _Owner, which frees the mp3s_buf when the last such
+    result is gone; a result that is copied (_view, C.string_at) is made inside `with _Owner(owner):`, which frees it at the end.
+  - device memory a method allocates for the length of one call comes from Context.device_scope(), which frees it on the way out.
 """
 import ctypes as C
 import os
-import threading
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmp3s_hip.so")
+from . import _abi
+from ._abi import *  # noqa: F401,F403
+from ._abi import _HERE, _lock  # noqa: F401
 
-MP3S_PCM_I16, MP3S_PCM_F32, MP3S_PCM_F64 = 0, 1, 2
-E_NO_DEVICE, E_HIP, E_ARG, E_MALFORMED, E_UNSUPPORTED, E_STEP_RANGE, E_NOMEM, E_EXIT, E_BUSY, E_TABLES = -1, -2, -3, -4, -5, -6, -7, -8, -9, -10
-RF_ACTIVE, RF_USED_ADDR_IN, RF_STEP_RANGE, RF_LOG_GUARD, RF_LISTED = 1, 2, 4, 8, 16
+_EMPTY = C.c_char()          # where an empty file's pointer points (a null pointer is an argument error)
+_PCM_DTYPES = {MP3S_PCM_I16: np.int16, MP3S_PCM_F32: np.float32, MP3S_PCM_F64: np.float64}
 
 
-class Mp3sError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__(f"mp3s error {code}: {msg}")
-        self.code = code
-        self.text = msg      # for E_EXIT: the exact string the reference passes to sys.exit()
-
-
-class GranuleSI(C.Structure):
-    _fields_ = [("global_gain", C.c_uint8), ("scalefac_scale", C.c_uint8), ("block_type", C.c_uint8),
-                ("mixed_block_flag", C.c_uint8), ("preflag", C.c_uint8), ("sub_block_gain", C.c_uint8 * 3),
-                ("scale_fac_l", C.c_uint8 * 22), ("scale_fac_s", C.c_uint8 * 39), ("pad", C.c_uint8 * 3)]
-
-
-GRANULE_SI_DTYPE = np.dtype([("global_gain", "u1"), ("scalefac_scale", "u1"), ("block_type", "u1"),
-                             ("mixed_block_flag", "u1"), ("preflag", "u1"), ("sub_block_gain", "u1", (3,)),
-                             ("scale_fac_l", "u1", (22,)), ("scale_fac_s", "u1", (3, 13)), ("pad", "u1", (3,))])
-FRAME_HDR_DTYPE = np.dtype([("sr_idx", "u1"), ("nch", "u1"), ("ms_stereo", "u1"), ("flags", "u1"),
-                            ("stream_first", "<u4")])
-RATE_FRAME_DTYPE = np.dtype([("max_bits", "<i4"), ("sr_idx", "<i4"), ("hide_end", "<i4"), ("stream", "<i4")])
-UNIT_SIDE_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"),
-                            ("scalefac_compress", "u1"), ("window_switching", "u1"), ("block_type", "u1"),
-                            ("mixed_block_flag", "u1"), ("table_select", "u1", (3,)), ("region0_count", "u1"),
-                            ("region1_count", "u1"), ("preflag", "u1"), ("scalefac_scale", "u1"),
-                            ("count1table_select", "u1"), ("sub_block_gain", "u1", (3,))])
-FRAME_SIDE_DTYPE = np.dtype([("md_off", "<u4"), ("md_len", "<u4"), ("nch", "u1"), ("sr_idx", "u1"), ("ms_stereo", "u1"),
-                             ("flags", "u1"), ("scfsi", "u1", (2, 4)), ("unit", UNIT_SIDE_DTYPE, (2, 2)),
-                             ("reserved", "<u4")])
-assert UNIT_SIDE_DTYPE.itemsize == 20 and FRAME_SIDE_DTYPE.itemsize == 104
-GR_OUT_DTYPE = np.dtype([("part2_3_length", "<i4"), ("big_values", "<i4"), ("count1", "<i4"),
-                         ("quantizer_step", "<i4"), ("region0_count", "<i4"), ("region1_count", "<i4"),
-                         ("count1table_select", "<i4"), ("table_select", "<i4", (3,)), ("address", "<i4", (3,)),
-                         ("n_tables", "<i4"), ("flags", "<i4"), ("reserved0", "<i4"), ("xrmax", "<i4"),
-                         ("reserved", "<i4")])
-assert GRANULE_SI_DTYPE.itemsize == 72 and FRAME_HDR_DTYPE.itemsize == 8 and GR_OUT_DTYPE.itemsize == 72
-CHAIN_SEG_DTYPE = np.dtype([("first_frame", "<i4"), ("n_frames", "<i4"), ("hide_base", "<i4"), ("hide_begin", "<i4"),
-                            ("hide_end", "<i4"), ("reserved", "<i4"), ("chain_in", "<i4", (4, 4))])
-CHAIN_SEG_OUT_DTYPE = np.dtype([("cursor", "<i8"), ("chain", "<i4", (4, 4)), ("carry_used", "<i4"), ("reserved", "<i4")])
-assert CHAIN_SEG_DTYPE.itemsize == 88 and CHAIN_SEG_OUT_DTYPE.itemsize == 80
-
-
-class Parsed(C.Structure):
-    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("n_bits", C.c_int32), ("dup_last_frame", C.c_int32), ("is_", C.c_void_p), ("si", C.c_void_p),
-                ("hdr", C.c_void_p), ("bits", C.c_void_p), ("table_select", C.c_void_p), ("frame_size", C.c_void_p)]
-
-
-class Scanned(C.Structure):
-    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("n_bits", C.c_int32), ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("max_part2_3_length", C.c_int32),
-                ("side", C.c_void_p),
-                ("hdr", C.c_void_p), ("blob", C.c_void_p), ("blob_len", C.c_size_t), ("bits", C.c_void_p),
-                ("frame_size", C.c_void_p)]
-
-
-FRAME_REF_DTYPE = np.dtype([("file_off", "<u4"), ("md_off", "<u4"), ("md_len", "<u2"), ("frame_size", "<u2"), ("stream", "<u2"), ("flags", "<u2")])
-STREAM_REF_DTYPE = np.dtype([("base", "<u4"), ("end", "<u4"), ("first_frame", "<u4"), ("n_frames", "<u4"), ("prev_size", "<u2", (9,)),
-                             ("reserved", "<u2", (3,))])
-assert FRAME_REF_DTYPE.itemsize == 16 and STREAM_REF_DTYPE.itemsize == 40
-PS_INHERITS, PS_MISMATCH = 1, 2
-
-
-class StreamRef(C.Structure):
-    _fields_ = [("base", C.c_uint32), ("end", C.c_uint32), ("first_frame", C.c_uint32), ("n_frames", C.c_uint32),
-                ("prev_size", C.c_uint16 * 9), ("reserved", C.c_uint16 * 3)]
-
-
-class Walked(C.Structure):
-    _fields_ = [("regular", C.c_int32), ("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("dup_last_frame", C.c_int32), ("max_part2_3_length", C.c_int32), ("any_silent", C.c_int32), ("blob_len", C.c_size_t),
-                ("refs", C.c_void_p), ("stream", StreamRef), ("tables", C.c_void_p)]
-
-
-class Decoded(C.Structure):
-    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("n_bits", C.c_int32), ("n_rows", C.c_int64), ("pcm", C.c_void_p), ("bits", C.c_void_p)]
-
-
-class Encoded(C.Structure):
-    _fields_ = [("n_frames", C.c_int32), ("too_long", C.c_int32), ("hide_offset", C.c_int64), ("mp3", C.c_void_p),
-                ("mp3_len", C.c_size_t), ("gr", C.c_void_p), ("scfsi", C.c_void_p), ("rate_passes", C.c_int32)]
-
-
-class Carry(C.Structure):
-    """what crosses a block boundary in the encoder: message cursor + per (ch*2+gr) address1..3 / quantizerStepSize"""
-    _fields_ = [("cursor", C.c_int64), ("chain", (C.c_int32 * 4) * 4)]
-
-    def to_array(self):
-        return np.array([self.cursor] + [self.chain[k][j] for k in range(4) for j in range(4)], dtype=np.int64)
-
-    @classmethod
-    def from_array(cls, a):
-        c = cls()
-        c.cursor = int(a[0])
-        for k in range(4):
-            for j in range(4):
-                c.chain[k][j] = int(a[1 + 4 * k + j])
-        return c
-
-
-class WavInfo(C.Structure):
-    _fields_ = [("channels", C.c_int32), ("samplerate", C.c_int32), ("bits_per_sample", C.c_int32), ("bitrate", C.c_int32),
-                ("num_of_samples", C.c_int64), ("data_offset", C.c_int64), ("n_values", C.c_int64)]
-
-
-class WavImport(C.Structure):
-    _fields_ = [("format", C.c_int32), ("channels", C.c_int32), ("samplerate", C.c_int32), ("bits_per_sample", C.c_int32),
-                ("block_align", C.c_int32), ("bitrate", C.c_int32), ("data_offset", C.c_int64), ("n_samples", C.c_int64), ("n_frames", C.c_int64)]
-
-
-WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32 = 1, 2, 3, 4, 5
-
-
-class WavResample(C.Structure):
-    _fields_ = [("in_", WavImport), ("out_rate", C.c_int32), ("L", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("half", C.c_int32),
-                ("n_out", C.c_int64), ("n_frames", C.c_int64)]
-
-
-class File(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("len", C.c_size_t), ("kbps", C.c_int32), ("sampling_rate", C.c_int32),
-                ("channels", C.c_int32), ("n_frames", C.c_int32), ("too_long", C.c_int32), ("n_bits", C.c_int32),
-                ("hide_offset", C.c_int64), ("bits", C.c_void_p)]
-
-
-class Capacity(C.Structure):
-    """mp3s_capacity: what mp3s_capacity_files / mp3s_capacity_wavs answer per file"""
-    _fields_ = [("bits", C.c_int64), ("hide_offset", C.c_int64), ("text_bytes", C.c_int64), ("too_long", C.c_int32), ("n_frames", C.c_int32),
-                ("kbps", C.c_int32), ("sampling_rate", C.c_int32), ("channels", C.c_int32), ("active_units", C.c_int32),
-                ("fallback", C.c_int32), ("reserved", C.c_int32), ("profile", C.c_void_p)]
-
-
-CAPACITY_SEG_DTYPE = np.dtype([("bits", "<i8"), ("active_units", "<i4"), ("reserved", "<i4")])
-
-
-class TableAudit(C.Structure):
-    """mp3s_table_audit: what mp3s_table_audit_files answers per file and k_table_audit_streams writes per stream"""
-    _fields_ = [("regions", C.c_int64), ("natural", C.c_int64), ("forced", C.c_int64), ("forced_ones", C.c_int64), ("foreign", C.c_int64),
-                ("empty", C.c_int64), ("excess_bits", C.c_int64), ("first_forced", C.c_int64), ("last_forced", C.c_int64),
-                ("n_frames", C.c_int32), ("channels", C.c_int32), ("sampling_rate", C.c_int32), ("kbps", C.c_int32),
-                ("window_units", C.c_int32), ("reserved", C.c_int32), ("profile", C.c_void_p)]
-
-
-TABLE_AUDIT_DTYPE = np.dtype([("regions", "<i8"), ("natural", "<i8"), ("forced", "<i8"), ("forced_ones", "<i8"), ("foreign", "<i8"), ("empty", "<i8"),
-                              ("excess_bits", "<i8"), ("first_forced", "<i8"), ("last_forced", "<i8"), ("n_frames", "<i4"), ("channels", "<i4"),
-                              ("sampling_rate", "<i4"), ("kbps", "<i4"), ("window_units", "<i4"), ("reserved", "<i4"), ("profile", "<u8")])
-TABLE_AUDIT_UNIT_DTYPE = np.dtype([("cls", "u1", (3,)), ("forced_bits", "u1"), ("nat", "u1", (3,)), ("window", "u1"), ("excess", "<i2", (3,)),
-                                   ("reserved", "<u2")])
-TABLE_AUDIT_SEG_DTYPE = np.dtype([("first_frame", "<i4"), ("n_frames", "<i4")])
-assert TABLE_AUDIT_DTYPE.itemsize == 104 and TABLE_AUDIT_UNIT_DTYPE.itemsize == 16 and TABLE_AUDIT_SEG_DTYPE.itemsize == 8
-TA_NONE, TA_NATURAL, TA_FORCED, TA_FOREIGN, TA_EMPTY = 0, 1, 2, 3, 4     # MP3S_TA_*
-TABLE_AUDIT_FIELDS = ("regions", "natural", "forced", "forced_ones", "foreign", "empty", "excess_bits", "first_forced", "last_forced",
-                      "n_frames", "channels", "sampling_rate", "kbps", "window_units")
-
-
-class PcmDistortion(C.Structure):
-    """mp3s_pcm_distortion: what mp3s_pcm_distortion_files answers per pair"""
-    _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("n_samples", C.c_int64), ("n_diff", C.c_int64), ("first_diff", C.c_int64),
-                ("rows_a", C.c_int64), ("rows_b", C.c_int64), ("max_abs", C.c_uint32), ("channels", C.c_int32), ("sampling_rate", C.c_int32),
-                ("n_frames", C.c_int32), ("snr_db", C.c_double), ("psnr_db", C.c_double), ("profile", C.c_void_p)]
-
-
-class PcmPair(C.Structure):
-    _fields_ = [("a_first", C.c_uint32), ("b_first", C.c_uint32), ("n_frames", C.c_uint32), ("out_first", C.c_uint32)]
-
-
-class PcmFrameDiff(C.Structure):
-    _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("max_abs", C.c_uint32), ("n_diff", C.c_uint32), ("first_diff", C.c_uint32),
-                ("reserved", C.c_uint32)]
-
-
-class PcmPairDiff(C.Structure):
-    _fields_ = [("err2", C.c_uint64), ("sig2", C.c_uint64), ("n_diff", C.c_uint64), ("first_diff", C.c_int64), ("max_abs", C.c_uint32),
-                ("reserved", C.c_uint32)]
-
-
-PCM_PAIR_DTYPE = np.dtype([("a_first", "<u4"), ("b_first", "<u4"), ("n_frames", "<u4"), ("out_first", "<u4")])
-PCM_FRAME_DIFF_DTYPE = np.dtype([("err2", "<u8"), ("sig2", "<u8"), ("max_abs", "<u4"), ("n_diff", "<u4"), ("first_diff", "<u4"), ("reserved", "<u4")])
-PCM_PAIR_DIFF_DTYPE = np.dtype([("err2", "<u8"), ("sig2", "<u8"), ("n_diff", "<u8"), ("first_diff", "<i8"), ("max_abs", "<u4"), ("reserved", "<u4")])
-NO_DIFF = 0xFFFFFFFF         # mp3s_pcm_frame_diff.first_diff of a frame without a differing sample
-
-
-class PcmRunPair(C.Structure):
-    """mp3s_pcm_run_pair: rows of the PCM buffer"""
-    _fields_ = [("a_first", C.c_uint32), ("a_rows", C.c_uint32), ("b_first", C.c_uint32), ("b_rows", C.c_uint32), ("out_first", C.c_uint32),
-                ("reserved", C.c_uint32)]
-
-
-class PcmLag(C.Structure):
-    """mp3s_pcm_lag: the lag record of a pair"""
-    _fields_ = [("lag", C.c_int32), ("n_best", C.c_uint32), ("err2_best", C.c_uint64), ("err2_at_0", C.c_uint64), ("search_first", C.c_uint32),
-                ("search_rows", C.c_uint32), ("n_rows", C.c_uint32), ("n_chunks", C.c_uint32)]
-
-
-class PcmAlignment(C.Structure):
-    """mp3s_pcm_alignment: what mp3s_pcm_alignment_files answers per pair"""
-    _fields_ = [("at_lag", PcmDistortion), ("lag", PcmLag), ("scores", C.c_void_p)]
-
-
-PCM_RUN_PAIR_DTYPE = np.dtype([("a_first", "<u4"), ("a_rows", "<u4"), ("b_first", "<u4"), ("b_rows", "<u4"), ("out_first", "<u4"), ("reserved", "<u4")])
-PCM_LAG_DTYPE = np.dtype([("lag", "<i4"), ("n_best", "<u4"), ("err2_best", "<u8"), ("err2_at_0", "<u8"), ("search_first", "<u4"), ("search_rows", "<u4"),
-                          ("n_rows", "<u4"), ("n_chunks", "<u4")])
-PCM_MAX_LAG = 4608           # MP3S_PCM_MAX_LAG
-
-
-class PcmBatchItem(C.Structure):
-    _fields_ = [("src_row", C.c_int64), ("n_rows", C.c_int64), ("first_row", C.c_int64), ("slot", C.c_int32), ("reserved", C.c_int32)]
-
-
-class PcmUnbatchItem(C.Structure):
-    _fields_ = [("dst_frame", C.c_int64), ("n_rows", C.c_int64), ("slot", C.c_int32), ("reserved", C.c_int32)]
-
-
-class PcmBatchInfo(C.Structure):
-    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("n_rows", C.c_int64), ("first_row", C.c_int64), ("valid_rows", C.c_int64)]
-
-
-class PcmResampleRatio(C.Structure):
-    _fields_ = [("L", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("half", C.c_int32)]
-
-
-class PcmResampleItem(C.Structure):
-    _fields_ = [("src_row", C.c_int64), ("n_rows", C.c_int64), ("first_row", C.c_int64), ("slot", C.c_int32), ("L", C.c_int32), ("M", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-class PcmBatchInfoAt(C.Structure):
-    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("n_rows", C.c_int64), ("first_row", C.c_int64), ("valid_rows", C.c_int64), ("in_rows", C.c_int64),
-                ("out_rate", C.c_int32), ("L", C.c_int32), ("M", C.c_int32), ("reserved", C.c_int32)]
-
-
-PCM_RESAMPLE_ITEM_DTYPE = np.dtype([("src_row", "<i8"), ("n_rows", "<i8"), ("first_row", "<i8"), ("slot", "<i4"), ("L", "<i4"), ("M", "<i4"), ("reserved", "<i4")])
-PCM_BATCH_INFO_AT_DTYPE = np.dtype([("n_frames", "<i4"), ("nch", "<i4"), ("sampling_rate", "<i4"), ("bit_rate", "<i4"), ("n_rows", "<i8"), ("first_row", "<i8"),
-                                    ("valid_rows", "<i8"), ("in_rows", "<i8"), ("out_rate", "<i4"), ("L", "<i4"), ("M", "<i4"), ("reserved", "<i4")])
-PCM_BATCH_ITEM_DTYPE = np.dtype([("src_row", "<i8"), ("n_rows", "<i8"), ("first_row", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
-PCM_UNBATCH_ITEM_DTYPE = np.dtype([("dst_frame", "<i8"), ("n_rows", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
-PCM_BATCH_INFO_DTYPE = np.dtype([("n_frames", "<i4"), ("nch", "<i4"), ("sampling_rate", "<i4"), ("bit_rate", "<i4"),
-                                 ("n_rows", "<i8"), ("first_row", "<i8"), ("valid_rows", "<i8")])
-BATCH_I16, BATCH_F32 = 0, 1  # MP3S_BATCH_*: int16, float32 = int16 / 32768
-BATCH_FORMATS = {"i16": BATCH_I16, "f32": BATCH_F32, BATCH_I16: BATCH_I16, BATCH_F32: BATCH_F32}
-BATCH_DTYPES = {BATCH_I16: np.dtype(np.int16), BATCH_F32: np.dtype(np.float32)}
+def __getattr__(name):
+    if name == "_lib":       # the loaded library, cached by _abi.lib()
+        return _abi._lib
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _addr(p):
@@ -265,16 +37,6 @@ def _addr(p):
     if p is None:
         return None
     return C.c_void_p(p.value if isinstance(p, C.c_void_p) else int(p))
-
-
-class IndexInfo(C.Structure):
-    _fields_ = [("n_frames", C.c_int64), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
-                ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("reserved", C.c_int32)]
-
-
-SELECT_SPAN_DTYPE = np.dtype([("first_entry", "<i4"), ("reach", "<i4")])
-SELECT_VARIANTS = 10
-NO_CURSOR = 0x3fffffff
 
 
 def select_patterns():
@@ -297,183 +59,6 @@ def select_plan(segs, cap):
     return spans, unit[:n], cursor[:n]
 
 
-class PipeStats(C.Structure):
-    _fields_ = [("submitted", C.c_int64), ("collected", C.c_int64), ("fast", C.c_int64), ("slow", C.c_int64),
-                ("scan_ms", C.c_double), ("issue_ms", C.c_double), ("last_device_span_ms", C.c_double), ("scan_cpu_ms", C.c_double),
-                ("resolved", C.c_int64), ("rehearsal_ms", C.c_double), ("rehearsals", C.c_int64), ("lanes", C.c_int64), ("queue_shared", C.c_int64)]
-
-
-class Block(C.Structure):
-    _fields_ = [("total_frames", C.c_int64), ("first_frame", C.c_int64), ("n_frames", C.c_int64), ("is_last", C.c_int32),
-                ("carry_used", C.c_int32), ("carry_out", Carry), ("file", File)]
-
-
-# every symbol include/mp3s.h declares (tests/test_abi.py checks the library exports all of them)
-SYMBOLS = ["mp3s_ctx_create", "mp3s_ctx_destroy", "mp3s_ctx_wait", "mp3s_ctx_wait_last", "mp3s_last_error", "mp3s_version", "mp3s_device_name", "mp3s_sync", "mp3s_debug_tables", "mp3s_debug_scfsi_energies", "mp3s_debug_parse_scanned_frame",
-           "mp3s_dev_alloc", "mp3s_dev_free", "mp3s_dev_upload", "mp3s_dev_download", "mp3s_dev_memset",
-           "mp3s_timer_start", "mp3s_timer_stop", "mp3s_bench_copy", "mp3s_synth_mode", "mp3s_profile_enable", "mp3s_profile_select", "mp3s_profile_collect", "mp3s_decode_transform_dev", "mp3s_decode_transform",
-           "mp3s_encode_transform_dev", "mp3s_encode_transform", "mp3s_debug_guard_margin", "mp3s_rate_loop_dev", "mp3s_chain_resolve_dev", "mp3s_chain_redo_dev", "mp3s_select_patterns", "mp3s_select_plan", "mp3s_rate_select_dev", "mp3s_rate_variants_dev", "mp3s_select_dev", "mp3s_huffman_decode_dev", "mp3s_pack_frames_dev", "mp3s_scan_stream", "mp3s_buf_free",
-           "mp3s_parse_stream", "mp3s_format_stream", "mp3s_rate_frames", "mp3s_decode_stream", "mp3s_decode_streams", "mp3s_decode_block", "mp3s_encode_pcm", "mp3s_encode_block",
-           "mp3s_wav_parse", "mp3s_wav_header", "mp3s_message_frame", "mp3s_message_reveal", "mp3s_decode_file", "mp3s_encode_file",
-           "mp3s_hide_message", "mp3s_clear_file", "mp3s_hide_message_fd", "mp3s_clear_file_fd", "mp3s_decode_file_fd", "mp3s_hide_messages", "mp3s_reencode_block", "mp3s_reveal_message",
-           "mp3s_pipe_create", "mp3s_pipe_destroy", "mp3s_pipe_submit", "mp3s_pipe_submit_decode", "mp3s_pipe_collect", "mp3s_pipe_get_stats",
-           "mp3s_index_stream", "mp3s_index_free", "mp3s_scan_range", "mp3s_decode_block_indexed", "mp3s_reencode_block_indexed",
-           "mp3s_hide_message_chunked", "mp3s_walk_stream", "mp3s_parse_frames_dev", "mp3s_stego_bits", "mp3s_ctx_set_option", "mp3s_ctx_get_option", "mp3s_ctx_run_stats", "mp3s_ctx_host_share", "mp3s_dev_copy", "mp3s_pipe_submit_block", "mp3s_pipe_collect_block", "mp3s_encode_files", "mp3s_pipe_submit_encode", "mp3s_debug_wav_gather", "mp3s_pipe_next_is_block", "mp3s_debug_walk_rate", "mp3s_device_count", "mp3s_device_pci", "mp3s_wav_import_info", "mp3s_wav_resample_info", "mp3s_wav_resample_taps",
-           "mp3s_reveal_bits_dev", "mp3s_reveal_messages", "mp3s_debug_reveal_messages",
-           "mp3s_capacity_dev", "mp3s_capacity_files", "mp3s_capacity_wavs", "mp3s_capacity_text_bytes",
-           "mp3s_pcm_diff_dev", "mp3s_pcm_distortion_files", "mp3s_pcm_align_dev", "mp3s_pcm_alignment_files",
-           "mp3s_table_audit_dev", "mp3s_table_audit_files",
-           "mp3s_pcm_batch_dev", "mp3s_pcm_unbatch_dev", "mp3s_pcm_batch_decode_files", "mp3s_pcm_batch_encode",
-           "mp3s_pcm_resample_plan", "mp3s_pcm_batch_resample_dev", "mp3s_pcm_batch_decode_files_at", "mp3s_pcm_batch_encode_at"]
-
-REVEAL_TILE = 256            # MP3S_REVEAL_TILE: frames a workgroup of k_reveal takes at a time
-RV_BAD_REF = 1
-_EMPTY = C.c_char()          # where an empty file's pointer points (a null pointer is an argument error)
-
-_lib = None
-_lock = threading.Lock()
-
-
-def lib():
-    """Load libmp3s_hip.so (raises if it has not been built: no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is missing: build it with `make -C mp3-steganography-lib_amd` "
-                              "(or `python __graft_entry__.py`); the HIP extension has no CPU fallback")
-        L = C.CDLL(LIB_PATH)
-        vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
-        pvp = C.POINTER(C.c_void_p)
-        L.mp3s_last_error.restype = C.c_char_p
-        L.mp3s_version.restype = C.c_char_p
-        L.mp3s_ctx_create.argtypes = [i32, pvp]
-        L.mp3s_device_count.argtypes = [C.POINTER(C.c_int)]
-        L.mp3s_ctx_destroy.argtypes = [vp]
-        L.mp3s_ctx_destroy.restype = None
-        L.mp3s_device_name.argtypes = [vp, C.c_char_p, sz]
-        L.mp3s_device_pci.argtypes = [vp, C.c_char_p, sz]
-        L.mp3s_ctx_run_stats.argtypes = [vp, vp]
-        L.mp3s_ctx_set_option.argtypes = [vp, i32, i64]
-        L.mp3s_ctx_get_option.argtypes = [vp, i32, C.POINTER(C.c_int64)]
-        L.mp3s_sync.argtypes = [vp]
-        L.mp3s_ctx_wait.argtypes = [vp, vp]
-        L.mp3s_ctx_wait_last.argtypes = [vp, vp]
-        L.mp3s_debug_tables.argtypes = [C.POINTER(sz)]
-        L.mp3s_debug_tables.restype = vp
-        L.mp3s_debug_scfsi_energies.argtypes = [vp, i32, vp]
-        L.mp3s_dev_alloc.argtypes = [vp, sz, pvp]
-        L.mp3s_dev_free.argtypes = [vp, vp]
-        L.mp3s_dev_upload.argtypes = [vp, vp, vp, sz]
-        L.mp3s_dev_download.argtypes = [vp, vp, vp, sz]
-        L.mp3s_dev_memset.argtypes = [vp, vp, i32, sz]
-        L.mp3s_dev_copy.argtypes = [vp, vp, vp, sz]
-        L.mp3s_timer_start.argtypes = [vp]
-        L.mp3s_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
-        L.mp3s_bench_copy.argtypes = [vp, sz, i32, C.POINTER(C.c_double)]
-        L.mp3s_synth_mode.argtypes = [vp, C.c_double, C.POINTER(C.c_int64)]
-        L.mp3s_profile_enable.argtypes = [vp, i32]
-        L.mp3s_profile_select.argtypes = [vp, C.c_uint]
-        L.mp3s_profile_collect.argtypes = [vp, vp, vp, i32]
-        L.mp3s_decode_transform_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        L.mp3s_decode_transform.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-        L.mp3s_encode_transform_dev.argtypes = [vp, vp, vp, i32, vp]
-        L.mp3s_encode_transform.argtypes = [vp, vp, vp, i32, vp]
-        L.mp3s_rate_loop_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp]
-        L.mp3s_chain_resolve_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
-        L.mp3s_chain_redo_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
-        L.mp3s_select_patterns.argtypes = [vp]
-        L.mp3s_select_patterns.restype = None
-        L.mp3s_select_plan.argtypes = [vp, i32, vp, vp, vp, i32]
-        L.mp3s_rate_select_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-        L.mp3s_rate_variants_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-        L.mp3s_select_dev.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
-        L.mp3s_huffman_decode_dev.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
-        L.mp3s_pack_frames_dev.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
-        L.mp3s_scan_stream.argtypes = [vp, sz, pvp, C.POINTER(Scanned)]
-        L.mp3s_buf_free.argtypes = [vp]
-        L.mp3s_buf_free.restype = None
-        L.mp3s_parse_stream.argtypes = [vp, sz, pvp, C.POINTER(Parsed)]
-        L.mp3s_format_stream.argtypes = [i32, i32, i32, vp, vp, vp, pvp, pvp, C.POINTER(sz)]
-        L.mp3s_debug_parse_scanned_frame.argtypes = [vp, vp, vp, vp]
-        L.mp3s_rate_frames.argtypes = [i32, i32, i32, i32, vp, vp]
-        L.mp3s_decode_stream.argtypes = [vp, vp, sz, i32, pvp, C.POINTER(Decoded)]
-        L.mp3s_decode_streams.argtypes = [vp, pvp, C.POINTER(sz), i32, i32, pvp, C.POINTER(Decoded), vp]
-        L.mp3s_encode_pcm.argtypes = [vp, vp, i64, i32, i32, i32, vp, i32, pvp, C.POINTER(Encoded)]
-        psz = C.POINTER(sz)
-        L.mp3s_wav_parse.argtypes = [vp, sz, i32, C.POINTER(WavInfo)]
-        L.mp3s_wav_import_info.argtypes = [vp, sz, i32, C.POINTER(WavImport)]
-        L.mp3s_wav_resample_info.argtypes = [vp, sz, i32, i32, C.POINTER(WavResample)]
-        L.mp3s_wav_resample_taps.argtypes = [i32, i32, vp, i32, C.POINTER(i32)]
-        L.mp3s_wav_header.argtypes = [i64, i32, i32, vp]
-        L.mp3s_message_frame.argtypes = [vp, sz, pvp, pvp, psz]
-        L.mp3s_message_reveal.argtypes = [vp, sz, pvp, pvp, psz]
-        L.mp3s_decode_file.argtypes = [vp, vp, sz, pvp, C.POINTER(File)]
-        L.mp3s_encode_file.argtypes = [vp, vp, sz, i32, vp, i32, pvp, C.POINTER(File)]
-        L.mp3s_hide_message.argtypes = [vp, vp, sz, vp, sz, pvp, C.POINTER(File)]
-        L.mp3s_clear_file.argtypes = [vp, vp, sz, pvp, C.POINTER(File)]
-        L.mp3s_decode_file_fd.argtypes = [vp, vp, sz, C.c_int, pvp, C.POINTER(File)]
-        L.mp3s_hide_message_fd.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.POINTER(File)]
-        L.mp3s_clear_file_fd.argtypes = [vp, vp, sz, C.c_int, C.POINTER(File)]
-        L.mp3s_decode_block.argtypes = [vp, vp, sz, C.c_int64, C.c_int64, i32, pvp, C.POINTER(Decoded)]
-        L.mp3s_encode_block.argtypes = [vp, vp, C.c_int64, i32, C.c_int64, i32, i32, i32, vp, i32, C.POINTER(Carry), C.POINTER(Carry),
-                                        C.POINTER(C.c_int32), pvp, C.POINTER(Encoded)]
-        L.mp3s_reencode_block.argtypes = [vp, vp, sz, vp, sz, i32, i32, C.POINTER(Carry), pvp, C.POINTER(Block)]
-        L.mp3s_hide_messages.argtypes = [vp, vp, vp, i32, vp, vp, pvp, vp, vp]
-        L.mp3s_reveal_message.argtypes = [vp, sz, pvp, C.POINTER(File)]
-        L.mp3s_index_stream.argtypes = [vp, sz, pvp, C.POINTER(IndexInfo)]
-        L.mp3s_index_free.argtypes = [vp]
-        L.mp3s_index_free.restype = None
-        L.mp3s_scan_range.argtypes = [vp, sz, vp, C.c_int64, C.c_int64, pvp, C.POINTER(Scanned)]
-        L.mp3s_decode_block_indexed.argtypes = [vp, vp, sz, vp, C.c_int64, C.c_int64, i32, pvp, C.POINTER(Decoded)]
-        L.mp3s_reencode_block_indexed.argtypes = [vp, vp, sz, vp, vp, sz, i32, i32, C.POINTER(Carry), pvp, C.POINTER(Block)]
-        L.mp3s_hide_message_chunked.argtypes = [vp, vp, sz, vp, sz, C.c_int64, pvp, C.POINTER(File)]
-        L.mp3s_walk_stream.argtypes = [vp, sz, pvp, C.POINTER(Walked)]
-        L.mp3s_parse_frames_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, i32, C.c_uint32, vp, vp, vp, vp, vp]
-        L.mp3s_stego_bits.argtypes = [vp, i64, i32, vp, pvp, pvp, psz]
-        L.mp3s_reveal_bits_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, i32, vp, vp, vp, vp]
-        L.mp3s_reveal_messages.argtypes = [vp, vp, vp, i32, pvp, vp, vp]
-        L.mp3s_debug_reveal_messages.argtypes = [vp, vp, vp, i32, i32, pvp, vp, vp]
-        L.mp3s_capacity_dev.argtypes = [vp, vp, vp, i32, vp, vp]
-        L.mp3s_capacity_files.argtypes = [vp, vp, vp, i32, vp, vp, i32, pvp, vp, vp]
-        L.mp3s_capacity_wavs.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, pvp, vp, vp]
-        L.mp3s_capacity_text_bytes.argtypes = [i64]
-        L.mp3s_capacity_text_bytes.restype = i64
-        L.mp3s_table_audit_dev.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]
-        L.mp3s_table_audit_files.argtypes = [vp, vp, vp, i32, i32, pvp, vp, vp]
-        L.mp3s_pcm_diff_dev.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp]
-        L.mp3s_pcm_distortion_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, pvp, vp, vp]
-        L.mp3s_pcm_align_dev.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
-        L.mp3s_pcm_alignment_files.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, pvp, vp, vp]
-        L.mp3s_pcm_batch_dev.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i64, vp]
-        L.mp3s_pcm_unbatch_dev.argtypes = [vp, vp, i32, i32, i64, vp, vp, i32, vp]
-        L.mp3s_pcm_batch_decode_files.argtypes = [vp, vp, vp, i32, vp, i64, i32, i32, vp, sz, vp, vp]
-        L.mp3s_pcm_batch_encode.argtypes = [vp, vp, i32, i32, i32, i64, vp, i32, i32, vp, vp, pvp, vp, vp]
-        L.mp3s_pcm_resample_plan.argtypes = [i32, i32, vp]
-        L.mp3s_pcm_batch_resample_dev.argtypes = [vp, vp, i32, vp, i32, i32, i32, i64, vp]
-        L.mp3s_pcm_batch_decode_files_at.argtypes = [vp, vp, vp, i32, i32, vp, i64, i32, i32, vp, sz, vp, vp]
-        L.mp3s_pcm_batch_encode_at.argtypes = [vp, vp, i32, i32, i32, i64, vp, i32, i32, i32, vp, vp, pvp, vp, vp]
-        L.mp3s_pipe_create.argtypes = [vp, i32, sz, i32, pvp]
-        L.mp3s_pipe_destroy.argtypes = [vp]
-        L.mp3s_pipe_destroy.restype = None
-        L.mp3s_pipe_submit.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(C.c_int64)]
-        L.mp3s_encode_files.argtypes = [vp, vp, vp, i32, vp, vp, vp, pvp, vp, vp]
-        L.mp3s_debug_wav_gather.argtypes = [vp, vp, vp, i32, vp, C.c_int64, C.POINTER(C.c_int64)]
-        L.mp3s_pipe_submit_encode.argtypes = [vp, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_int64)]
-        L.mp3s_pipe_submit_decode.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_int64)]
-        L.mp3s_pipe_collect.argtypes = [vp, C.POINTER(C.c_int64), pvp, vp, vp, i32, C.POINTER(C.c_int32)]
-        L.mp3s_pipe_get_stats.argtypes = [vp, C.POINTER(PipeStats)]
-        L.mp3s_pipe_submit_block.argtypes = [vp, vp, sz, vp, sz, i32, i32, C.POINTER(Carry), C.POINTER(C.c_int64)]
-        L.mp3s_pipe_collect_block.argtypes = [vp, C.POINTER(C.c_int64), pvp, C.POINTER(Block)]
-        L.mp3s_pipe_next_is_block.argtypes = [vp]
-        L.mp3s_debug_walk_rate.argtypes = [vp, sz, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        _lib = L
-    return _lib
-
-
 def device_count():
     """HIP devices this process can open (mp3s_device_count); touches the HIP runtime"""
     n = C.c_int()
@@ -481,26 +66,125 @@ def device_count():
     return n.value
 
 
-def check(rc):
-    if rc != 0:
-        raise Mp3sError(rc, lib().mp3s_last_error().decode("utf-8", "replace"))
+# ---- arguments: every helper returns what has to stay alive beside the pointers it hands out
+def _file_list(files, none_is_null=False):
+    """a list of byte strings as the arrays of a list-of-files call -> (n, what has to stay alive beside them, pointers, lengths).
+    An empty file points at _EMPTY: a null pointer is an argument error, whatever numpy calls the address of an empty array.
+    none_is_null: a file that is None travels as a null pointer of length 0, which its entry of the answer speaks for"""
+    n = len(files)
+    bufs = [None if none_is_null and f is None else np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[None if b is None else b.ctypes.data if len(b) else C.addressof(_EMPTY) for b in bufs])
+    lens = (C.c_size_t * n)(*[0 if b is None else len(b) for b in bufs])
+    return n, (files, bufs), ptrs, lens
 
 
-def _view(ptr, dtype, shape):
+def _pair_lists(mp3s_a, mp3s_b, none_is_null=False):
+    """two lists of byte strings as the arrays of a pair-list call -> (n, what has to stay alive beside them, a's pointers and lengths,
+    b's).  none_is_null: as for _file_list"""
+    n, keep_a, pa, la = _file_list(mp3s_a, none_is_null)
+    _, keep_b, pb, lb = _file_list(mp3s_b, none_is_null)
+    return n, (keep_a, keep_b), pa, la, pb, lb
+
+
+def _message(message, empty_is_null=False):
+    """one message as (the buffer to keep alive, pointer, length in bytes).  The library tells two spellings apart and both are in use:
+    the list, block and chunked calls take None (clear: a null pointer) or a str, "" being a one-byte buffer of length 0;
+    empty_is_null (hide_message, recode_to_fd, message_frame): a str only, "" being a null pointer of length 0"""
+    if message is None and not empty_is_null:
+        return None, None, 0
+    m = message.encode("utf-8")
+    if empty_is_null and not m:
+        return None, None, 0
+    mb = np.frombuffer(m or b"\0", dtype=np.uint8)
+    return mb, mb.ctypes.data, len(m)
+
+
+def _message_list(messages):
+    """one message (or None) per file as the arrays of a list call -> (the buffers to keep alive, pointers, lengths), each message as
+    _message spells it; messages=None (nothing anywhere) -> three None"""
+    if messages is None:
+        return None, None, None
+    n = len(messages)
+    bufs, ptrs, lens = zip(*[_message(t) for t in messages]) if n else ((), (), ())
+    return bufs, (C.c_void_p * n)(*ptrs), (C.c_size_t * n)(*lens)
+
+
+def _hide_bits(hide_bits):
+    """one 0/1 array (None or empty: nothing is hidden) as (the array to keep alive, pointer, length)"""
+    if hide_bits is None or not len(hide_bits):
+        return None, None, 0
+    hb = np.ascontiguousarray(hide_bits, dtype=np.uint8)
+    return hb, hb.ctypes.data, len(hb)
+
+
+def _hide_bits_list(hide_bits, messages, n, what="file"):
+    """hide_bits (one 0/1 array or None per file) or messages (one str or None per file, framed with message_frame) as the arrays of a
+    list call -> (the arrays to keep alive, pointers, int32 lengths); three None with neither"""
+    if hide_bits is not None and messages is not None:
+        raise ValueError("hide_bits or messages, not both")
+    if messages is not None:
+        hide_bits = [None if m is None else np.array(message_frame(m), dtype=np.uint8) for m in messages]
+    if hide_bits is None:
+        return None, None, None
+    if len(hide_bits) != n:
+        raise ValueError(f"one bit string (or None) per {what}")
+    hbs, ptrs, lens = zip(*[_hide_bits(h) for h in hide_bits]) if n else ((), (), ())
+    return hbs, (C.c_void_p * n)(*ptrs), (C.c_int32 * n)(*lens)
+
+
+def _encode_args(wavs, bitrate, hide_bits, messages):
+    """the argument arrays of mp3s_encode_files / mp3s_pipe_submit_encode (+ everything that has to stay alive beside them)"""
+    n = len(wavs)
+    rates = [int(bitrate)] * n if np.isscalar(bitrate) else [int(b) for b in bitrate]
+    if len(rates) != n:
+        raise ValueError("one bitrate per file")
+    hbs, hptr, hlen = _hide_bits_list(hide_bits, messages, n)
+    _, keep, files, lens = _file_list(wavs)
+    return n, files, lens, (C.c_int32 * n)(*rates), hptr, hlen, (keep, hbs)
+
+
+# ---- results: one builder per shape
+class _Owner:
+    """keeps an mp3s_buf alive for the numpy arrays that look into it (no copy of large results); as a `with` block, for results that
+    are copies: the buffer is freed when the block ends"""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def free(self):
+        if self.handle:
+            lib().mp3s_buf_free(self.handle)
+            self.handle = None
+    __del__ = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def _view_owned(ptr, dtype, shape, owner):
     n = int(np.prod(shape)) * np.dtype(dtype).itemsize
     if n == 0 or not ptr:
         return np.zeros(shape, dtype=dtype)
-    return np.frombuffer((C.c_char * n).from_address(ptr), dtype=dtype).reshape(shape).copy()
+    buf = (C.c_char * n).from_address(ptr)
+    buf._mp3s_owner = owner                    # the array's base is `buf`; `buf` keeps the owner
+    return np.frombuffer(buf, dtype=dtype).reshape(shape)
 
 
-def _file_list(files):
-    """a list of byte strings as the arrays of a list-of-files call -> (n, what has to stay alive beside them, pointers, lengths).
-    An empty file points at _EMPTY: a null pointer is an argument error, whatever numpy calls the address of an empty array."""
-    n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data if len(b) else C.addressof(_EMPTY) for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in bufs])
-    return n, (files, bufs), ptrs, lens
+def _view(ptr, dtype, shape):
+    return _view_owned(ptr, dtype, shape, None).copy()
+
+
+def _owned_bytes(ptr, n, own):
+    """read-only bytes-like view (compare, hash, write, len, slice) of n bytes of a library buffer that `own` keeps
+    alive: a 40 MB file is handed over, not copied"""
+    if not n:
+        return b""
+    raw = (C.c_char * n).from_address(ptr)
+    raw._mp3s_owner = own
+    return memoryview(raw).cast("B").toreadonly()
 
 
 def _per_file(out, status, make, n=None, what="file"):
@@ -508,17 +192,37 @@ def _per_file(out, status, make, n=None, what="file"):
     return [Mp3sError(status[i], f"{what} {i}") if status[i] else make(out[i]) for i in range(len(status) if n is None else n)]
 
 
-def _pair_lists(mp3s_a, mp3s_b, none_is_null=False):
-    """two lists of byte strings as the arrays of a pair-list call -> (n, what has to stay alive beside them, a's pointers and lengths,
-    b's).  none_is_null: a file that is None travels as a null pointer, which the pair answers for"""
-    r = []
-    for files in (mp3s_a, mp3s_b):
-        n, keep, ptrs, lens = _file_list([b"" if none_is_null and f is None else f for f in files])
-        for i, f in enumerate(files):
-            if none_is_null and f is None:
-                ptrs[i] = None
-        r += [keep, ptrs, lens]
-    return n, (r[0], r[3]), r[1], r[2], r[4], r[5]
+def _file_dict(f, own, data="view", bits="view", hide=True):
+    """the dict of an mp3s_file.  data: "view" = a read-only view of the library's buffer that holds `own`, "copy" = bytes, "len" = no
+    "data" but its length as "len" (the calls that write to a file descriptor); bits: "view" (holds `own`), "copy", or None = no "bits";
+    hide=False: a call that hides nothing, "too_long" / "hide_offset" are False / 0 whatever the record holds"""
+    n = f.len
+    d = {"len" if data == "len" else "data": n if data == "len" else _owned_bytes(f.data, n, own) if data == "view" else C.string_at(f.data, n) if n else b"",
+         "kbps": f.kbps, "sampling_rate": f.sampling_rate, "channels": f.channels, "n_frames": f.n_frames,
+         "too_long": bool(f.too_long) if hide else False, "hide_offset": f.hide_offset if hide else 0}
+    if bits is not None:
+        d["bits"] = _view_owned(f.bits, np.uint8, (f.n_bits,), own) if bits == "view" else _view(f.bits, np.uint8, (f.n_bits,))
+    return d
+
+
+def _block_dict(b, own=None):
+    """the dict of an mp3s_block; "mp3" is a copy, or with `own` a read-only view of the library's buffer that holds it"""
+    f = b.file
+    return {"total_frames": b.total_frames, "first_frame": b.first_frame, "n_frames": b.n_frames, "is_last": bool(b.is_last),
+            "carry_used": bool(b.carry_used), "carry_out": b.carry_out.to_array(),
+            "mp3": _owned_bytes(f.data, f.len, own) if own is not None else C.string_at(f.data, f.len) if f.len else b"",
+            "kbps": f.kbps, "sampling_rate": f.sampling_rate, "too_long": bool(f.too_long), "hide_offset": f.hide_offset}
+
+
+def _decoded_dict(d, out_format, own):
+    """the dict of an mp3s_decoded: "pcm" looks into the library's buffer (no 46 MB copy per 10k frames) and holds `own`, "bits" is a copy"""
+    return {"n_frames": d.n_frames, "channels": d.nch, "sampling_rate": d.sampling_rate, "bit_rate": d.bit_rate,
+            "pcm": _view_owned(d.pcm, _PCM_DTYPES[out_format], (d.n_rows, d.nch), own), "bits": _view(d.bits, np.uint8, (d.n_bits,))}
+
+
+def _batch_info_dict(x):
+    """the dict of an mp3s_pcm_batch_info; an mp3s_pcm_batch_info_at adds what the resampler did"""
+    return {"channels" if k == "nch" else k: getattr(x, k) for k, _ in x._fields_ if k != "reserved"}
 
 
 def _with_hide_fields(out, took, diff, hidden):
@@ -530,25 +234,38 @@ def _with_hide_fields(out, took, diff, hidden):
     return out
 
 
-class _Owner:
-    """keeps an mp3s_buf alive for the numpy arrays that look into it (no copy of large results)"""
-
-    def __init__(self, handle):
-        self.handle = handle
-
-    def __del__(self):
-        if self.handle:
-            lib().mp3s_buf_free(self.handle)
-            self.handle = None
+def _close_quietly(self):
+    """the __del__ of everything here that has a close()"""
+    try:
+        self.close()
+    except Exception:
+        pass
 
 
-def _view_owned(ptr, dtype, shape, owner):
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    if n == 0 or not ptr:
-        return np.zeros(shape, dtype=dtype)
-    buf = (C.c_char * n).from_address(ptr)
-    buf._mp3s_owner = owner                    # the array's base is `buf`; `buf` keeps the owner
-    return np.frombuffer(buf, dtype=dtype).reshape(shape)
+class _DeviceScope:
+    """device buffers for the length of a `with` block (Context.device_scope): what alloc / to_device make through it is freed when the
+    block ends, whatever raised and wherever -- a later allocation that fails included"""
+
+    def __init__(self, ctx):
+        self.ctx, self.made = ctx, []
+
+    def alloc(self, nbytes):
+        self.made.append(self.ctx.alloc(nbytes))
+        return self.made[-1]
+
+    def to_device(self, arr):
+        arr = np.ascontiguousarray(arr)
+        p = self.alloc(arr.nbytes)
+        self.ctx.upload(p, arr)
+        return p
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        while self.made:
+            self.ctx.free(self.made.pop())
+        return False
 
 
 class Context:
@@ -595,11 +312,7 @@ class Context:
         check(lib().mp3s_ctx_get_option(self.handle, self.OPTIONS[name], C.byref(v)))
         return v.value
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _close_quietly
 
     def device_name(self):
         buf = C.create_string_buffer(256)
@@ -639,42 +352,39 @@ class Context:
         self.upload(p, arr)
         return p
 
+    def device_scope(self):
+        """`with ctx.device_scope() as dev:` -- dev.alloc / dev.to_device as above, everything made through dev freed when the block ends"""
+        return _DeviceScope(self)
+
     def parse_frames(self, data: bytes, walked, want_tsel=True):
         """side info + main-data gather of a walked stream on the device: -> dict(side, hdr, blob, tsel, status)"""
         n = walked["n_frames"]
-        d_img = self.to_device(np.frombuffer(data, dtype=np.uint8))
-        d_refs, d_streams = self.to_device(walked["refs"]), self.to_device(walked["stream"])
-        d_side, d_hdr, d_blob = self.alloc(n * 104), self.alloc(n * 8), self.alloc(walked["blob_len"] + 16)
-        d_tsel = self.alloc(n * 8) if want_tsel else None
-        d_st = self.to_device(np.zeros(4, dtype=np.int32))
-        try:
+        with self.device_scope() as dev:
+            d_img = dev.to_device(np.frombuffer(data, dtype=np.uint8))
+            d_refs, d_streams = dev.to_device(walked["refs"]), dev.to_device(walked["stream"])
+            d_side, d_hdr, d_blob = dev.alloc(n * 104), dev.alloc(n * 8), dev.alloc(walked["blob_len"] + 16)
+            d_tsel = dev.alloc(n * 8) if want_tsel else None
+            d_st = dev.to_device(np.zeros(4, dtype=np.int32))
             check(lib().mp3s_parse_frames_dev(self.handle, d_img, 0, d_refs, d_streams, n, 0, d_side, d_hdr, d_blob, d_tsel, d_st))
             return {"side": self.download(d_side, FRAME_SIDE_DTYPE, (n,)), "hdr": self.download(d_hdr, FRAME_HDR_DTYPE, (n,)),
                     "blob": self.download(d_blob, np.uint8, (walked["blob_len"],)),
                     "tsel": self.download(d_tsel, np.uint64, (n,)) if want_tsel else None,
                     "status": int(self.download(d_st, np.int32, (4,))[0])}
-        finally:
-            for p in (d_img, d_refs, d_streams, d_side, d_hdr, d_blob, d_tsel, d_st):
-                if p is not None:
-                    self.free(p)
 
     def reveal_bits(self, data: bytes, walked):
         """the stego bits of a walked stream on the device (mp3s_reveal_bits_dev, one stream): -> (packed uint8 array: eight bits
         to a byte, MSB first, the last byte zero-padded; n_bits)"""
         n = walked["n_frames"]
         room = (12 * n + 31) // 32 * 4
-        d_img = self.to_device(np.frombuffer(data, dtype=np.uint8))
-        d_refs, d_streams = self.to_device(walked["refs"]), self.to_device(walked["stream"])
-        d_off, d_packed, d_out = self.to_device(np.zeros(1, dtype=np.uint32)), self.alloc(room), self.alloc(8)
-        try:
+        with self.device_scope() as dev:
+            d_img = dev.to_device(np.frombuffer(data, dtype=np.uint8))
+            d_refs, d_streams = dev.to_device(walked["refs"]), dev.to_device(walked["stream"])
+            d_off, d_packed, d_out = dev.to_device(np.zeros(1, dtype=np.uint32)), dev.alloc(room), dev.alloc(8)
             check(lib().mp3s_reveal_bits_dev(self.handle, d_img, 0, d_refs, d_streams, 1, d_off, d_packed, d_out, C.c_void_p(d_out.value + 4)))
             n_bits, status = (int(v) for v in self.download(d_out, np.int32, (2,)))
             if status:
                 raise Mp3sError(E_MALFORMED, f"k_reveal refused the stream's frame references (status {status})")
             return self.download(d_packed, np.uint8, (room,))[:(n_bits + 7) // 8].copy(), n_bits
-        finally:
-            for p in (d_img, d_refs, d_streams, d_off, d_packed, d_out):
-                self.free(p)
 
     def wait_for(self, other):
         """work submitted to this context from now on starts after everything submitted to `other` so far"""
@@ -707,7 +417,6 @@ class Context:
 
         class _Probe:
             def __enter__(self):
-                lib().mp3s_debug_guard_margin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
                 self.n = int(n_samples)
                 self.d_x, self.d_eps = ctx.alloc(self.n * 8), ctx.alloc(self.n * 8)
                 check(lib().mp3s_dev_memset(ctx.handle, self.d_x, 0, self.n * 8))
@@ -757,8 +466,7 @@ class Context:
         si = np.ascontiguousarray(si, dtype=GRANULE_SI_DTYPE)
         hdr = np.ascontiguousarray(hdr, dtype=FRAME_HDR_DTYPE)
         n = is_.shape[0]
-        dt = {MP3S_PCM_I16: np.int16, MP3S_PCM_F32: np.float32, MP3S_PCM_F64: np.float64}[out_format]
-        pcm = np.empty(((n - n_halo) * 1152, nch), dtype=dt)
+        pcm = np.empty(((n - n_halo) * 1152, nch), dtype=_PCM_DTYPES[out_format])
         check(lib().mp3s_decode_transform(self.handle, is_.ctypes.data, si.ctypes.data, hdr.ctypes.data, n, nch, n_halo,
                                           out_format, pcm.ctypes.data))
         return pcm
@@ -777,27 +485,19 @@ class Context:
     # ---- whole-stream pipelines
     def decode_stream(self, data: bytes, out_format=MP3S_PCM_I16):
         buf = np.frombuffer(data, dtype=np.uint8)
-        owner = C.c_void_p()
-        d = Decoded()
+        owner, d = C.c_void_p(), Decoded()
         check(lib().mp3s_decode_stream(self.handle, buf.ctypes.data, len(data), out_format, C.byref(owner), C.byref(d)))
-        own = _Owner(owner)                    # the PCM array looks into the library's buffer: no 46 MB copy per 10k frames
-        dt = {MP3S_PCM_I16: np.int16, MP3S_PCM_F32: np.float32, MP3S_PCM_F64: np.float64}[out_format]
-        return {"n_frames": d.n_frames, "channels": d.nch, "sampling_rate": d.sampling_rate, "bit_rate": d.bit_rate,
-                "pcm": _view_owned(d.pcm, dt, (d.n_rows, d.nch), own), "bits": _view(d.bits, np.uint8, (d.n_bits,))}
+        return _decoded_dict(d, out_format, _Owner(owner))
 
     def decode_block(self, data: bytes, first_frame, n_frames, out_format=MP3S_PCM_I16, index=None):
         """frames [first_frame, first_frame + n_frames) of the stream (clipped to its end): one shard of a stream that is
         spread over several GPUs.  "bits", "bit_rate", "sampling_rate" describe the whole stream.  With an `index`
         (StreamIndex) only the block is scanned, and "bits" are those of the block's frames."""
         buf = np.frombuffer(data, dtype=np.uint8)
-        owner = C.c_void_p()
-        d = Decoded()
+        owner, d = C.c_void_p(), Decoded()
         check(lib().mp3s_decode_block_indexed(self.handle, buf.ctypes.data, len(data), index.handle if index is not None else None,
                                               int(first_frame), int(n_frames), out_format, C.byref(owner), C.byref(d)))
-        own = _Owner(owner)
-        dt = {MP3S_PCM_I16: np.int16, MP3S_PCM_F32: np.float32, MP3S_PCM_F64: np.float64}[out_format]
-        return {"n_frames": d.n_frames, "channels": d.nch, "sampling_rate": d.sampling_rate, "bit_rate": d.bit_rate,
-                "pcm": _view_owned(d.pcm, dt, (d.n_rows, d.nch), own), "bits": _view(d.bits, np.uint8, (d.n_bits,))}
+        return _decoded_dict(d, out_format, _Owner(owner))
 
     def decode_streams(self, files, out_format=MP3S_PCM_I16, per_file=False):
         """Decode many MP3 files as one device batch (one Huffman + one transform launch per channel count).
@@ -806,35 +506,24 @@ class Context:
         if len(files) == 0:
             return []
         n, _keep, ptrs, lens = _file_list(files)
-        owner = C.c_void_p()
-        d = (Decoded * n)()
+        owner, d = C.c_void_p(), (Decoded * n)()
         status = (C.c_int32 * n)()                 # (stays zero without per_file: a failing file fails the call)
         check(lib().mp3s_decode_streams(self.handle, ptrs, lens, n, out_format, C.byref(owner), d, status if per_file else None))
         own = _Owner(owner)
-        dt = {MP3S_PCM_I16: np.int16, MP3S_PCM_F32: np.float32, MP3S_PCM_F64: np.float64}[out_format]
-        return _per_file(d, status, lambda x: {
-            "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate,
-            "pcm": _view_owned(x.pcm, dt, (x.n_rows, x.nch), own), "bits": _view(x.bits, np.uint8, (x.n_bits,))})
+        return _per_file(d, status, lambda x: _decoded_dict(x, out_format, own))
 
     def encode_pcm(self, pcm_i16, samplerate, bitrate, hide_bits=None):
         pcm_i16 = np.ascontiguousarray(pcm_i16, dtype=np.int16)
         nch = 1 if pcm_i16.ndim == 1 else pcm_i16.shape[1]
-        hb, nh = None, 0
-        if hide_bits is not None and len(hide_bits):
-            hb = np.ascontiguousarray(hide_bits, dtype=np.uint8)
-            nh = len(hb)
-        owner = C.c_void_p()
-        e = Encoded()
+        _hb, hptr, nh = _hide_bits(hide_bits)
+        owner, e = C.c_void_p(), Encoded()
         check(lib().mp3s_encode_pcm(self.handle, pcm_i16.ctypes.data, pcm_i16.shape[0], nch, samplerate, bitrate,
-                                    hb.ctypes.data if hb is not None else None, nh, C.byref(owner), C.byref(e)))
-        try:
+                                    hptr, nh, C.byref(owner), C.byref(e)))
+        with _Owner(owner):
             return {"n_frames": e.n_frames, "too_long": bool(e.too_long), "hide_offset": e.hide_offset,
                     "mp3": _view(e.mp3, np.uint8, (e.mp3_len,)).tobytes(),
                     "gr": _view(e.gr, GR_OUT_DTYPE, (e.n_frames * 4,)),
                     "scfsi": _view(e.scfsi, np.int32, (e.n_frames, 2, 4)), "rate_passes": e.rate_passes}
-        finally:
-            lib().mp3s_buf_free(owner)
-
 
     def encode_block(self, pcm_i16, lead_frames, first_frame, last_block, samplerate, bitrate, hide_bits=None, carry_in=None):
         """one contiguous block of a longer stream (include/mp3s.h mp3s_encode_block).  pcm_i16 holds lead_frames frames
@@ -842,39 +531,23 @@ class Context:
         pcm_i16 = np.ascontiguousarray(pcm_i16, dtype=np.int16)
         if pcm_i16.ndim != 2 or pcm_i16.shape[1] != 2:
             raise Mp3sError(E_UNSUPPORTED, "stereo PCM [rows][2] expected")
-        hb, nh = None, 0
-        if hide_bits is not None and len(hide_bits):
-            hb = np.ascontiguousarray(hide_bits, dtype=np.uint8)
-            nh = len(hb)
+        _hb, hptr, nh = _hide_bits(hide_bits)
         cin = Carry.from_array(carry_in) if carry_in is not None else None
         cout, used, owner, e = Carry(), C.c_int32(0), C.c_void_p(), Encoded()
         check(lib().mp3s_encode_block(self.handle, pcm_i16.ctypes.data, pcm_i16.shape[0], int(lead_frames), int(first_frame),
-                                      1 if last_block else 0, int(samplerate), int(bitrate), hb.ctypes.data if hb is not None else None, nh,
+                                      1 if last_block else 0, int(samplerate), int(bitrate), hptr, nh,
                                       C.byref(cin) if cin is not None else None, C.byref(cout), C.byref(used), C.byref(owner), C.byref(e)))
-        try:
+        with _Owner(owner):
             return {"n_frames": e.n_frames, "too_long": bool(e.too_long), "hide_offset": e.hide_offset,
                     "mp3": _view(e.mp3, np.uint8, (e.mp3_len,)).tobytes(), "gr": _view(e.gr, GR_OUT_DTYPE, (e.n_frames * 4,)),
                     "carry_out": cout.to_array(), "carry_used": bool(used.value), "rate_passes": e.rate_passes}
-        finally:
-            lib().mp3s_buf_free(owner)
 
     # ---- whole files as byte strings (include/mp3s.h section vi)
-    @staticmethod
-    def _owned_bytes(ptr, n, own):
-        """read-only bytes-like view (compare, hash, write, len, slice) of n bytes of a library buffer that `own` keeps
-        alive: a 40 MB file is handed over, not copied"""
-        if not n:
-            return b""
-        raw = (C.c_char * n).from_address(ptr)
-        raw._mp3s_owner = own
-        return memoryview(raw).cast("B").toreadonly()
+    _owned_bytes = staticmethod(_owned_bytes)
 
     @staticmethod
     def _file(f, owner):
-        own = _Owner(owner)
-        return {"data": Context._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-                "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)}
+        return _file_dict(f, _Owner(owner))
 
     def decode_file(self, mp3: bytes):
         """MP3 bytes -> WAV bytes (+ kbps of the last header and the stego bits).  "data" is a read-only view of the
@@ -882,21 +555,14 @@ class Context:
         buf = np.frombuffer(mp3, dtype=np.uint8)
         owner, f = C.c_void_p(), File()
         check(lib().mp3s_decode_file(self.handle, buf.ctypes.data, len(mp3), C.byref(owner), C.byref(f)))
-        own = _Owner(owner)
-        return {"data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                "channels": f.channels, "n_frames": f.n_frames, "too_long": False, "hide_offset": 0,
-                "bits": _view(f.bits, np.uint8, (f.n_bits,))}
+        return _file_dict(f, _Owner(owner), bits="copy", hide=False)
 
     def encode_file(self, wav: bytes, bitrate=320, hide_bits=None):
         """WAV bytes -> MP3 bytes, with the reference's header checks and sample-count rules."""
         buf = np.frombuffer(wav, dtype=np.uint8)
-        hb, nh = None, 0
-        if hide_bits is not None and len(hide_bits):
-            hb = np.ascontiguousarray(hide_bits, dtype=np.uint8)
-            nh = len(hb)
+        _hb, hptr, nh = _hide_bits(hide_bits)
         owner, f = C.c_void_p(), File()
-        check(lib().mp3s_encode_file(self.handle, buf.ctypes.data, len(wav), int(bitrate), hb.ctypes.data if hb is not None else None,
-                                     nh, C.byref(owner), C.byref(f)))
+        check(lib().mp3s_encode_file(self.handle, buf.ctypes.data, len(wav), int(bitrate), hptr, nh, C.byref(owner), C.byref(f)))
         return self._file(f, owner)
 
     def decode_file_to_fd(self, mp3: bytes, fd: int):
@@ -906,18 +572,14 @@ class Context:
         buf = np.frombuffer(mp3, dtype=np.uint8)
         owner, f = C.c_void_p(), File()
         check(lib().mp3s_decode_file_fd(self.handle, buf.ctypes.data, len(mp3), int(fd), C.byref(owner), C.byref(f)))
-        own = _Owner(owner)
-        return {"len": f.len, "kbps": f.kbps, "sampling_rate": f.sampling_rate, "channels": f.channels, "n_frames": f.n_frames,
-                "too_long": False, "hide_offset": 0, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)}
+        return _file_dict(f, _Owner(owner), data="len", hide=False)
 
     def hide_message(self, mp3: bytes, message: str):
         """decode + re-encode with "<count>#<message>" hidden; the PCM stays on the device in between."""
         buf = np.frombuffer(mp3, dtype=np.uint8)
-        m = message.encode("utf-8")
-        mb = np.frombuffer(m, dtype=np.uint8) if m else None
+        _mb, mptr, nm = _message(message, empty_is_null=True)
         owner, f = C.c_void_p(), File()
-        check(lib().mp3s_hide_message(self.handle, buf.ctypes.data, len(mp3), mb.ctypes.data if mb is not None else None, len(m),
-                                      C.byref(owner), C.byref(f)))
+        check(lib().mp3s_hide_message(self.handle, buf.ctypes.data, len(mp3), mptr, nm, C.byref(owner), C.byref(f)))
         return self._file(f, owner)
 
     def clear_file(self, mp3: bytes):
@@ -935,43 +597,31 @@ class Context:
         if message is None:
             check(lib().mp3s_clear_file_fd(self.handle, buf.ctypes.data, len(mp3), int(fd), C.byref(f)))
         else:
-            m = message.encode("utf-8")
-            mb = np.frombuffer(m, dtype=np.uint8) if m else None
-            check(lib().mp3s_hide_message_fd(self.handle, buf.ctypes.data, len(mp3), mb.ctypes.data if mb is not None else None, len(m),
-                                             int(fd), C.byref(f)))
-        return {"len": f.len, "kbps": f.kbps, "sampling_rate": f.sampling_rate, "channels": f.channels, "n_frames": f.n_frames,
-                "too_long": bool(f.too_long), "hide_offset": f.hide_offset}
+            _mb, mptr, nm = _message(message, empty_is_null=True)
+            check(lib().mp3s_hide_message_fd(self.handle, buf.ctypes.data, len(mp3), mptr, nm, int(fd), C.byref(f)))
+        return _file_dict(f, None, data="len", bits=None)
 
     def reencode_block(self, mp3: bytes, message, rank, world, carry_in=None, index=None):
         """this rank's block of hide_message (message: str) / clear_file (None) on one stream spread over `world` ranks:
         decode + re-encode of the block on the device (include/mp3s.h mp3s_reencode_block).  carry_in: int64[17], None
         for rank 0."""
         buf = np.frombuffer(mp3, dtype=np.uint8)
-        mb = None if message is None else np.frombuffer(message.encode("utf-8") or b"\0", dtype=np.uint8)
-        nm = 0 if message is None else len(message.encode("utf-8"))
+        _mb, mptr, nm = _message(message)
         cin = Carry.from_array(carry_in) if carry_in is not None else None
         owner, b = C.c_void_p(), Block()
         check(lib().mp3s_reencode_block_indexed(self.handle, buf.ctypes.data, len(mp3), index.handle if index is not None else None,
-                                                None if mb is None else mb.ctypes.data, nm, int(rank), int(world),
+                                                mptr, nm, int(rank), int(world),
                                                 C.byref(cin) if cin is not None else None, C.byref(owner), C.byref(b)))
-        try:
-            f = b.file
-            return {"total_frames": b.total_frames, "first_frame": b.first_frame, "n_frames": b.n_frames, "is_last": bool(b.is_last),
-                    "carry_used": bool(b.carry_used), "carry_out": b.carry_out.to_array(),
-                    "mp3": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                    "too_long": bool(f.too_long), "hide_offset": f.hide_offset}
-        finally:
-            lib().mp3s_buf_free(owner)
+        with _Owner(owner):
+            return _block_dict(b)
 
     def hide_message_chunked(self, mp3: bytes, message, chunk_frames):
         """hide_message (message: str) / clear_file (None) on a file of any length, chunk_frames frames at a time through the
         device: one index walk, every chunk scanned on its own and run on the real carry of the one in front of it"""
         buf = np.frombuffer(mp3, dtype=np.uint8)
-        mb = None if message is None else np.frombuffer(message.encode("utf-8") or b"\0", dtype=np.uint8)
-        nm = 0 if message is None else len(message.encode("utf-8"))
+        _mb, mptr, nm = _message(message)
         owner, f = C.c_void_p(), File()
-        check(lib().mp3s_hide_message_chunked(self.handle, buf.ctypes.data, len(mp3), None if mb is None else mb.ctypes.data, nm,
-                                              int(chunk_frames), C.byref(owner), C.byref(f)))
+        check(lib().mp3s_hide_message_chunked(self.handle, buf.ctypes.data, len(mp3), mptr, nm, int(chunk_frames), C.byref(owner), C.byref(f)))
         return self._file(f, owner)
 
     def decode_chunks(self, mp3: bytes, chunk_frames, out_format=MP3S_PCM_I16):
@@ -994,17 +644,11 @@ class Context:
         if len(mp3s) == 0:
             return []
         n, _keep, files, lens = _file_list(mp3s)
-        msgs = [None if t is None else np.frombuffer(t.encode("utf-8") or b"\0", dtype=np.uint8) for t in messages]
-        mptr = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in msgs])
-        mlen = (C.c_size_t * n)(*[0 if t is None else len(t.encode("utf-8")) for t in messages])
+        _msgs, mptr, mlen = _message_list(messages)
         out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_hide_messages(self.handle, files, lens, n, mptr, mlen, C.byref(owner), out, status))
-        try:
-            return _per_file(out, status, lambda f: {
-                "data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long), "hide_offset": f.hide_offset})
-        finally:
-            lib().mp3s_buf_free(owner)
+        with _Owner(owner):
+            return _per_file(out, status, lambda f: _file_dict(f, None, data="copy", bits=None))
 
     def reveal_messages(self, mp3s, _max_streams=None):
         """reveal_message over a list of files as ONE device batch (mp3s_reveal_messages): the files the walk calls regular through
@@ -1018,13 +662,8 @@ class Context:
             check(lib().mp3s_reveal_messages(self.handle, files, lens, n, C.byref(owner), out, status))
         else:
             check(lib().mp3s_debug_reveal_messages(self.handle, files, lens, n, int(_max_streams), C.byref(owner), out, status))
-        try:
-            return _per_file(out, status, lambda f: {
-                "data": C.string_at(f.data, f.len) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                "channels": f.channels, "n_frames": f.n_frames, "too_long": False, "hide_offset": 0,
-                "bits": _view(f.bits, np.uint8, (f.n_bits,))})
-        finally:
-            lib().mp3s_buf_free(owner)
+        with _Owner(owner):
+            return _per_file(out, status, lambda f: _file_dict(f, None, data="copy", bits="copy", hide=False))
 
     def encode_files(self, wavs, bitrate=320, hide_bits=None, messages=None):
         """encode_file over a list of WAV files as one device batch per (sampling rate, bitrate).  bitrate: one int, or one per
@@ -1033,15 +672,11 @@ class Context:
         would raise."""
         if len(wavs) == 0:
             return []
-        n, files, lens, kbps, hptr, hlen, keep = _encode_args(wavs, bitrate, hide_bits, messages)
+        n, files, lens, kbps, hptr, hlen, _keep = _encode_args(wavs, bitrate, hide_bits, messages)
         out, status, owner = (File * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_encode_files(self.handle, files, lens, n, kbps, hptr, hlen, C.byref(owner), out, status))
         own = _Owner(owner)
-        del keep
-        return _per_file(out, status, lambda f: {
-            "data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-            "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)})
+        return _per_file(out, status, lambda f: _file_dict(f, own))
 
     @staticmethod
     def _capacity(x, own):
@@ -1060,11 +695,7 @@ class Context:
         if len(mp3s) == 0:
             return []
         n, _keep, files, lens = _file_list(mp3s)
-        mptr = mlen = None
-        if messages is not None:
-            msgs = [None if t is None else np.frombuffer(t.encode("utf-8") or b"\0", dtype=np.uint8) for t in messages]
-            mptr = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in msgs])
-            mlen = (C.c_size_t * n)(*[0 if t is None else len(t.encode("utf-8")) for t in messages])
+        _msgs, mptr, mlen = _message_list(messages)
         out, status, owner = (Capacity * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_capacity_files(self.handle, files, lens, n, mptr, mlen, 1 if profile else 0, C.byref(owner), out, status))
         own = _Owner(owner)
@@ -1075,11 +706,10 @@ class Context:
         its chain check.  With hide_bits / messages "hide_offset" / "too_long" are those of encode_files."""
         if len(wavs) == 0:
             return []
-        n, files, lens, kbps, hptr, hlen, keep = _encode_args(wavs, bitrate, hide_bits, messages)
+        n, files, lens, kbps, hptr, hlen, _keep = _encode_args(wavs, bitrate, hide_bits, messages)
         out, status, owner = (Capacity * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_capacity_wavs(self.handle, files, lens, n, kbps, hptr, hlen, 1 if profile else 0, C.byref(owner), out, status))
         own = _Owner(owner)
-        del keep
         return _per_file(out, status, lambda x: self._capacity(x, own))
 
     def capacity_dev(self, gr, segs, profile=True):
@@ -1088,18 +718,13 @@ class Context:
         gr = np.ascontiguousarray(gr, dtype=GR_OUT_DTYPE)
         segs = np.ascontiguousarray(segs, dtype=CHAIN_SEG_DTYPE)
         n_frames = len(gr) // 4
-        d_gr, d_segs = self.to_device(gr if len(gr) else np.zeros(1, dtype=GR_OUT_DTYPE)), self.to_device(segs)
-        d_out = self.alloc(len(segs) * CAPACITY_SEG_DTYPE.itemsize)
-        d_prof = self.alloc(max(n_frames, 1) * 4) if profile else None
-        try:
+        with self.device_scope() as dev:
+            d_gr, d_segs = dev.to_device(gr if len(gr) else np.zeros(1, dtype=GR_OUT_DTYPE)), dev.to_device(segs)
+            d_out = dev.alloc(len(segs) * CAPACITY_SEG_DTYPE.itemsize)
+            d_prof = dev.alloc(max(n_frames, 1) * 4) if profile else None
             check(lib().mp3s_capacity_dev(self.handle, d_gr, d_segs, len(segs), d_out, d_prof))
-            out = self.download(d_out, CAPACITY_SEG_DTYPE, (len(segs),))
-            prof = self.download(d_prof, np.uint32, (n_frames,)) if profile else None
-        finally:
-            for p in (d_gr, d_segs, d_out, d_prof):
-                if p is not None:
-                    self.free(p)
-        return out, prof
+            return (self.download(d_out, CAPACITY_SEG_DTYPE, (len(segs),)),
+                    self.download(d_prof, np.uint32, (n_frames,)) if profile else None)
 
     @staticmethod
     def _table_audit(x, own):
@@ -1120,10 +745,7 @@ class Context:
         that file's front end raises.  profile: "profile" = uint32 [n_frames], natural | forced << 4 | foreign << 8 | empty << 12."""
         if len(mp3s) == 0:
             return []
-        n, _keep, files, lens = _file_list([b"" if f is None else f for f in mp3s])
-        for i, f in enumerate(mp3s):
-            if f is None:
-                files[i] = None
+        n, _keep, files, lens = _file_list(mp3s, none_is_null=True)
         out, status, owner = (TableAudit * n)(), (C.c_int32 * n)(), C.c_void_p()
         check(lib().mp3s_table_audit_files(self.handle, files, lens, n, 1 if profile else 0, C.byref(owner), out, status))
         own = _Owner(owner)
@@ -1139,20 +761,15 @@ class Context:
         n_frames = len(side)
         if is_.size != n_frames * 2304:
             raise ValueError("is_ must hold 2304 samples per side record")
-        d_is, d_side, d_segs = self.to_device(is_), self.to_device(side), self.to_device(segs)
-        d_out = self.alloc(len(segs) * TABLE_AUDIT_DTYPE.itemsize)
-        d_units = self.alloc(n_frames * 4 * TABLE_AUDIT_UNIT_DTYPE.itemsize) if units else None
-        d_prof = self.alloc(n_frames * 4) if profile else None
-        try:
+        with self.device_scope() as dev:
+            d_is, d_side, d_segs = dev.to_device(is_), dev.to_device(side), dev.to_device(segs)
+            d_out = dev.alloc(len(segs) * TABLE_AUDIT_DTYPE.itemsize)
+            d_units = dev.alloc(n_frames * 4 * TABLE_AUDIT_UNIT_DTYPE.itemsize) if units else None
+            d_prof = dev.alloc(n_frames * 4) if profile else None
             check(lib().mp3s_table_audit_dev(self.handle, d_is, d_side, n_frames, int(nch), d_segs, len(segs), d_units, d_out, d_prof))
-            out = self.download(d_out, TABLE_AUDIT_DTYPE, (len(segs),))
-            un = self.download(d_units, TABLE_AUDIT_UNIT_DTYPE, (n_frames, 4)) if units else None
-            prof = self.download(d_prof, np.uint32, (n_frames,)) if profile else None
-        finally:
-            for p in (d_is, d_side, d_segs, d_out, d_units, d_prof):
-                if p is not None:
-                    self.free(p)
-        return out, un, prof
+            return (self.download(d_out, TABLE_AUDIT_DTYPE, (len(segs),)),
+                    self.download(d_units, TABLE_AUDIT_UNIT_DTYPE, (n_frames, 4)) if units else None,
+                    self.download(d_prof, np.uint32, (n_frames,)) if profile else None)
 
     @staticmethod
     def _distortion(x, own):
@@ -1196,16 +813,13 @@ class Context:
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         pairs = np.ascontiguousarray(pairs, dtype=PCM_PAIR_DTYPE)
         n_rec = int((pairs["out_first"].astype(np.int64) + pairs["n_frames"]).max()) if len(pairs) else 0
-        d_pcm = self.to_device(pcm if pcm.size else np.zeros(8, dtype=np.int16))
-        d_pairs = self.to_device(pairs)
-        d_frames, d_out = self.alloc(max(n_rec, 1) * 32), self.alloc(len(pairs) * 40)
-        try:
+        with self.device_scope() as dev:
+            d_pcm = dev.to_device(pcm if pcm.size else np.zeros(8, dtype=np.int16))
+            d_pairs = dev.to_device(pairs)
+            d_frames, d_out = dev.alloc(max(n_rec, 1) * 32), dev.alloc(len(pairs) * 40)
             check(lib().mp3s_dev_memset(self.handle, d_frames, 0xFF, max(n_rec, 1) * 32))
             check(lib().mp3s_pcm_diff_dev(self.handle, d_pcm, int(nch), d_pairs, pairs.ctypes.data, len(pairs), d_frames, d_out))
             return self.download(d_frames, PCM_FRAME_DIFF_DTYPE, (n_rec,)), self.download(d_out, PCM_PAIR_DIFF_DTYPE, (len(pairs),))
-        finally:
-            for p in (d_pcm, d_pairs, d_frames, d_out):
-                self.free(p)
 
     def pcm_alignments(self, mp3s_a, mp3s_b, max_lag=2304, search_rows=4608, lags=None, profile=False):
         """mp3s_a[i] against mp3s_b[i] across a re-encode's delay (mp3s_pcm_alignment_files): both lists are decoded on the device, the
@@ -1259,10 +873,10 @@ class Context:
         given = None if lags is None else np.ascontiguousarray(lags, dtype=np.int32)
         padded = np.zeros((pcm.size + 15) // 8 * 8 + 8, dtype=np.int16)   # (a whole dword behind the last row)
         padded[:pcm.size] = pcm
-        d_pcm, d_runs = self.to_device(padded), self.to_device(runs)
-        d_scores, d_lags = (self.alloc(n * n_lags * 8) if given is None else None), self.alloc(n * 40)
-        d_frames, d_out = self.alloc(max(n_rec, 1) * 32), self.alloc(n * 40)
-        try:
+        with self.device_scope() as dev:
+            d_pcm, d_runs = dev.to_device(padded), dev.to_device(runs)
+            d_scores, d_lags = (dev.alloc(n * n_lags * 8) if given is None else None), dev.alloc(n * 40)
+            d_frames, d_out = dev.alloc(max(n_rec, 1) * 32), dev.alloc(n * 40)
             check(lib().mp3s_dev_memset(self.handle, d_frames, 0xFF, max(n_rec, 1) * 32))
             if d_scores is not None:
                 check(lib().mp3s_dev_memset(self.handle, d_scores, 0xFF, n * n_lags * 8))
@@ -1270,10 +884,6 @@ class Context:
                                            None if given is None else given.ctypes.data, d_scores, d_lags, d_frames, d_out))
             return (None if d_scores is None else self.download(d_scores, np.uint64, (n, n_lags)), self.download(d_lags, PCM_LAG_DTYPE, (n,)),
                     self.download(d_frames, PCM_FRAME_DIFF_DTYPE, (n_rec,)), self.download(d_out, PCM_PAIR_DIFF_DTYPE, (n,)))
-        finally:
-            for p in (d_pcm, d_runs, d_scores, d_lags, d_frames, d_out):
-                if p is not None:
-                    self.free(p)
 
     # ---- PCM batches in the caller's device memory (include/mp3s.h section vi-f)
     def pcm_batch_dev(self, d_pcm, nch, d_items, items, channels, fmt, rows, d_out):
@@ -1313,10 +923,7 @@ class Context:
         n = len(mp3s)
         if n == 0:
             return []
-        _, _keep, ptrs, lens = _file_list([b"" if f is None else f for f in mp3s])
-        for i, f in enumerate(mp3s):
-            if f is None:
-                ptrs[i] = None
+        _, _keep, ptrs, lens = _file_list(mp3s, none_is_null=True)
         first = None
         if first_rows is not None:
             if len(first_rows) != n:
@@ -1327,15 +934,11 @@ class Context:
             info = (PcmBatchInfoAt * n)()
             check(lib().mp3s_pcm_batch_decode_files_at(self.handle, ptrs, lens, n, int(samplerate), first, int(rows), int(channels), BATCH_FORMATS[fmt],
                                                        _addr(d_out), int(out_bytes), info, status if per_file else None))
-            return _per_file(info, status, lambda x: {
-                "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate, "n_rows": x.n_rows,
-                "first_row": x.first_row, "valid_rows": x.valid_rows, "in_rows": x.in_rows, "out_rate": x.out_rate, "L": x.L, "M": x.M})
-        info = (PcmBatchInfo * n)()
-        check(lib().mp3s_pcm_batch_decode_files(self.handle, ptrs, lens, n, first, int(rows), int(channels), BATCH_FORMATS[fmt], _addr(d_out),
-                                                int(out_bytes), info, status if per_file else None))
-        return _per_file(info, status, lambda x: {
-            "n_frames": x.n_frames, "channels": x.nch, "sampling_rate": x.sampling_rate, "bit_rate": x.bit_rate, "n_rows": x.n_rows,
-            "first_row": x.first_row, "valid_rows": x.valid_rows})
+        else:
+            info = (PcmBatchInfo * n)()
+            check(lib().mp3s_pcm_batch_decode_files(self.handle, ptrs, lens, n, first, int(rows), int(channels), BATCH_FORMATS[fmt], _addr(d_out),
+                                                    int(out_bytes), info, status if per_file else None))
+        return _per_file(info, status, _batch_info_dict)
 
     def batch_rows(self, mp3s, per_file=False, samplerate=None):
         """the sizing call of decode_batch: the dicts it returns ("n_rows" = the rows file i decodes to, at `samplerate` when one is
@@ -1356,17 +959,7 @@ class Context:
         n = int(n_items)
         if len(lengths) != n:
             raise ValueError("one length per item")
-        if hide_bits is not None and messages is not None:
-            raise ValueError("hide_bits or messages, not both")
-        if messages is not None:
-            hide_bits = [None if m is None else np.array(message_frame(m), dtype=np.uint8) for m in messages]
-        hbs = hptr = hlen = None
-        if hide_bits is not None:
-            if len(hide_bits) != n:
-                raise ValueError("one bit string (or None) per item")
-            hbs = [None if h is None or not len(h) else np.ascontiguousarray(h, dtype=np.uint8) for h in hide_bits]
-            hptr = (C.c_void_p * n)(*[None if h is None else h.ctypes.data for h in hbs])
-            hlen = (C.c_int32 * n)(*[0 if h is None else len(h) for h in hbs])
+        _hbs, hptr, hlen = _hide_bits_list(hide_bits, messages, n, what="item")
         nr = (C.c_int64 * max(n, 1))(*[int(x) for x in lengths])
         out, status, owner = (File * max(n, 1))(), (C.c_int32 * max(n, 1))(), C.c_void_p()
         if resample:
@@ -1376,15 +969,11 @@ class Context:
             check(lib().mp3s_pcm_batch_encode(self.handle, _addr(d_in), n, int(channels), BATCH_FORMATS[fmt], int(rows), nr, int(samplerate),
                                               int(bitrate), hptr, hlen, C.byref(owner), out, status if per_file else None))
         own = _Owner(owner)
-        del hbs
-        return _per_file(out, status, lambda f: {
-            "data": self._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-            "hide_offset": f.hide_offset, "bits": _view_owned(f.bits, np.uint8, (f.n_bits,), own)}, n=n)
+        return _per_file(out, status, lambda f: _file_dict(f, own), n=n)
 
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
-        n, files, lens, _, _, _, keep = _encode_args(wavs, 128, None, None)
+        n, files, lens, _, _, _, _keep = _encode_args(wavs, 128, None, None)
         if self.get_option("wav_resample"):          # the frames at the target rate
             cap = sum(wav_resample_info(w, 128, self.get_option("wav_resample"))["n_frames"] for w in wavs)
         elif self.get_option("wav_import"):          # a frame of mono 8-bit samples is 1 152 bytes of its file
@@ -1393,30 +982,7 @@ class Context:
             cap = sum(len(w) for w in wavs) // 4608 + n
         pcm, got = np.zeros((cap, 1152, 2), dtype=np.int16), C.c_int64()
         check(lib().mp3s_debug_wav_gather(self.handle, files, lens, n, pcm.ctypes.data, cap, C.byref(got)))
-        del keep
         return pcm[:got.value]
-
-
-def _encode_args(wavs, bitrate, hide_bits, messages):
-    """the argument arrays of mp3s_encode_files / mp3s_pipe_submit_encode (+ everything that has to stay alive beside them)"""
-    n = len(wavs)
-    rates = [int(bitrate)] * n if np.isscalar(bitrate) else [int(b) for b in bitrate]
-    if len(rates) != n:
-        raise ValueError("one bitrate per file")
-    if hide_bits is not None and messages is not None:
-        raise ValueError("hide_bits or messages, not both")
-    if messages is not None:
-        hide_bits = [None if m is None else np.array(message_frame(m), dtype=np.uint8) for m in messages]
-    if hide_bits is not None and len(hide_bits) != n:
-        raise ValueError("one bit string (or None) per file")
-    _, keep, files, lens = _file_list(wavs)
-    kbps = (C.c_int32 * n)(*rates)
-    hbs = hptr = hlen = None
-    if hide_bits is not None:
-        hbs = [None if h is None or not len(h) else np.ascontiguousarray(h, dtype=np.uint8) for h in hide_bits]
-        hptr = (C.c_void_p * n)(*[None if h is None else h.ctypes.data for h in hbs])
-        hlen = (C.c_int32 * n)(*[0 if h is None else len(h) for h in hbs])
-    return n, files, lens, kbps, hptr, hlen, (keep, hbs)
 
 
 class Pipe:
@@ -1434,6 +1000,14 @@ class Pipe:
         self._keep = {}                         # ticket -> the buffers the job borrows
         self._out, self._status, self._cap = (File * max_files)(), (C.c_int32 * max_files)(), max_files
 
+    def _submitted(self, rc, ticket, keep):
+        """the end of every submit: None when every slot is taken, else the ticket, with `keep` held until the job is collected"""
+        if rc == E_BUSY:
+            return None
+        check(rc)
+        self._keep[ticket.value] = keep
+        return ticket.value
+
     def submit(self, mp3s, messages):
         """-> ticket, or None when `depth` jobs are in flight (collect one first).  messages: one str (or None = clear)
         per file, or None = clear all."""
@@ -1443,19 +1017,10 @@ class Pipe:
         if n > self._cap:
             raise ValueError(f"{n} files in one job, the pipe was made for {self._cap} (max_files)")
         _, keep, files, lens = _file_list(mp3s)
-        msgs = mptr = mlen = None
-        if messages is not None:
-            enc = [None if t is None else t.encode("utf-8") for t in messages]
-            msgs = [None if e is None else np.frombuffer(e or b"\0", dtype=np.uint8) for e in enc]
-            mptr = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in msgs])
-            mlen = (C.c_size_t * n)(*[0 if e is None else len(e) for e in enc])
+        msgs, mptr, mlen = _message_list(messages)
         t = C.c_int64()
         rc = lib().mp3s_pipe_submit(self.handle, files, lens, n, mptr, mlen, C.byref(t))
-        if rc == E_BUSY:
-            return None
-        check(rc)
-        self._keep[t.value] = (keep, msgs, files, lens, mptr, mlen)
-        return t.value
+        return self._submitted(rc, t, (keep, msgs, files, lens, mptr, mlen))
 
     def submit_decode(self, mp3s):
         """a decode job (MP3 -> WAV bytes + stego bits per file) -> ticket, or None when every slot is taken"""
@@ -1465,11 +1030,7 @@ class Pipe:
         _, keep, files, lens = _file_list(mp3s)
         t = C.c_int64()
         rc = lib().mp3s_pipe_submit_decode(self.handle, files, lens, n, C.byref(t))
-        if rc == E_BUSY:
-            return None
-        check(rc)
-        self._keep[t.value] = (keep, files, lens)
-        return t.value
+        return self._submitted(rc, t, (keep, files, lens))
 
     def submit_encode(self, wavs, bitrate=320, hide_bits=None, messages=None):
         """an encode job (WAV -> MP3 per file; the arguments of Context.encode_files) -> ticket, or None when every slot is taken"""
@@ -1478,28 +1039,19 @@ class Pipe:
         n, files, lens, kbps, hptr, hlen, keep = _encode_args(wavs, bitrate, hide_bits, messages)
         t = C.c_int64()
         rc = lib().mp3s_pipe_submit_encode(self.handle, files, lens, n, kbps, hptr, hlen, C.byref(t))
-        if rc == E_BUSY:
-            return None
-        check(rc)
-        self._keep[t.value] = (keep, files, lens, hptr)
-        return t.value
+        return self._submitted(rc, t, (keep, files, lens, hptr))
 
     def submit_block(self, mp3, message, rank, world, carry_in=None):
         """a block job: rank `rank` of `world`'s share of hide_message (message: str) / clear_file (None) on one stream (the
         arguments of Context.reencode_block) -> ticket, or None when every slot is taken.  collect() hands out the dict
         Context.reencode_block returns."""
         buf = np.frombuffer(mp3, dtype=np.uint8)
-        enc = None if message is None else message.encode("utf-8")
-        mb = None if enc is None else np.frombuffer(enc or b"\0", dtype=np.uint8)
+        mb, mptr, nm = _message(message)
         cin = Carry.from_array(carry_in) if carry_in is not None else None
         t = C.c_int64()
-        rc = lib().mp3s_pipe_submit_block(self.handle, buf.ctypes.data, len(mp3), None if mb is None else mb.ctypes.data, 0 if enc is None else len(enc),
+        rc = lib().mp3s_pipe_submit_block(self.handle, buf.ctypes.data, len(mp3), mptr, nm,
                                           int(rank), int(world), C.byref(cin) if cin is not None else None, C.byref(t))
-        if rc == E_BUSY:
-            return None
-        check(rc)
-        self._keep[t.value] = (mp3, buf, mb)
-        return t.value
+        return self._submitted(rc, t, (mp3, buf, mb))
 
     def collect(self):
         """-> (ticket, [per file: the dict Context.hide_message returns, or the Mp3sError that file alone would raise]);
@@ -1513,11 +1065,7 @@ class Pipe:
             rc = lib().mp3s_pipe_collect_block(self.handle, C.byref(t), C.byref(owner), C.byref(b))
             self._keep.pop(t.value, None)
             check(rc)
-            own, f = _Owner(owner), b.file
-            return t.value, {"total_frames": b.total_frames, "first_frame": b.first_frame, "n_frames": b.n_frames, "is_last": bool(b.is_last),
-                             "carry_used": bool(b.carry_used), "carry_out": b.carry_out.to_array(),
-                             "mp3": Context._owned_bytes(f.data, f.len, own) if f.len else b"", "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-                             "too_long": bool(f.too_long), "hide_offset": f.hide_offset}
+            return t.value, _block_dict(b, _Owner(owner))
         t, owner, nf = C.c_int64(), C.c_void_p(), C.c_int32()
         rc = lib().mp3s_pipe_collect(self.handle, C.byref(t), C.byref(owner), self._out, self._status, self._cap, C.byref(nf))
         if rc == E_BUSY:
@@ -1527,10 +1075,7 @@ class Pipe:
         self._keep.pop(t.value, None)
         check(rc)
         own = _Owner(owner)
-        return t.value, _per_file(self._out, self._status, lambda f: {
-            "data": Context._owned_bytes(f.data, f.len, own), "kbps": f.kbps, "sampling_rate": f.sampling_rate,
-            "channels": f.channels, "n_frames": f.n_frames, "too_long": bool(f.too_long),
-            "hide_offset": f.hide_offset, "bits": _view(f.bits, np.uint8, (f.n_bits,))}, nf.value)
+        return t.value, _per_file(self._out, self._status, lambda f: _file_dict(f, own, bits="copy"), nf.value)
 
     def stats(self):
         s = PipeStats()
@@ -1546,11 +1091,7 @@ class Pipe:
             if self in getattr(self.ctx, "_pipes", ()):
                 self.ctx._pipes.remove(self)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _close_quietly
 
 
 class StreamIndex:
@@ -1570,26 +1111,15 @@ class StreamIndex:
         buf = np.frombuffer(self._data, dtype=np.uint8)
         owner, p = C.c_void_p(), Scanned()
         check(lib().mp3s_scan_range(buf.ctypes.data, len(self._data), self.handle, int(first_frame), int(n_frames), C.byref(owner), C.byref(p)))
-        try:
-            n = p.n_frames
-            return {"n_frames": n, "channels": p.nch, "sampling_rate": p.sampling_rate, "bit_rate": p.bit_rate,
-                    "dup_last_frame": p.dup_last_frame, "gpu_ok": bool(p.gpu_ok), "max_part2_3_length": p.max_part2_3_length,
-                    "side": _view(p.side, FRAME_SIDE_DTYPE, (n,)), "hdr": _view(p.hdr, FRAME_HDR_DTYPE, (n,)),
-                    "blob": _view(p.blob, np.uint8, (p.blob_len,)), "bits": _view(p.bits, np.uint8, (p.n_bits,)),
-                    "frame_size": _view(p.frame_size, np.int32, (n,))}
-        finally:
-            lib().mp3s_buf_free(owner)
+        with _Owner(owner):
+            return _scanned_dict(p)
 
     def close(self):
         if self.handle:
             lib().mp3s_index_free(self.handle)
             self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _close_quietly
 
 
 def reveal_message(mp3: bytes):
@@ -1680,14 +1210,11 @@ def wav_header(n_rows, nch, rate):
 
 def message_frame(message: str):
     """'<character count>#<message>' as UTF-8 bits, MSB first (uint8 0/1)."""
-    m = message.encode("utf-8")
-    mb = np.frombuffer(m, dtype=np.uint8) if m else None
+    _mb, mptr, nm = _message(message, empty_is_null=True)
     owner, p, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-    check(lib().mp3s_message_frame(mb.ctypes.data if mb is not None else None, len(m), C.byref(owner), C.byref(p), C.byref(n)))
-    try:
+    check(lib().mp3s_message_frame(mptr, nm, C.byref(owner), C.byref(p), C.byref(n)))
+    with _Owner(owner):
         return _view(p.value, np.uint8, (n.value,))
-    finally:
-        lib().mp3s_buf_free(owner)
 
 
 def message_reveal(bits):
@@ -1695,19 +1222,16 @@ def message_reveal(bits):
     b = np.ascontiguousarray(bits, dtype=np.uint8)
     owner, p, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
     check(lib().mp3s_message_reveal(b.ctypes.data if len(b) else None, len(b), C.byref(owner), C.byref(p), C.byref(n)))
-    try:
+    with _Owner(owner):
         return _view(p.value, np.uint8, (n.value,)).tobytes()
-    finally:
-        lib().mp3s_buf_free(owner)
 
 
 def parse_stream(data: bytes):
     """Host front end only (no GPU): Huffman-decoded spectra, side records, stego bits."""
     buf = np.frombuffer(data, dtype=np.uint8)
-    owner = C.c_void_p()
-    p = Parsed()
+    owner, p = C.c_void_p(), Parsed()
     check(lib().mp3s_parse_stream(buf.ctypes.data, len(data), C.byref(owner), C.byref(p)))
-    try:
+    with _Owner(owner):
         n = p.n_frames
         return {"n_frames": n, "channels": p.nch, "sampling_rate": p.sampling_rate, "bit_rate": p.bit_rate,
                 "dup_last_frame": p.dup_last_frame, "is": _view(p.is_, np.int16, (n, 2, 2, 576)),
@@ -1715,35 +1239,34 @@ def parse_stream(data: bytes):
                 "bits": _view(p.bits, np.uint8, (p.n_bits,)),
                 "table_select": _view(p.table_select, np.int32, (n, 2, 2, 3)),
                 "frame_size": _view(p.frame_size, np.int32, (n,))}
-    finally:
-        lib().mp3s_buf_free(owner)
+
+
+def _scanned_dict(p):
+    """the dict of an mp3s_scanned, every array a copy"""
+    n = p.n_frames
+    return {"n_frames": n, "channels": p.nch, "sampling_rate": p.sampling_rate, "bit_rate": p.bit_rate,
+            "dup_last_frame": p.dup_last_frame, "gpu_ok": bool(p.gpu_ok), "max_part2_3_length": p.max_part2_3_length,
+            "side": _view(p.side, FRAME_SIDE_DTYPE, (n,)), "hdr": _view(p.hdr, FRAME_HDR_DTYPE, (n,)),
+            "blob": _view(p.blob, np.uint8, (p.blob_len,)), "bits": _view(p.bits, np.uint8, (p.n_bits,)),
+            "frame_size": _view(p.frame_size, np.int32, (n,))}
 
 
 def scan_stream(data: bytes):
     """Host byte-level scan only (no GPU): frame side info + main-data blob for the device Huffman kernel."""
     buf = np.frombuffer(data, dtype=np.uint8)
-    owner = C.c_void_p()
-    p = Scanned()
+    owner, p = C.c_void_p(), Scanned()
     check(lib().mp3s_scan_stream(buf.ctypes.data, len(data), C.byref(owner), C.byref(p)))
-    try:
-        n = p.n_frames
-        return {"n_frames": n, "channels": p.nch, "sampling_rate": p.sampling_rate, "bit_rate": p.bit_rate,
-                "dup_last_frame": p.dup_last_frame, "gpu_ok": bool(p.gpu_ok), "max_part2_3_length": p.max_part2_3_length,
-                "side": _view(p.side, FRAME_SIDE_DTYPE, (n,)), "hdr": _view(p.hdr, FRAME_HDR_DTYPE, (n,)),
-                "blob": _view(p.blob, np.uint8, (p.blob_len,)), "bits": _view(p.bits, np.uint8, (p.n_bits,)),
-                "frame_size": _view(p.frame_size, np.int32, (n,))}
-    finally:
-        lib().mp3s_buf_free(owner)
+    with _Owner(owner):
+        return _scanned_dict(p)
 
 
 def walk_stream(data: bytes):
     """Host walk from frame header to frame header (no GPU): what the device-side parser (Context.parse_frames_dev) needs.
     regular == False: the stream needs scan_stream (false syncs, inherited header fields, pointers in front of the file)."""
     buf = np.frombuffer(data, dtype=np.uint8)
-    owner = C.c_void_p()
-    w = Walked()
+    owner, w = C.c_void_p(), Walked()
     check(lib().mp3s_walk_stream(buf.ctypes.data, len(data), C.byref(owner), C.byref(w)))
-    try:
+    with _Owner(owner):
         if not w.regular:
             return {"regular": False}
         n = w.n_frames
@@ -1753,8 +1276,6 @@ def walk_stream(data: bytes):
                 "dup_last_frame": w.dup_last_frame, "max_part2_3_length": w.max_part2_3_length, "any_silent": bool(w.any_silent),
                 "blob_len": w.blob_len, "refs": _view(w.refs, FRAME_REF_DTYPE, (n,)), "stream": stream,
                 "tables": _view(w.tables, np.uint8, (n, 4))}
-    finally:
-        lib().mp3s_buf_free(owner)
 
 
 def walk_rate(data: bytes, seconds=1.0):
@@ -1771,10 +1292,8 @@ def stego_bits(tsel, nch, carry=None):
     carry = np.zeros(4, dtype=np.uint8) if carry is None else np.ascontiguousarray(carry, dtype=np.uint8).copy()
     owner, bits, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
     check(lib().mp3s_stego_bits(tsel.ctypes.data, len(tsel), nch, carry.ctypes.data, C.byref(owner), C.byref(bits), C.byref(n)))
-    try:
+    with _Owner(owner):
         return _view(bits.value, np.uint8, (n.value,)), carry
-    finally:
-        lib().mp3s_buf_free(owner)
 
 
 def rate_frames(samplerate, bitrate, nch, n_frames):
@@ -1792,25 +1311,8 @@ def format_stream(samplerate, bitrate, ix, gr, scfsi):
     owner, mp3, ln = C.c_void_p(), C.c_void_p(), C.c_size_t()
     check(lib().mp3s_format_stream(samplerate, bitrate, n, ix.ctypes.data, gr.ctypes.data, scfsi.ctypes.data,
                                    C.byref(owner), C.byref(mp3), C.byref(ln)))
-    try:
+    with _Owner(owner):
         return _view(mp3.value, np.uint8, (ln.value,)).tobytes()
-    finally:
-        lib().mp3s_buf_free(owner)
-
-
-DEV_TABLES_DTYPE = np.dtype([
-    ("synth_matrix", "<f8", (64, 32)), ("synth_window", "<f8", (512,)), ("synth_window_t", "<f8", (32, 16)), ("imdct_cos36", "<f8", (36, 18)),
-    ("imdct_cos12", "<f8", (12, 6)), ("sine_block", "<f8", (4, 36)), ("alias_cs", "<f8", (8,)), ("alias_ca", "<f8", (8,)),
-    ("pow43", "<f8", (8207,)), ("pow2q", "<f8", (312,)), ("pow2h", "<f8", (40,)), ("sqrt2", "<f8"),
-    ("synth_fast", "<f8", (344,)), ("synth_eps_a", "<f8"), ("synth_eps_x", "<f8"), ("synth_eps_g", "<f8"), ("imdct_kappa", "<f8"), ("synth_window_f", "<f8", (32, 16)), ("synth_window_fs", "<f8", (32, 16)), ("synth_xbound", "<f8"), ("synth_reserved", "<f8"), ("synth_stream", "<f8", (2, 8, 112)), ("stream_cx", "<f8", (32, 16)), ("stream_taps", "<f8", (2, 32, 16)), ("imdct_rot", "<f8", (1, 18)), ("imdct_pq", "<f8", (10, 18)),
-    ("rq_map", "u1", (3, 3, 32, 20)), ("reorder_src", "<i2", (3, 576)), ("pre_tab", "u1", (24,)),
-    ("enwindow", "<i4", (512,)), ("fl", "<i4", (32, 64)), ("cos_l", "<i4", (18, 36)), ("mdct_cs", "<i4", (8,)),
-    ("mdct_ca", "<i4", (8,)), ("steptab", "<f8", (128,)), ("steptabi", "<i4", (128,)), ("_pad_int2idx", "u1", (8,)), ("int2idx", "<u2", (10000,)),   # (int2idx is alignas(16))
-    ("sfb_long", "<i4", (3, 23)), ("en_base", "<i4", (32,)), ("en_step", "<i4", (32,)), ("subdv", "<i4", (23, 2)), ("subdiv_lut", "<u4", (3, 289)), ("hlen13", "u1", (256,)), ("hlen15", "u1", (256,)),
-    ("hlen16", "u1", (256,)), ("hlen24", "u1", (256,)), ("hlen_c1a", "u1", (16,)), ("linbits", "u1", (32,)),
-    ("linmax", "<i4", (32,)), ("transform", "u1", (32, 2)), ("dec_max", "u1", (32,)),
-    ("huf_tinfo", "<u4", (32,)), ("_pad_huf_tab", "u1", (8,)), ("huf_tab", "<u2", (10256 + 1200 + 2560,)),   # (huf_tab is alignas(16))
-    ("hcod", "<u4", (4, 256)), ("hcod_c1a", "u1", (16,)), ("rl_hl", "<u4", (256, 2)), ("rl_c1w", "<u4", (16,)), ("rl_t1", "<u4", (128,)), ("rl_t2", "<u4", (128,)), ("rl_t8", "<u4", (128,))], align=True)   # (the struct is 16-byte aligned)
 
 
 def debug_tables():
@@ -1823,12 +1325,9 @@ def debug_tables():
 
 def host_share(handle=None):
     """mp3s_ctx_host_share; without a context handle: the host's side alone (gpu_node_cpus 0), no GPU needed"""
-    class S(C.Structure):
-        _fields_ = [("pinned_pooled_bytes", C.c_uint64), ("pinned_pool_cap_bytes", C.c_uint64), ("local_world_size", C.c_int32),
-                    ("cpus_allowed", C.c_int32), ("gpu_node_cpus", C.c_int32), ("reserved", C.c_int32)]
-    st = S()
+    st = HostShare()
     check(lib().mp3s_ctx_host_share(handle, C.byref(st)))
-    return {k: int(getattr(st, k)) for k, _ in S._fields_ if k != "reserved"}
+    return {k: int(getattr(st, k)) for k, _ in HostShare._fields_ if k != "reserved"}
 
 
 _default_ctx = None

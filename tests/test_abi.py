@@ -1,7 +1,12 @@
-"""The C-ABI library loads and exports every symbol include/mp3s.h declares (no compute without a GPU)."""
+"""The C-ABI library loads and exports every symbol include/mp3s.h declares, and the binding (mp3stego/_abi.py, mp3stego/_lib.py) agrees
+with that header: prototypes by count, records by size, and its own surface with what it was before (no compute without a GPU)."""
 import ctypes as C
+import inspect
+import json
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -9,10 +14,31 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def header_text():
+    """include/mp3s.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mp3s.h")).read(), flags=re.S)
+
+
 def declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "mp3s.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mp3s_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(mp3s_[a-z0-9_]+)\s*\(", header_text())))
+
+
+def declared_parameter_counts():
+    """{function: the number of parameters include/mp3s.h declares it with}; () and (void) count as 0"""
+    counts = {}
+    for name, params in re.findall(r"\b(mp3s_[a-z0-9_]+)\s*\(([^()]*)\)", header_text()):
+        assert name not in counts, f"{name} is declared twice"
+        counts[name] = 0 if params.strip() in ("", "void") else params.count(",") + 1
+    return counts
+
+
+def declared_records():
+    """the names (without mp3s_) of the records include/mp3s.h defines: typedef struct { ... } mp3s_<name>;"""
+    return re.findall(r"typedef\s+struct\s*\{[^{}]*\}\s*mp3s_([a-z0-9_]+)\s*;", header_text())
+
+
+def mirror_size(m):
+    return m.itemsize if isinstance(m, np.dtype) else C.sizeof(m)
 
 
 def test_every_declared_symbol_is_exported(mlib):
@@ -50,7 +76,94 @@ def test_argument_checks_do_not_need_a_gpu(mlib):
     assert L.mp3s_rate_frames(22050, 128, 2, 4, out.ctypes.data, None) == mlib.E_UNSUPPORTED
     assert L.mp3s_rate_frames(44100, 100, 2, 4, out.ctypes.data, None) == mlib.E_UNSUPPORTED
     # the probes of round 6: a null context is refused; the host's share of a rank is answered without one
-    L.mp3s_debug_guard_margin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     assert L.mp3s_debug_guard_margin(None, None, None, 0) == mlib.E_ARG
     hs = mlib.host_share()
     assert hs["cpus_allowed"] >= 1 and hs["local_world_size"] >= 1 and hs["gpu_node_cpus"] == 0 and hs["pinned_pool_cap_bytes"] >= 1 << 30
+
+
+def test_prototypes_match_the_header():
+    """ONE table gives every declared function its prototype: exactly the declared names, in the header's order, each with as many
+    argument types as the header declares parameters -- no exceptions"""
+    from mp3stego import _abi, _lib
+    counts = declared_parameter_counts()
+    assert sorted(counts) == declared_symbols() and len(counts) >= 115
+    assert list(_abi.PROTOTYPES) == list(counts), "the table lists what the header declares, in its order"
+    assert _abi.SYMBOLS == list(_abi.PROTOTYPES) and _lib.SYMBOLS is _abi.SYMBOLS
+    wrong = {name: (len(argtypes), counts[name]) for name, (_, argtypes) in _abi.PROTOTYPES.items() if len(argtypes) != counts[name]}
+    assert not wrong, f"(argtypes, declared parameters) differ: {wrong}"
+    for name, (restype, _) in _abi.PROTOTYPES.items():          # what returns int in the header has no restype in the table
+        returns = re.search(r"([A-Za-z_][A-Za-z0-9_ ]*?[ *]+)" + name + r"\s*\(", header_text()).group(1).strip()
+        assert (restype is None) == (returns == "int"), (name, returns, restype)
+        assert (restype is _abi.VOID) == (returns == "void"), (name, returns, restype)
+    pkg = os.path.join(ROOT, "mp3-steganography-lib_amd", "mp3stego")     # and nothing else in the package assigns a prototype
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                hits = re.findall(r"\.(?:argtypes|restype)\s*=[^=]", open(os.path.join(dirpath, f)).read())
+                assert len(hits) == (2 if f == "_abi.py" else 0), (f, hits)
+
+
+def test_every_prototype_is_applied(mlib):
+    L = mlib.lib()
+    for name, (restype, argtypes) in mlib.PROTOTYPES.items():
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is (C.c_int if restype is None else None if restype is mlib.VOID else restype), name
+
+
+def test_record_sizes_match_the_compiler(tmp_path):
+    """every ctypes.Structure and numpy dtype that mirrors a record of include/mp3s.h is as large as the host C compiler makes the record"""
+    from mp3stego import _abi
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("needs a C compiler")
+    records = declared_records()
+    assert len(records) >= 44 and len(set(records)) == len(records)
+    assert set(_abi.RECORDS) <= set(records), "the map names records the header does not define"
+    # no header record with a mirror is missing: a mirror is the record's name as a class (GranuleSI) or as a dtype (GRANULE_SI_DTYPE)
+    mirrors = {n.lower().replace("_", ""): v for n, v in vars(_abi).items()
+               if isinstance(v, np.dtype) or (inspect.isclass(v) and issubclass(v, C.Structure))}
+    for r in records:
+        found = [mirrors[k] for k in (r.replace("_", ""), r.replace("_", "") + "dtype") if k in mirrors]
+        assert [m for m in found if not any(m is x for x in _abi.RECORDS.get(r, ()))] == [], f"mp3s_{r} has a mirror that RECORDS leaves out"
+    listed = [m for ms in _abi.RECORDS.values() for m in ms]
+    unlisted = [n for n, v in mirrors.items() if not any(v is m for m in listed)]
+    assert unlisted == ["devtablesdtype"], "every mirror but the device tables' (not a record of the header) is in RECORDS"
+    src = tmp_path / "sizes.c"
+    src.write_text('#include "mp3s.h"\n#include <stdio.h>\nint main(void) {\n'
+                   + "".join('    printf("%s %%zu\\n", sizeof(mp3s_%s));\n' % (r, r) for r in _abi.RECORDS) + "    return 0;\n}\n")
+    exe = tmp_path / "sizes"
+    r = subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    sizes = {k: int(v) for k, v in (line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, timeout=60).stdout.splitlines())}
+    assert set(sizes) == set(_abi.RECORDS)
+    wrong = {r: (sizes[r], [mirror_size(m) for m in ms]) for r, ms in _abi.RECORDS.items() if any(mirror_size(m) != sizes[r] for m in ms)}
+    assert not wrong, f"(sizeof in C, sizes of the mirrors) differ: {wrong}"
+
+
+def test_binding_surface_is_pinned(golden_dir):
+    """every name mp3stego._lib had before the binding was split is still an attribute of it, and every public function and every method of
+    Context, Pipe and StreamIndex still takes the pinned parameters first (tests/golden/gen_binding_surface.py wrote the file from the
+    commit before the split); what was added behind them has a default"""
+    from mp3stego import _lib
+    pinned = json.load(open(os.path.join(golden_dir, "g15_binding_surface.json")))
+    assert len(pinned["names"]) >= 148 and len(pinned["functions"]) >= 27 and sum(len(m) for m in pinned["methods"].values()) >= 82
+    missing = [n for n in pinned["names"] if not hasattr(_lib, n)]
+    assert not missing, f"names mp3stego._lib no longer has: {missing}"
+
+    def check(where, fn, was):
+        sig = inspect.signature(fn)
+        params = list(sig.parameters.values())
+        k = [k for k in range(len(params) + 1) if str(sig.replace(parameters=params[:k])) == was]
+        assert k, f"{where}{sig} no longer begins with the pinned {was}"
+        added = [p.name for p in params[k[0]:] if p.default is p.empty and p.kind not in (p.VAR_POSITIONAL, p.VAR_KEYWORD)]
+        assert not added, f"{where}: added parameters without a default: {added}"
+    for name, was in pinned["functions"].items():
+        assert inspect.isfunction(getattr(_lib, name)), name
+        check(name, getattr(_lib, name), was)
+    for cls, methods in pinned["methods"].items():
+        for name, was in methods.items():
+            assert name in vars(getattr(_lib, cls)), f"{cls}.{name} is gone"
+            fn = vars(getattr(_lib, cls))[name]
+            check(f"{cls}.{name}", getattr(fn, "__func__", fn), was)
