@@ -447,14 +447,7 @@ int mp3s_decode_file_fd(mp3s_ctx *c, const uint8_t *mp3, size_t len, int fd, mp3
     c->sink_fd = -1;
     if (rc) return rc;
     const size_t done = out->len > 44 ? std::min(c->sink_done, out->len - 44) : 0;
-    auto put = [&](const uint8_t *src, size_t n, size_t at) {
-        while (n) {
-            const ssize_t w = pwrite(fd, src, n, (off_t)at);
-            if (w <= 0) return false;
-            src += w; at += (size_t)w; n -= (size_t)w;
-        }
-        return true;
-    };
+    auto put = [&](const uint8_t *src, size_t n, size_t at) { return pwrite_all(fd, src, n, at) == n; };
     if (!put(out->data, 44, 0) || !put(out->data + 44 + done, out->len - 44 - done, 44 + done) || ftruncate(fd, (off_t)out->len) != 0) {
         mp3s_buf_free(*owner); *owner = nullptr;
         return fail(MP3S_E_ARG, "writing the WAV to the file descriptor failed (errno %d)", errno);

@@ -841,12 +841,8 @@ static int reencode_fd(mp3s_ctx *c, const uint8_t *mp3, size_t len, const uint8_
     int rc = reencode(c, mp3, len, msg, n_msg, hide, &owner, out);
     c->sink_fd = -1;
     if (rc == MP3S_OK) {
-        size_t at = std::min(c->sink_done, out->len);
-        while (at < out->len) {
-            const ssize_t w = pwrite(fd, out->data + at, out->len - at, (off_t)at);
-            if (w <= 0) { rc = fail(MP3S_E_ARG, "writing the result to the file descriptor failed (errno %d)", errno); break; }
-            at += (size_t)w;
-        }
+        const size_t at = std::min(c->sink_done, out->len);
+        if (pwrite_all(fd, out->data + at, out->len - at, at) != out->len - at) rc = fail(MP3S_E_ARG, "writing the result to the file descriptor failed (errno %d)", errno);
         if (rc == MP3S_OK && ftruncate(fd, (off_t)out->len) != 0) rc = fail(MP3S_E_ARG, "cutting the output file to length failed (errno %d)", errno);
     }
     if (owner) mp3s_buf_free(owner);

@@ -3,6 +3,7 @@
 // part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <array>
@@ -284,6 +285,18 @@ struct mp3s_buf {
 // MP3S_TRACE=1: phase timings of the file pipelines on stderr
 inline bool trace_on() { static const bool on = getenv("MP3S_TRACE") != nullptr; return on; }
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// (mp3s_*_fd) pwrite until the n bytes of `src` stand in the file from `at` on, or a write fails: the bytes written.  A count below n is for the
+// caller to react to; errno is the failed write's.
+inline size_t pwrite_all(int fd, const uint8_t *src, size_t n, size_t at)
+{
+    size_t done = 0;
+    while (done < n) {
+        const ssize_t w = pwrite(fd, src + done, n - done, (off_t)(at + done));
+        if (w <= 0) break;
+        done += (size_t)w;
+    }
+    return done;
+}
 
 // ---------------------------------------------------------------- the frame of the list-of-files calls (file_lists.cpp)
 // mp3s_decode_streams, mp3s_hide_messages, mp3s_encode_files, mp3s_reveal_messages and mp3s_pipe_collect answer per file by ONE

@@ -204,6 +204,7 @@ int issue_down(mp3s_pipe *P, Job &j, Slot &s);
 bool prepare_encode(mp3s_pipe *P, Job &j, Slot &s);
 int issue_encode(mp3s_pipe *P, Job &j, Slot &s, bool defer_down);
 void sync_all(mp3s_pipe *P);
+void pipe_release_slots(mp3s_pipe *P, bool drain);   // a one-file call is over: every slot free; drain: nothing of it in flight any more either
 void bind_to(const std::vector<int> &cpus);
 bool finish_fast(mp3s_pipe *P, Job *j, Slot &s, bool *resolved);
 int pipe_create(mp3s_ctx *c, int depth, size_t max_job_bytes, int scan_threads, bool internal, mp3s_pipe **out, size_t max_frames = 0);

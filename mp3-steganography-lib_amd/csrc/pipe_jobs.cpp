@@ -728,6 +728,20 @@ void sync_all(mp3s_pipe *P)
     (void)hipStreamSynchronize(P->s_down);
 }
 
+// The context's own pipe at the end of a one-file call (run_file.cpp): its slots are free for the next call.  drain: the call ends early, with
+// chunks possibly in flight -- every stream of the pipe is waited for first, the runtime's error is taken, and no download is remembered as
+// reading a PCM buffer.  (A call that succeeded has retired every chunk; keep_slot stays as its last chunks left it.)
+void pipe_release_slots(mp3s_pipe *P, bool drain)
+{
+    if (drain) {
+        sync_all(P);
+        if (P->s_img) (void)hipStreamSynchronize(P->s_img);
+        (void)hipGetLastError();
+    }
+    for (auto &s : P->slots) s.busy = false;
+    if (drain) P->keep_slot[0] = P->keep_slot[1] = -1;
+}
+
 namespace {
 
 void run_slow(mp3s_pipe *P, Job &j)   // mu_issue held

@@ -7,27 +7,8 @@
 // PCM in front of the chunk are recomputed and dropped; the padding recurrence is replayed from the frame index; the message
 // cursor and the inherited addresses (17 integers) are GUESSED -- "the message is hidden, nothing is inherited" -- and every
 // chunk reports whether it looked at them: only a chunk that did, on a guess that was wrong, is run again on the real carry.
-#include <unistd.h>
 #include "pipe_internal.h"
-
-namespace {
-
-bool same_effect(const mp3s_carry &a, const mp3s_carry &b, int64_t n_hide)
-{
-    return std::memcmp(a.chain, b.chain, sizeof a.chain) == 0 && std::min<int64_t>(a.cursor, n_hide) == std::min<int64_t>(b.cursor, n_hide);
-}
-
-struct RunChunk {
-    std::unique_ptr<Job> job;
-    long first = 0, count = 0;
-    bool last = false;
-    mp3s_carry guess = {}, out = {};
-    bool carry_used = false;
-    int64_t out_off = 0, out_len = 0;
-    bool done = false;
-};
-
-}  // namespace
+#include "run_plan.h"
 
 int ensure_own_pipe(mp3s_ctx *c, size_t chunk_bytes, size_t chunk_frames)
 {
@@ -38,6 +19,8 @@ int ensure_own_pipe(mp3s_ctx *c, size_t chunk_bytes, size_t chunk_frames)
         // half rate (r06, tools/repro_config5.py + rocprofv3 --memory-copy-trace: 28 instead of 56 GB/s down, the same sizes, agents and stream;
         // kept instead: the first call 9 instead of 20 ms, none slow behind it -- config 5's joint_ms_short_48k_192 at 1.6 or 2.5 ms by where the
         // seven timed calls fell).  Frame sizes are bounded (1 441 bytes), so at most a few pipes are ever parked; they go with the context.
+        // (a whole-mode piece and growing files park more than "a few".  What is asked for here is RunPlan's pipe_bytes /
+        // pipe_frames, run_plan.h: a bound on the parked pipes is a change to this function and that field.)
         pipe_quiesce(c->own_pipe);
         c->parked_pipes.push_back(c->own_pipe);
         c->own_pipe = nullptr;
@@ -63,107 +46,81 @@ void destroy_own_pipe(mp3s_ctx *c)   // (the context is being destroyed)
     forget_lanes(c);
 }
 
-constexpr int kRunWhole = 2;             // run_file_impl: the stream inherits scalefactors across frames -- once more, as one piece
-constexpr long kWholeFrames = 4 * kDecodeChunk;   // ... if it is not longer than this (the slots are sized for the piece)
+namespace {
 
-static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, const uint8_t *utf8, size_t n_msg, int out_format, mp3s_buf **owner, RunResult *out, bool whole);
+struct RunChunk {
+    std::unique_ptr<Job> job;
+    long first = 0, count = 0;
+    bool last = false;
+    mp3s_carry guess = {}, out = {};
+    bool carry_used = false;
+    int64_t out_off = 0, out_len = 0;
+    bool done = false;
+};
 
-int run_file(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, const uint8_t *utf8, size_t n_msg, int out_format, mp3s_buf **owner, RunResult *out)
-{
-    int rc = run_file_impl(c, mp3, len, mode, utf8, n_msg, out_format, owner, out, false);
-    // A granule of a mixed block (or one behind a short granule 0 with scfsi set) reads scalefactors written many frames earlier
-    // (SURVEY D10); the Huffman kernel finds them by walking back through the stream's side records, which a chunk that
-    // starts in the middle of the stream cannot.  Such a file goes through the same stages in ONE piece (the transforms still
-    // in groups): 1.7 instead of 4.4 ms for 10 000 frames, which the synchronous path spends in the host parser.
-    if (rc == kRunWhole) rc = run_file_impl(c, mp3, len, mode, utf8, n_msg, out_format, owner, out, true);
-    return rc == kRunWhole ? kRunFallback : rc;
-}
+// (for the duration of the call the context computes on the stream its pipe rehearsed best with, if that is not its own)
+struct StreamSwap {
+    mp3s_ctx *c; hipStream_t keep;
+    StreamSwap(mp3s_ctx *c_, hipStream_t s) : c(c_), keep(c_->stream) { if (s) c->stream = s; }
+    ~StreamSwap() { if (c->stream != keep) { (void)hipStreamSynchronize(c->stream); c->stream = keep; } }
+};
+struct FileUpGuard { mp3s_pipe *P; ~FileUpGuard() { file_up_end(P); } };
 
-static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, const uint8_t *utf8, size_t n_msg, int out_format, mp3s_buf **owner, RunResult *out, bool whole)
-{
-    c->sink_done = 0;                                                // (mp3s_*_fd: nothing of THIS attempt's result is in the file yet)
-    if (!c->opt[MP3S_OPT_FILE_PIPELINE] || !c->opt[MP3S_OPT_DEVICE_PARSE]) return kRunFallback;
-    const bool decode = mode == kRunDecode;
-    const double t_call0 = trace_on() ? now_ms() : 0;
-    FrameWalker w;
-    // (errors and empty streams: the synchronous path words them)
-    if (len < 8 || len > 0xffff0000ull || w.open(mp3, len) || w.ended || w.hd.version != 1 || w.hd.layer != 3 || w.frame_size <= 0) {
-        c->run_stats.fallbacks++;
-        return kRunFallback;
-    }
-    const long fs0 = w.frame_size;
-    const long n_est = (long)((len - (size_t)w.offset) / (size_t)std::max<long>(fs0 - 1, 24)) + 8;
-    std::vector<uint8_t> bits;
-    if (mode == kRunHide) {
-        message_frame(utf8, n_msg, bits);
-        if (bits.size() > 0x3fffff00) { c->run_stats.fallbacks++; return kRunFallback; }
-    }
-    const int64_t n_hide = (int64_t)bits.size();
-    // ---- the chunk plan.  Every chunk costs a dozen launches and their gaps, so few chunks; the first one small, so that
-    //      the device starts early; a message's reach inside the first chunk, where the cursor is decided (not guessed)
-    const long reach_frames = n_hide ? (long)((n_hide * 5 / 14 + 32) / 4 * 9 / 8 + 64) : 0;
-    long chunk = (long)c->opt[MP3S_OPT_CHUNK_FRAMES];
-    long first_chunk;
-    const long kMaxChunk = kDecodeChunk - 2;
-    if (chunk > 0) { chunk = std::min(chunk, kMaxChunk); first_chunk = chunk; }
-    else if (n_est <= 3000) { chunk = first_chunk = std::min(kMaxChunk, n_est + 16); }                    // one chunk: nothing to overlap with
-    else {
-        // A short first chunk, so that the device starts early, then chunks as long as a transform group takes: every chunk
-        // costs the host 0.15 ms of walking, laying out and queueing (two dozen runtime calls), which four chunks of a
-        // 10 000-frame file do not win back (round 3, profiles/r03a_chunk_plans.json: 2 048 + the rest 1.41 ms, four chunks 1.49, one 1.57;
-        // a 100 000-frame file: 8 192 + 16 000s 8.1 ms)
-        first_chunk = std::min<long>(8192, std::max<long>(2048, n_est / 12));
-        chunk = kMaxChunk;
-    }
-    if (c->opt[MP3S_OPT_FIRST_CHUNK_FRAMES] > 0) first_chunk = (long)std::min<int64_t>(c->opt[MP3S_OPT_FIRST_CHUNK_FRAMES], kMaxChunk);
-    first_chunk = std::min(kMaxChunk, std::max(first_chunk, reach_frames));
-    if (whole) {
-        if (n_est > kWholeFrames) { c->run_stats.fallbacks++; return kRunFallback; }
-        first_chunk = chunk = n_est + 64;          // one piece
-    }
-    const long cap_frames = std::max(chunk, first_chunk) + 2;
-    // (a message that reaches further than a chunk: the synchronous path's plan over the whole file)
-    if (reach_frames > kMaxChunk || ensure_own_pipe(c, (size_t)cap_frames * (size_t)(fs0 + 2) + 4096, (size_t)cap_frames)) { c->run_stats.fallbacks++; return kRunFallback; }
-    mp3s_pipe *P = c->own_pipe;
-    HIPCHK(hipSetDevice(c->device));
-    // (for the duration of the call the context computes on the stream its pipe rehearsed best with, if that is not its own)
-    struct StreamSwap {
-        mp3s_ctx *c; hipStream_t keep;
-        StreamSwap(mp3s_ctx *c_, hipStream_t s) : c(c_), keep(c_->stream) { if (s) c->stream = s; }
-        ~StreamSwap() { if (c->stream != keep) { (void)hipStreamSynchronize(c->stream); c->stream = keep; } }
-    } swap(c, P->s_comp);
-    // the file's bytes set off for the device now (the first chunk's first), the walk follows
-    struct FileUpGuard { mp3s_pipe *P; ~FileUpGuard() { file_up_end(P); } } up_guard{P};
-    file_up_begin(P, mp3, len, (size_t)w.offset + (size_t)std::min<long>(first_chunk, n_est) * (size_t)(fs0 + 1) + 2048, n_est);
+// One call on one file, from the first chunk's walk to the result: what run_file_impl opened and planned (borrowed), the stream's frame
+// table, the result block, the chunks and where the early sink stands.  run_file_impl drives it: step() chunk after chunk, the last issue_b,
+// settle(), fill().
+struct FileRun {
+    mp3s_ctx *c; mp3s_pipe *P;
+    const uint8_t *mp3; size_t len;
+    const bool decode; const int out_format; const size_t esz;
+    FrameWalker &w;
+    const std::vector<uint8_t> &bits; const int64_t n_hide;   // the framed message
+    const long fs0, n_est, cap_frames;
+    const double t_call0;
     // ---- the stream's frame table, grown as the walk proceeds
-    std::vector<FrameRef> &refs = c->h_refs;
-    if ((long)refs.size() < n_est + 64) refs.resize((size_t)n_est + 64);
-    std::vector<uint8_t> &tables = c->h_tables;
-    if (n_hide) { w.tables_wanted = (long)n_hide + (long)n_hide / 16 + 64; tables.resize((size_t)first_chunk * 4 + 16); }
+    std::vector<FrameRef> &refs;
+    std::vector<uint8_t> &tables;
     long n_walked = 0;
-    std::unique_ptr<mp3s_buf> res(new mp3s_buf());
+    std::unique_ptr<mp3s_buf> res;
     std::vector<RunChunk> chunks;
     PlaceEntry fix;                              // the stream's last frame, decoded here when the walk ends (E14)
     bool have_fix = false;
     int rate = 0, kbps = 0, nch = 0;
-    const size_t esz = pcm_elem(out_format);
     size_t res_cap = 0;
+    int64_t hide_offset = 0;
+    // (mp3s_*_fd: a chunk's bytes go to the file as soon as they are final -- while the chunks behind it are still on the device.)
+    // Only into a file that was EMPTY when the call began (sink_early): a stream that is refused late -- a damaged frame in the last chunk, found
+    // on the device -- ends in an error, and the reference has not touched its output file at that point; a file that held something is written
+    // at the end of a call that succeeded (the entry point does that), a fresh one is removed by the caller that created it.
+    bool sink_on;
+    size_t sink_next = 0;
+    mp3s_carry sink_real = {};
+
+    FileRun(mp3s_ctx *c_, const uint8_t *mp3_, size_t len_, bool decode_, int out_format_, FrameWalker &w_, const std::vector<uint8_t> &bits_, long fs0_, long n_est_,
+            const RunPlan &plan, double t_call0_)
+        : c(c_), P(c_->own_pipe), mp3(mp3_), len(len_), decode(decode_), out_format(out_format_), esz(pcm_elem(out_format_)), w(w_), bits(bits_),
+          n_hide((int64_t)bits_.size()), fs0(fs0_), n_est(n_est_), cap_frames(plan.cap_frames), t_call0(t_call0_), refs(c_->h_refs), tables(c_->h_tables),
+          res(new mp3s_buf()),
+          sink_on(c_->sink_fd >= 0 && c_->sink_early && (!decode_ || out_format_ == MP3S_PCM_I16))   // (a decode's chunks have no carries: final when they are down)
+    {
+        if ((long)refs.size() < n_est + 64) refs.resize((size_t)n_est + 64);
+        if (n_hide) { w.tables_wanted = (long)n_hide + (long)n_hide / 16 + 64; tables.resize((size_t)plan.first_chunk * 4 + 16); }
+    }
+
     // EVERY way out of the call after the first chunk has been queued goes through here (another path takes the file, or a hard
     // error such as MP3S_E_HIP): nothing of this call may still be in flight when its result block, its jobs and the slots are
     // let go -- a queued download would otherwise write into page-locked memory the pool hands to the next call
-    auto fallback = [&](const char *why, int code = kRunFallback) {
+    int fallback(const char *why, int code = kRunFallback)
+    {
         if (trace_on()) fprintf(stderr, "mp3s: run_file: %s -> %s\n", why, code == kRunWhole ? "once more, in one piece" : code == kRunFallback ? "synchronous path" : "error");
         if (code == kRunFallback) c->run_stats.fallbacks++;
-        sync_all(P);
-        if (P->s_img) (void)hipStreamSynchronize(P->s_img);
-        (void)hipGetLastError();
-        for (auto &s : P->slots) s.busy = false;
-        P->keep_slot[0] = P->keep_slot[1] = -1;
+        pipe_release_slots(P, true);
         return code;
-    };
+    }
+
     // retire chunk k: wait for its results, settle its verdict and its carry
-    int64_t hide_offset = 0;
-    auto retire = [&](size_t k) -> int {
+    int retire(size_t k)
+    {
         RunChunk &rc = chunks[k];
         if (rc.done) return MP3S_OK;
         Job *j = rc.job.get();
@@ -171,14 +128,14 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         if (issue_down(P, *j, s)) return kRunFallback;
         if (hipEventSynchronize(s.e_down) != hipSuccess) return fail(MP3S_E_HIP, "waiting for a chunk's results failed");
         if (trace_on()) {
-            float up = 0, huff = 0, rate = 0, comp = 0, down = 0;
+            float up = 0, huff = 0, rl = 0, comp = 0, down = 0;
             hipEvent_t e0 = P->slots[(size_t)chunks[0].job->slot].e_start;
             if (k >= (size_t)P->depth) e0 = s.e_start;
-            (void)hipEventElapsedTime(&up, e0, s.e_up); (void)hipEventElapsedTime(&huff, e0, s.e_huff); (void)hipEventElapsedTime(&rate, e0, s.e_rate);
+            (void)hipEventElapsedTime(&up, e0, s.e_up); (void)hipEventElapsedTime(&huff, e0, s.e_huff); (void)hipEventElapsedTime(&rl, e0, s.e_rate);
             (void)hipEventElapsedTime(&comp, e0, s.e_comp); (void)hipEventElapsedTime(&down, e0, s.e_down);
             (void)hipGetLastError();
             fprintf(stderr, "mp3s: run_file: chunk %zu's results are here %.3f ms after the call's start; on the device, from the first chunk's start: inputs up %.3f, "
-                            "front end done %.3f, rate loop done %.3f, tail done %.3f, results down %.3f ms\n", k, now_ms() - t_call0, up, huff, rate, comp, down);
+                            "front end done %.3f, rate loop done %.3f, tail done %.3f, results down %.3f ms\n", k, now_ms() - t_call0, up, huff, rl, comp, down);
         }
         bool resolved = false;
         const bool ok = finish_fast(P, j, s, &resolved);
@@ -198,46 +155,34 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         }
         rc.done = true;
         return MP3S_OK;
-    };
-    // (mp3s_*_fd: a chunk's bytes go to the file as soon as they are final -- while the chunks behind it are still on the device.  Final =
-    // the chunk will not be run again on its real carry: the test of the settling loop at the end, on a copy of the carries, nothing
-    // settled here.  Chunks 0 .. k have been retired.)
-    // Only into a file that was EMPTY when the call began (sink_early): a stream that is refused late -- a damaged frame in the last chunk, found
-    // on the device -- ends in an error, and the reference has not touched its output file at that point; a file that held something is written
-    // at the end of a call that succeeded (the entry point does that), a fresh one is removed by the caller that created it.
-    bool sink_on = c->sink_fd >= 0 && c->sink_early && (!decode || out_format == MP3S_PCM_I16);   // (a decode's chunks have no carries: final when they are down)
-    size_t sink_next = 0;
-    mp3s_carry sink_real = {};
-    auto sink_upto = [&](size_t k) {
+    }
+
+    // The early sink (see sink_on), chunks 0 .. k having been retired.  Final = the chunk will not be run again on its real carry: the test
+    // settle() makes at the end (carry_settles, run_plan.h), here on a copy of the carries, nothing settled.
+    void sink_upto(size_t k)
+    {
         for (; sink_on && sink_next <= k && sink_next < chunks.size(); sink_next++) {
             const RunChunk &rc = chunks[sink_next];
             mp3s_carry mine = rc.out;
-            if (!decode && sink_next > 0) {
-                const bool live = std::min<int64_t>(sink_real.cursor, n_hide) < n_hide;
-                if (!same_effect(sink_real, rc.guess, n_hide) && (rc.carry_used || live)) { sink_on = false; break; }   // (it will be run again: its bytes change)
-                mine.cursor = sink_real.cursor + (rc.out.cursor - rc.guess.cursor);
-            }
+            if (!decode && sink_next > 0 && !carry_settles(sink_real, rc.guess, rc.carry_used, n_hide, mine)) { sink_on = false; break; }   // (it will be run again: its bytes change)
             const size_t off = decode ? (size_t)rc.first * 1152 * (size_t)nch * esz : (size_t)rc.out_off;
-            size_t left = decode ? (size_t)rc.count * 1152 * (size_t)nch * esz : (size_t)rc.out_len, at = off;
+            const size_t n = decode ? (size_t)rc.count * 1152 * (size_t)nch * esz : (size_t)rc.out_len;
             if (off != c->sink_done) { sink_on = false; break; }
-            const uint8_t *src = res->big[0].data() + (decode ? 64 : 0) + off;
-            while (left) {
-                const ssize_t w = pwrite(c->sink_fd, src, left, (off_t)(c->sink_base + at));
-                if (w <= 0) { sink_on = false; break; }                     // (the caller writes what is missing, and reports what fails there)
-                src += w; at += (size_t)w; left -= (size_t)w;
-            }
-            if (!sink_on) break;
-            c->sink_done = at;
+            // (a write that fails: the caller writes what is missing, and reports what fails there)
+            if (pwrite_all(c->sink_fd, res->big[0].data() + (decode ? 64 : 0) + off, n, c->sink_base + off) != n) { sink_on = false; break; }
+            c->sink_done = off + n;
             sink_real = mine;
         }
-    };
+    }
+
     // issue frames [first, first + count) of the stream as a chunk on slot `slot`
     // A chunk is queued in two steps.  issue_a: its front end (file piece, parse, Huffman -- a latency chain of 0.1 ms whatever the
     // chunk's size).  issue_b: the results of the chunk in front, this chunk's encoder inputs (laid out here, 0.1 ms of host time
-    // for 8 000 frames) and everything behind the front end.  The main loop runs issue_a(k + 1) BEFORE issue_b(k) (round 4): the next
+    // for 8 000 frames) and everything behind the front end.  step() runs issue_a(k + 1) BEFORE issue_b(k) (round 4): the next
     // chunk's front end is then on the device while this chunk's kernels still run -- queued behind issue_b(k) it started 0.1 ms
     // later, ended behind the chunk's rate loop, and the compute stream sat idle for 0.05 ms between two chunks.
-    auto issue_a = [&](size_t k, const mp3s_carry *carry) -> int {
+    int issue_a(size_t k, const mp3s_carry *carry)
+    {
         RunChunk &rc = chunks[k];
         rc.job.reset(new Job());
         Job &j = *rc.job;
@@ -269,8 +214,9 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
             return fail(MP3S_E_HIP, "chunk %zu: failure injected by MP3S_OPT_FAIL_CHUNK", k);
         }
         return MP3S_OK;
-    };
-    auto issue_b = [&](size_t k) -> int {
+    }
+    int issue_b(size_t k)
+    {
         RunChunk &rc = chunks[k];
         Job &j = *rc.job;
         Slot &s = P->slots[(size_t)j.slot];
@@ -286,17 +232,13 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         const int e = issue_back(P, j, s, true, true);
         if (trace_on()) fprintf(stderr, "mp3s:   inputs + back of chunk %zu %.3f ms\n", k, now_ms() - t_i);
         return e ? kRunFallback : MP3S_OK;
-    };
-    auto issue = [&](size_t k, const mp3s_carry *carry) -> int {
-        const int r = issue_a(k, carry);
-        return r ? r : issue_b(k);
-    };
-    // ---- walk and issue, chunk after chunk
-    long want = first_chunk;
-    // (a helper thread that walks the chunks behind the first while this one queues was tried: it wakes up later than the walk takes --
-    // 1.56 instead of 1.38 ms per 10 000-frame file)
-    for (size_t k = 0; k == 0 || !w.ended; k++) {
-        const double t_walk0 = trace_on() ? now_ms() : 0;
+    }
+    int issue(size_t k, const mp3s_carry *carry) { const int r = issue_a(k, carry); return r ? r : issue_b(k); }
+
+    // walk up to `want` frames behind those walked so far -> *got; the first chunk settles what the stream is and makes the result block,
+    // the last one decodes the stream's last frame
+    int walk_chunk(size_t k, long want, long *got_out)
+    {
         long got = 0;
         const long room = (long)refs.size() - n_walked - 8;
         if (room <= 0) return fallback("more frames than the file's first frame size promised");
@@ -309,13 +251,23 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
             if (nch < 1 || nch > 2) return fallback("channel count");
             if (!decode && reencode_params(w.sampling_rate, w.bit_rate, w.nch, got, 0, &kbps)) return fallback("not a stream the encoder takes");
             // the result block: the frames the file can hold at its first frame's size
-            res_cap = decode ? 64 + (size_t)(n_est + 64) * 1152 * (size_t)nch * esz : (size_t)(n_est + 64) * (size_t)(fs0 + 2);
+            res_cap = run_result_bytes(decode, n_est, fs0, nch, esz);
             if (!res->big[0].reserve(res_cap)) return fallback("no memory for the result");
         } else if (w.nch != nch) return fallback("channel count changes");
         if (w.ended) {
             if (w.dup_last) return fallback("a repeated last frame");
             have_fix = fill_place_entry(fix, 0, [&](int16_t *is, mp3s_granule_si *si) { bool alone = false; return w.decode_last(is, si, &alone) == 0 && alone; });
         }
+        *got_out = got;
+        return MP3S_OK;
+    }
+
+    // chunk k: walk it, retire the chunk that had its slot, queue its front end and the back of the chunk in front (issue_a's comment)
+    int step(size_t k, long want)
+    {
+        const double t_walk0 = trace_on() ? now_ms() : 0;
+        long got = 0;
+        if (const int r = walk_chunk(k, want, &got)) return r;
         const double t_walk1 = trace_on() ? now_ms() : 0;
         if (k >= (size_t)P->depth) {               // the slot's previous chunk first
             const int r = retire(k - (size_t)P->depth);
@@ -332,72 +284,118 @@ static int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, 
         int r = issue_a(k, nullptr);
         if (!r && k > 0) r = issue_b(k - 1);
         if (trace_on()) fprintf(stderr, "mp3s: run_file chunk %zu (%ld frames): walk %.3f ms, wait for the slot %.3f ms, prepare + issue %.3f ms\n", k, got, t_walk1 - t_walk0, t_ret - t_walk1, now_ms() - t_ret);
-        if (r) return fallback("a chunk does not fit the stages", r);
-        want = chunk;
+        return r ? fallback("a chunk does not fit the stages", r) : MP3S_OK;
     }
-    {
-        const int r = issue_b(chunks.size() - 1);
-        if (r) return fallback("a chunk does not fit the stages", r);
-    }
-    if (trace_on()) fprintf(stderr, "mp3s: run_file: all chunks queued %.3f ms after the call's start\n", now_ms() - t_call0);
+
     // ---- settle the chunks in order: the carries
-    if (!decode && (w.sampling_rate != rate || w.bit_rate / 1000 != kbps)) return fallback("the last header names another rate");
-    // (first everything that needs a chunk's device buffers -- its verdict, a resolve -- then the carries: a chunk that is run
-    // again takes a slot, and with it the buffers of the chunk that had it last)
-    for (size_t k = 0; k < chunks.size(); k++) {
-        const int r = retire(k);
-        if (r) return fallback("a chunk needs another path", r);
-        sink_upto(k);
-    }
-    mp3s_carry real = {};
-    for (size_t k = 0; k < chunks.size(); k++) {
-        int r = MP3S_OK;
-        RunChunk &rc = chunks[k];
-        if (decode) continue;
-        if (k > 0) {
-            const bool live = std::min<int64_t>(real.cursor, n_hide) < n_hide;     // the message is still being hidden at this boundary
-            if (!same_effect(real, rc.guess, n_hide) && (rc.carry_used || live)) {
+    int settle()
+    {
+        if (!decode && (w.sampling_rate != rate || w.bit_rate / 1000 != kbps)) return fallback("the last header names another rate");
+        // (first everything that needs a chunk's device buffers -- its verdict, a resolve -- then the carries: a chunk that is run
+        // again takes a slot, and with it the buffers of the chunk that had it last)
+        for (size_t k = 0; k < chunks.size(); k++) {
+            const int r = retire(k);
+            if (r) return fallback("a chunk needs another path", r);
+            sink_upto(k);
+        }
+        mp3s_carry real = {};
+        for (size_t k = 0; k < chunks.size() && !decode; k++) {
+            RunChunk &rc = chunks[k];
+            if (k > 0 && !carry_settles(real, rc.guess, rc.carry_used, n_hide, rc.out)) {
                 // the chunk looked at its carry and the guess was wrong: once more, on the real one (everything behind it has been issued
                 // and stays as it is unless its own carry turns out wrong in turn)
                 if (trace_on()) fprintf(stderr, "mp3s: run_file: chunk %zu depends on its carry: again\n", k);
                 sync_all(P);
                 c->run_stats.reruns++;
                 rc.done = false;
-                r = issue(k, &real);
+                int r = issue(k, &real);
                 if (!r) r = retire(k);
                 if (r) return fallback("a chunk needs another path", r);
                 sync_all(P);
-            } else {
-                // nothing in the chunk looked at the carry: every chain entry it hands on is its own; only the count of tables
-                // seen so far moves with the real cursor
-                rc.out.cursor = real.cursor + (rc.out.cursor - rc.guess.cursor);
             }
+            real = rc.out;
+            hide_offset = real.cursor;
         }
-        real = rc.out;
-        hide_offset = real.cursor;
+        return MP3S_OK;
     }
+
     // ---- the result
-    std::memset(out, 0, sizeof *out);
-    out->n_frames = n_walked; out->nch = nch; out->sampling_rate = w.sampling_rate; out->bit_rate = w.bit_rate;
-    if (decode) {
-        // stego bits: the serial pass over the table-index words of all chunks (their halo frames left out)
-        uint8_t carry[4] = {0, 0, 0, 0};
-        for (auto &rc : chunks) {
-            const Job &j = *rc.job;
-            stego_bits_from_tsel((const uint64_t *)j.res->big[1].data() + j.ck.halo, rc.count, nch, carry, res->bits);
+    void fill(RunResult *out)
+    {
+        std::memset(out, 0, sizeof *out);
+        out->n_frames = n_walked; out->nch = nch; out->sampling_rate = w.sampling_rate; out->bit_rate = w.bit_rate;
+        if (decode) {
+            // stego bits: the serial pass over the table-index words of all chunks (their halo frames left out)
+            uint8_t carry[4] = {0, 0, 0, 0};
+            for (auto &rc : chunks) {
+                const Job &j = *rc.job;
+                stego_bits_from_tsel((const uint64_t *)j.res->big[1].data() + j.ck.halo, rc.count, nch, carry, res->bits);
+            }
+            out->pcm = res->big[0].data() + 64; out->n_rows = (int64_t)n_walked * 1152;
+            out->bits = res->bits.data(); out->n_bits = res->bits.size();
+        } else {
+            const RunChunk &lc = chunks.back();
+            out->mp3 = res->big[0].data(); out->mp3_len = (size_t)(lc.out_off + lc.out_len);
+            out->kbps = kbps;
+            out->hide_offset = hide_offset;
+            out->too_long = hide_offset < n_hide - 1 ? 1 : 0;
         }
-        out->pcm = res->big[0].data() + 64; out->n_rows = (int64_t)n_walked * 1152;
-        out->bits = res->bits.data(); out->n_bits = res->bits.size();
-    } else {
-        const RunChunk &lc = chunks.back();
-        out->mp3 = res->big[0].data(); out->mp3_len = (size_t)(lc.out_off + lc.out_len);
-        out->kbps = kbps;
-        out->hide_offset = hide_offset;
-        out->too_long = hide_offset < n_hide - 1 ? 1 : 0;
     }
-    for (auto &s : P->slots) s.busy = false;
-    c->run_stats.files++; c->run_stats.chunks += (int64_t)chunks.size();
-    *owner = res.release();
+};
+
+int run_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, const uint8_t *utf8, size_t n_msg, int out_format, mp3s_buf **owner, RunResult *out, bool whole)
+{
+    c->sink_done = 0;                                                // (mp3s_*_fd: nothing of THIS attempt's result is in the file yet)
+    if (!c->opt[MP3S_OPT_FILE_PIPELINE] || !c->opt[MP3S_OPT_DEVICE_PARSE]) return kRunFallback;
+    const double t_call0 = trace_on() ? now_ms() : 0;
+    FrameWalker w;
+    // (errors and empty streams: the synchronous path words them)
+    if (len < 8 || len > 0xffff0000ull || w.open(mp3, len) || w.ended || w.hd.version != 1 || w.hd.layer != 3 || w.frame_size <= 0) {
+        c->run_stats.fallbacks++;
+        return kRunFallback;
+    }
+    const long fs0 = w.frame_size;
+    const long n_est = run_frames_estimate(len, (size_t)w.offset, fs0);
+    std::vector<uint8_t> bits;
+    if (mode == kRunHide) {
+        message_frame(utf8, n_msg, bits);
+        if (bits.size() > 0x3fffff00) { c->run_stats.fallbacks++; return kRunFallback; }
+    }
+    const RunPlan plan = run_plan(n_est, (int64_t)bits.size(), c->opt[MP3S_OPT_CHUNK_FRAMES], c->opt[MP3S_OPT_FIRST_CHUNK_FRAMES], whole);
+    if (!plan.ok || ensure_own_pipe(c, plan.pipe_bytes(fs0), plan.pipe_frames())) { c->run_stats.fallbacks++; return kRunFallback; }
+    mp3s_pipe *P = c->own_pipe;
+    HIPCHK(hipSetDevice(c->device));
+    StreamSwap swap(c, P->s_comp);
+    // the file's bytes set off for the device now (the first chunk's first), the walk follows
+    FileUpGuard up_guard{P};
+    file_up_begin(P, mp3, len, (size_t)w.offset + (size_t)std::min<long>(plan.first_chunk, n_est) * (size_t)(fs0 + 1) + 2048, n_est);
+    FileRun run(c, mp3, len, mode == kRunDecode, out_format, w, bits, fs0, n_est, plan, t_call0);
+    // ---- walk and issue, chunk after chunk
+    // (a helper thread that walks the chunks behind the first while this one queues was tried: it wakes up later than the walk takes --
+    // 1.56 instead of 1.38 ms per 10 000-frame file)
+    for (size_t k = 0; k == 0 || !w.ended; k++)
+        if (const int r = run.step(k, k == 0 ? plan.first_chunk : plan.chunk)) return r;
+    if (const int r = run.issue_b(run.chunks.size() - 1)) return run.fallback("a chunk does not fit the stages", r);
+    if (trace_on()) fprintf(stderr, "mp3s: run_file: all chunks queued %.3f ms after the call's start\n", now_ms() - t_call0);
+    if (const int r = run.settle()) return r;
+    run.fill(out);
+    pipe_release_slots(P, false);
+    c->run_stats.files++; c->run_stats.chunks += (int64_t)run.chunks.size();
+    *owner = run.res.release();
     if (trace_on()) fprintf(stderr, "mp3s: run_file: done %.3f ms after the call's start\n", now_ms() - t_call0);
     return MP3S_OK;
 }
+
+}  // namespace
+
+int run_file(mp3s_ctx *c, const uint8_t *mp3, size_t len, int mode, const uint8_t *utf8, size_t n_msg, int out_format, mp3s_buf **owner, RunResult *out)
+{
+    int rc = run_file_impl(c, mp3, len, mode, utf8, n_msg, out_format, owner, out, false);
+    // A granule of a mixed block (or one behind a short granule 0 with scfsi set) reads scalefactors written many frames earlier
+    // (SURVEY D10); the Huffman kernel finds them by walking back through the stream's side records, which a chunk that
+    // starts in the middle of the stream cannot.  Such a file goes through the same stages in ONE piece (the transforms still
+    // in groups): 1.7 instead of 4.4 ms for 10 000 frames, which the synchronous path spends in the host parser.
+    if (rc == kRunWhole) rc = run_file_impl(c, mp3, len, mode, utf8, n_msg, out_format, owner, out, true);
+    return rc == kRunWhole ? kRunFallback : rc;
+}
+

@@ -138,6 +138,7 @@ def reencode_sharded(ctx, mp3: bytes, message=None, comm=None):
     last_rank = min(comm.world, int(blk["total_frames"])) - 1                     # ranks behind it hold no frame
     if 0 < comm.rank <= last_rank:
         real = comm.recv(comm.rank - 1)
+        # (the same rule between the chunks of a one-file call, in C++: carry_settles of csrc/run_plan.h)
         live = min(int(real[0]), n_hide) < n_hide                    # the message is still being hidden at this boundary
         if not _same_effect(real, guess, n_hide) and (blk["carry_used"] or live):
             blk = ctx.reencode_block(mp3, message, comm.rank, comm.world, real, index=ix)

@@ -270,7 +270,7 @@ def rank_main(n_streams, frames, ranks):
             rreq.wait()
             carry_wait_ms += (time.perf_counter() - tw) * 1e3
             real = real_t.numpy().copy()
-            n_hide = len(_lib.message_frame(msgs[i]))
+            n_hide = len(_lib.message_frame(msgs[i]))     # (the rule of mp3stego/sharded.py; in C++: carry_settles of csrc/run_plan.h)
             live = min(int(real[0]), n_hide) < n_hide
             if not _same_effect(real, guess, n_hide) and (res["carry_used"] or live):
                 reruns += 1
