@@ -475,17 +475,17 @@ __device__ __forceinline__ void enc_mdct_pair(const int32_t (&in)[54], int32_t *
         __builtin_amdgcn_sched_barrier(0);
         const Coef nxt = load_coef(k < 17 ? k + 1 : 17);
         __builtin_amdgcn_sched_barrier(0);
-        int32_t a0 = 0, a1 = 0;
+        uint32_t a0 = 0, a1 = 0;   // the reference's np.int32 sums wrap (a full-scale tone leaves int32): unsigned adds, so that the wrap is defined
 #pragma unroll
         for (int q = 0; q < 9; q++) {
             const i32x4 c = cur.q[q];
-            a0 += mulhi_vs(in[4 * q], c.x);     a1 += mulhi_vs(in[18 + 4 * q], c.x);
-            a0 += mulhi_vs(in[4 * q + 1], c.y); a1 += mulhi_vs(in[19 + 4 * q], c.y);
-            a0 += mulhi_vs(in[4 * q + 2], c.z); a1 += mulhi_vs(in[20 + 4 * q], c.z);
-            a0 += mulhi_vs(in[4 * q + 3], c.w); a1 += mulhi_vs(in[21 + 4 * q], c.w);
+            a0 += (uint32_t)mulhi_vs(in[4 * q], c.x);     a1 += (uint32_t)mulhi_vs(in[18 + 4 * q], c.x);
+            a0 += (uint32_t)mulhi_vs(in[4 * q + 1], c.y); a1 += (uint32_t)mulhi_vs(in[19 + 4 * q], c.y);
+            a0 += (uint32_t)mulhi_vs(in[4 * q + 2], c.z); a1 += (uint32_t)mulhi_vs(in[20 + 4 * q], c.z);
+            a0 += (uint32_t)mulhi_vs(in[4 * q + 3], c.w); a1 += (uint32_t)mulhi_vs(in[21 + 4 * q], c.w);
         }
-        x0[k * MD_ROW] = a0;
-        x1[k * MD_ROW] = a1;
+        x0[k * MD_ROW] = (int32_t)a0;
+        x1[k * MD_ROW] = (int32_t)a1;
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
     }
