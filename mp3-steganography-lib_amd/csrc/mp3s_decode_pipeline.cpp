@@ -1,8 +1,8 @@
 // C-ABI of the library (include/mp3s.h), part 2: MP3 streams in, PCM out -- the host front end, the device batch
 // (Huffman decode + transforms, chunked with a one-frame halo) and the entry points built on them.
-#include <sys/stat.h>
 #include <unistd.h>
 #include <cerrno>
+#include "block_plan.h"
 #include "mp3s_internal.h"
 
 // keep frames [first, first + count) of a parsed stream (its main data, side records, samples)
@@ -215,9 +215,10 @@ int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
     // ---- transforms in chunks of kDecodeChunk frames; a chunk that starts inside a stream re-runs one halo frame.
     //      Host layout = device layout plus one extra frame after every stream that ends in a bad header (D12): the
     //      reference appends that stream's last PCM frame once more.
-    std::vector<long> out_first(idx.size());
+    std::vector<StreamSpan> spans(idx.size());
+    for (size_t k = 0; k < idx.size(); k++) spans[k] = {first_of[k], m.parsed[idx[k]].n_frames, m.parsed[idx[k]].dup_last_frame != 0};
     long extra = 0;
-    for (size_t k = 0; k < idx.size(); k++) { out_first[k] = first_of[k] + extra; extra += m.parsed[idx[k]].dup_last_frame ? 1 : 0; }
+    const std::vector<long> out_first = out_first_of(spans, &extra);
     uint8_t *arena = nullptr;
     if (!d_keep) {
         if (!m.arena[nch].reserve(m.head_room + (size_t)(n + extra) * frame_bytes))
@@ -225,29 +226,21 @@ int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
         arena = m.arena[nch].data() + m.head_room;
     }
     if (!rc) rc = mp3s_dev_upload(c, d_hdr, hdr.data(), (size_t)n * sizeof(mp3s_frame_hdr));
-    for (long start = 0; start < n && !rc; start += kDecodeChunk) {
-        const int halo = (start && hdr[(size_t)start].stream_first < (uint32_t)start) ? 1 : 0;
-        const long first = start - halo;
-        const int cnt = (int)std::min<long>(kDecodeChunk, n - start) + halo;
-        rc = decode_transform_chunk(c, (const int16_t *)d_is, (const mp3s_granule_si *)d_si, (const mp3s_frame_hdr *)d_hdr, first, cnt, nch,
-                                    halo, out_format, d_pcm);
+    auto inside_stream = [&](long f) { return hdr[(size_t)f].stream_first < (uint32_t)f; };
+    if (!rc) rc = for_transform_groups(n, 0, inside_stream, [&](const TransformGroup &g) -> int {
+        if (const int e = decode_transform_chunk(c, (const int16_t *)d_is, (const mp3s_granule_si *)d_si, (const mp3s_frame_hdr *)d_hdr, g.start - g.halo,
+                                                 g.cnt, nch, g.halo, out_format, d_pcm))
+            return e;
         // copy out in runs that are contiguous on both sides (a run ends where a duplicated frame is inserted)
-        const long end = start + (cnt - halo);
-        for (long a = start; a < end && !rc;) {
-            size_t k = (size_t)(std::upper_bound(first_of.begin(), first_of.end(), a) - first_of.begin()) - 1;
-            long b = end;
-            for (size_t j = k; j < idx.size() && first_of[j] < end; j++)
-                if (m.parsed[idx[j]].dup_last_frame) { b = std::min<long>(end, first_of[j] + m.parsed[idx[j]].n_frames); break; }
-            if (b <= a) b = std::min<long>(end, a + 1);
-            const size_t dst = (size_t)(out_first[k] + (a - first_of[k])) * frame_bytes, bytes = (size_t)(b - a) * frame_bytes;
-            const uint8_t *src = (const uint8_t *)d_pcm + (size_t)(a - start) * frame_bytes;
-            if (d_keep) {
-                if (hipMemcpyAsync((uint8_t *)d_keep + dst, src, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-                    rc = fail(MP3S_E_HIP, "device copy failed");
-            } else rc = mp3s_dev_download(c, arena + dst, src, bytes);
-            a = b;
-        }
-    }
+        return for_copy_runs(spans, out_first, g.start, g.start + (g.cnt - g.halo), [&](const CopyRun &r) -> int {
+            const size_t dst = (size_t)r.dst_frame * frame_bytes, bytes = (size_t)r.count * frame_bytes;
+            const uint8_t *src = (const uint8_t *)d_pcm + (size_t)(r.src_frame - g.start) * frame_bytes;
+            if (!d_keep) return mp3s_dev_download(c, arena + dst, src, bytes);
+            if (hipMemcpyAsync((uint8_t *)d_keep + dst, src, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                return fail(MP3S_E_HIP, "device copy failed");
+            return MP3S_OK;
+        });
+    });
     for (size_t k = 0; k < idx.size() && !rc; k++) {
         const ParsedStream &p = m.parsed[idx[k]];
         if (p.dup_last_frame && p.n_frames > 0) {
@@ -265,6 +258,13 @@ int decode_group(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int nc
     }
     if (!d_keep) hipStreamSynchronize(c->stream);
     return rc;
+}
+
+// what a one-file call through the overlapped stages decoded, as the caller's record (the fields run_file does not fill stay as they are)
+static void decoded_from_run(const RunResult &r, mp3s_decoded *out)
+{
+    out->n_frames = (int32_t)r.n_frames; out->nch = r.nch; out->sampling_rate = r.sampling_rate; out->bit_rate = r.bit_rate;
+    out->n_bits = (int32_t)r.n_bits; out->n_rows = r.n_rows; out->pcm = r.pcm; out->bits = r.bits;
 }
 
 extern "C" {
@@ -385,12 +385,13 @@ int mp3s_decode_block_indexed(mp3s_ctx *c, const uint8_t *file, size_t len, cons
     if (out_format < 0 || out_format > 2) return fail(MP3S_E_ARG, "out_format=%d", out_format);
     // one frame in front of the block is decoded for its state and dropped: the IMDCT overlap and the synthesis fifo
     // reach back less than a frame (Frame.py:151-153, 81-92)
-    const int halo = first_frame > 0 ? 1 : 0;
+    // (how long the stream is and whether it repeats its last frame is not known here: the window is asked for as if the block ended such a
+    // stream, and front_end cuts both down to what the stream has)
+    const BlockWindow w = block_window((long)first_frame, (long)n_frames, (long)(first_frame + n_frames), true, true);
+    const int halo = w.halo;
     std::unique_ptr<mp3s_buf> b(new mp3s_buf());
-    b->multi.reset(new mp3s_multi());
-    mp3s_multi &m = *b->multi;
-    m.parsed.resize(1); m.scanned.resize(1); m.pcm.assign(1, nullptr); m.files.assign(1, {file, len});
-    m.window.assign(1, {(long)first_frame - halo, (long)n_frames + halo, true});
+    mp3s_multi &m = one_stream_multi(*b, file, len);
+    m.window.assign(1, {w.w0, w.n_win, w.with_dup});
     m.all_bits.resize(1);
     m.index = reinterpret_cast<const StreamIndex *>(index);
     int rc = front_end(m, 0);
@@ -420,8 +421,7 @@ int mp3s_decode_stream(mp3s_ctx *c, const uint8_t *file, size_t len, int out_for
         const int rc = run_file(c, file, len, kRunDecode, nullptr, 0, out_format, owner, &r);
         if (rc != kRunFallback) {
             if (rc) return rc;
-            out->n_frames = (int32_t)r.n_frames; out->nch = r.nch; out->sampling_rate = r.sampling_rate; out->bit_rate = r.bit_rate;
-            out->n_bits = (int32_t)r.n_bits; out->n_rows = r.n_rows; out->pcm = r.pcm; out->bits = r.bits;
+            decoded_from_run(r, out);
             return MP3S_OK;
         }
     }
@@ -441,8 +441,7 @@ int mp3s_decode_file(mp3s_ctx *c, const uint8_t *mp3, size_t len, mp3s_buf **own
 int mp3s_decode_file_fd(mp3s_ctx *c, const uint8_t *mp3, size_t len, int fd, mp3s_buf **owner, mp3s_file *out)
 {
     if (!c || !mp3 || !owner || !out || fd < 0) return fail(MP3S_E_ARG, "bad argument");
-    struct stat st;
-    c->sink_fd = fd; c->sink_done = 0; c->sink_base = 44; c->sink_early = fstat(fd, &st) == 0 && st.st_size == 0;
+    sink_begin(c, fd, 44);
     int rc = decode_file_impl(c, mp3, len, owner, out);
     c->sink_fd = -1;
     if (rc) return rc;
@@ -463,10 +462,8 @@ static int decode_file_impl(mp3s_ctx *c, const uint8_t *mp3, size_t len, mp3s_bu
     mp3s_decoded d;
     RunResult r;
     int rc = run_file(c, mp3, len, kRunDecode, nullptr, 0, MP3S_PCM_I16, &b, &r);   // chunks through the overlapped stages ...
-    if (rc == MP3S_OK) {
-        d.n_frames = (int32_t)r.n_frames; d.nch = r.nch; d.sampling_rate = r.sampling_rate; d.bit_rate = r.bit_rate;
-        d.n_bits = (int32_t)r.n_bits; d.n_rows = r.n_rows; d.pcm = r.pcm; d.bits = r.bits;
-    } else if (rc == kRunFallback) {                                                  // ... or one stage after the other
+    if (rc == MP3S_OK) decoded_from_run(r, &d);
+    else if (rc == kRunFallback) {                                                  // ... or one stage after the other
         c->sink_done = 0;
         rc = decode_streams_impl(c, &mp3, &len, 1, MP3S_PCM_I16, 64, &b, &d, nullptr);
     }

@@ -1,8 +1,8 @@
 // C-ABI of the library (include/mp3s.h), part 3: PCM in (from the host, or left in HBM by the decode pipeline), MP3 out
 // -- the encoder's device batch with its serial chains, and the file / message / block entry points built on it.
-#include <sys/stat.h>
 #include <unistd.h>
 #include <cerrno>
+#include "block_plan.h"
 #include "chain_resolve.h"
 
 // the stream as the device's chain check and selection see it (chain_in stays zero: enc_fill's to add)
@@ -599,6 +599,25 @@ extern "C++" int reencode_check(const ParsedStream &p, int *kbps_out)
     return MP3S_OK;
 }
 
+// the streams `idx` of m (stereo) decoded into device PCM that stays: rows_frames frames of int16 in the context's kPoolPcm0
+static int decode_kept(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, int64_t rows_frames, void **d_keep_out)
+{
+    if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
+    void *d_keep = c->grab(kPoolPcm0, (size_t)rows_frames * 2304 * 2);
+    if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
+    if (const int rc = decode_group(c, m, idx, 2, MP3S_PCM_I16, d_keep)) return rc;
+    *d_keep_out = d_keep;
+    return MP3S_OK;
+}
+
+// what a one-file call through the overlapped stages made, as the caller's record
+static void file_from_run(const RunResult &r, mp3s_file *out)
+{
+    std::memset(out, 0, sizeof *out);
+    out->data = r.mp3; out->len = r.mp3_len; out->kbps = r.kbps; out->sampling_rate = r.sampling_rate; out->channels = 2;
+    out->n_frames = (int32_t)r.n_frames; out->too_long = r.too_long; out->hide_offset = r.hide_offset;
+}
+
 // The front half of reencode_group (mp3s_internal.h): the streams as segments of an encode batch, decoded on the device into HBM.
 extern "C++" int reencode_decode(mp3s_ctx *c, mp3s_multi &m, const std::vector<int> &idx, const std::vector<std::vector<uint8_t>> &bits,
                                  std::vector<EncSeg> &segs, std::vector<std::vector<uint8_t>> &guess, void **d_keep_out, int64_t *rows_frames_out)
@@ -618,13 +637,9 @@ extern "C++" int reencode_decode(mp3s_ctx *c, mp3s_multi &m, const std::vector<i
         segs[k].hide = bits[idx[k]].data(); segs[k].n_hide = (int)bits[idx[k]].size();
         rows_frames += segs[k].n_frames;
     }
-    if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
-    void *d_keep = c->grab(kPoolPcm0, (size_t)rows_frames * 2304 * 2);
-    if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
-    const int rc = decode_group(c, m, idx, 2, MP3S_PCM_I16, d_keep);
-    if (rc) return rc;
-    *d_keep_out = d_keep; *rows_frames_out = rows_frames;
-    return MP3S_OK;
+    const int rc = decode_kept(c, m, idx, rows_frames, d_keep_out);
+    if (!rc) *rows_frames_out = rows_frames;
+    return rc;
 }
 
 // Decode the streams `idx` of m (stereo, one sampling rate and bitrate) on the device into HBM and encode them from
@@ -690,9 +705,7 @@ int mp3s_reencode_block_indexed(mp3s_ctx *c, const uint8_t *mp3, size_t len, con
     if (!c || !mp3 || !owner || !out || world <= 0 || rank < 0 || rank >= world || (rank == 0 && carry_in) || (rank > 0 && !carry_in))
         return fail(MP3S_E_ARG, "bad argument (rank 0 has no carry, every other rank has one)");
     std::unique_ptr<mp3s_buf> top(new mp3s_buf());
-    top->multi.reset(new mp3s_multi());
-    mp3s_multi &m = *top->multi;
-    m.parsed.resize(1); m.scanned.resize(1); m.pcm.assign(1, nullptr); m.files.assign(1, {mp3, len});
+    mp3s_multi &m = one_stream_multi(*top, mp3, len);
     const StreamIndex *ix = reinterpret_cast<const StreamIndex *>(index);
     const bool ranged = ix && index_info(ix).gpu_ok;      // scan the block alone; otherwise the whole file, then cut
     int rc = MP3S_OK;
@@ -720,36 +733,31 @@ int mp3s_reencode_block_indexed(mp3s_ctx *c, const uint8_t *mp3, size_t len, con
     if (bits.size() > 0x7fffffff) return fail(MP3S_E_ARG, "message too long");
     // blocks of PCM frames; the frame the decoder repeats after a bad header (D12) is the stream's last PCM frame
     const long n = p.n_frames, total = n + (p.dup_last_frame ? 1 : 0);
-    const long base = total / world, rem = total % world;
-    const long first = rank * base + std::min<long>(rank, rem), count = base + (rank < rem ? 1 : 0);
+    const BlockShare share = block_share(total, rank, world);
+    const long first = share.first, count = share.count;
     std::memset(out, 0, sizeof *out);
     out->total_frames = total; out->first_frame = first; out->n_frames = count; out->is_last = first + count == total;
     out->file.kbps = kbps; out->file.sampling_rate = samplerate; out->file.channels = 2;
     if (count == 0) { m.files.clear(); *owner = top.release(); return MP3S_OK; }
-    const int lead = first > 0 ? 1 : 0;                   // PCM in front of the block, for the encoder's filter state
-    const int halo = first - lead > 0 ? 1 : 0;            // a frame in front of that, for the decoder's
-    const long w0 = first - lead - halo, w1 = std::min(first + count, n);
-    const bool with_dup = first + count == total && p.dup_last_frame;
-    m.window.assign(1, {w0, w1 - w0, with_dup});
+    // PCM in front of the block for the encoder's filter state (lead), a frame in front of that for the decoder's (halo)
+    const BlockWindow w = block_window(first, count, n, p.dup_last_frame != 0, false);
+    m.window.assign(1, {w.w0, w.n_win, w.with_dup});
     if (ranged) {
         m.index = ix;
         rc = front_end(m, 0);
         m.index = nullptr;
         if (rc) return fail(rc, "malformed or unsupported MP3 stream");
-    } else cut_window(p, m.scanned[0], w0, w1 - w0);
-    if (!with_dup) p.dup_last_frame = 0;
-    const int64_t rows_frames = (w1 - w0) + (with_dup ? 1 : 0);
-    if (hipSetDevice(c->device) != hipSuccess) return fail(MP3S_E_HIP, "hipSetDevice failed");
-    void *d_keep = c->grab(kPoolPcm0, (size_t)rows_frames * 2304 * 2);
-    if (!d_keep) return fail(MP3S_E_NOMEM, "hipMalloc failed for %lld frames of PCM", (long long)rows_frames);
-    rc = decode_group(c, m, std::vector<int>{0}, 2, MP3S_PCM_I16, d_keep);
+    } else cut_window(p, m.scanned[0], w.w0, w.n_win);
+    if (!w.with_dup) p.dup_last_frame = 0;
+    void *d_keep = nullptr;
+    rc = decode_kept(c, m, std::vector<int>{0}, w.n_win + (w.with_dup ? 1 : 0), &d_keep);
     if (rc) return rc;
     std::vector<EncSeg> segs(1);
     EncSeg &s = segs[0];
     s.n_frames = (int)count; s.hide = bits.data(); s.n_hide = (int)bits.size();
-    s.lead = lead; s.first_frame = first; s.last = out->is_last != 0; s.carry_in = carry_in;
+    s.lead = w.lead; s.first_frame = first; s.last = out->is_last != 0; s.carry_in = carry_in;
     std::unique_ptr<mp3s_buf> part(new mp3s_buf());
-    rc = encode_batch(c, nullptr, (const int16_t *)d_keep + (size_t)halo * 2304, segs, samplerate, kbps, part.get(), nullptr, false);
+    rc = encode_batch(c, nullptr, (const int16_t *)d_keep + (size_t)w.halo * 2304, segs, samplerate, kbps, part.get(), nullptr, false);
     if (rc) return rc;
     out->carry_out = s.carry_out; out->carry_used = s.carry_used ? 1 : 0;
     out->file.data = part->mp3 + s.mp3_off; out->file.len = s.mp3_len; out->file.n_frames = (int32_t)count;
@@ -775,9 +783,7 @@ int mp3s_hide_message_chunked(mp3s_ctx *c, const uint8_t *mp3, size_t len, const
         c->opt[MP3S_OPT_CHUNK_FRAMES] = keep;
         if (rr != kRunFallback) {
             if (rr) return rr;
-            std::memset(out, 0, sizeof *out);
-            out->data = r.mp3; out->len = r.mp3_len; out->kbps = r.kbps; out->sampling_rate = r.sampling_rate; out->channels = 2;
-            out->n_frames = (int32_t)r.n_frames; out->too_long = r.too_long; out->hide_offset = r.hide_offset;
+            file_from_run(r, out);
             return MP3S_OK;
         }
     }
@@ -821,9 +827,7 @@ static int reencode(mp3s_ctx *c, const uint8_t *mp3, size_t len, const uint8_t *
     const int rc = run_file(c, mp3, len, hide ? kRunHide : kRunClear, msg, n_msg, MP3S_PCM_I16, owner, &r);
     if (rc != kRunFallback) {
         if (rc) return rc;
-        std::memset(out, 0, sizeof *out);
-        out->data = r.mp3; out->len = r.mp3_len; out->kbps = r.kbps; out->sampling_rate = r.sampling_rate; out->channels = 2;
-        out->n_frames = (int32_t)r.n_frames; out->too_long = r.too_long; out->hide_offset = r.hide_offset;
+        file_from_run(r, out);
         return MP3S_OK;
     }
     c->sink_done = 0;                                  // (mp3s_*_fd: what the chunks wrote is written again from the result of the other path)
@@ -836,8 +840,7 @@ static int reencode(mp3s_ctx *c, const uint8_t *mp3, size_t len, const uint8_t *
 static int reencode_fd(mp3s_ctx *c, const uint8_t *mp3, size_t len, const uint8_t *msg, size_t n_msg, bool hide, int fd, mp3s_file *out)
 {
     mp3s_buf *owner = nullptr;
-    struct stat st;
-    c->sink_fd = fd; c->sink_done = 0; c->sink_base = 0; c->sink_early = fstat(fd, &st) == 0 && st.st_size == 0;
+    sink_begin(c, fd, 0);
     int rc = reencode(c, mp3, len, msg, n_msg, hide, &owner, out);
     c->sink_fd = -1;
     if (rc == MP3S_OK) {

@@ -3,6 +3,7 @@
 // part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -282,6 +283,15 @@ struct mp3s_buf {
     mp3s_gr_out *gr_out = nullptr;
 };
 
+// a result owner with the batch record of ONE borrowed stream (the block calls): b.multi made, stream 0 = (file, len), nothing parsed yet
+inline mp3s_multi &one_stream_multi(mp3s_buf &b, const uint8_t *file, size_t len)
+{
+    b.multi.reset(new mp3s_multi());
+    mp3s_multi &m = *b.multi;
+    m.parsed.resize(1); m.scanned.resize(1); m.pcm.assign(1, nullptr); m.files.assign(1, {file, len});
+    return m;
+}
+
 // MP3S_TRACE=1: phase timings of the file pipelines on stderr
 inline bool trace_on() { static const bool on = getenv("MP3S_TRACE") != nullptr; return on; }
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -296,6 +306,13 @@ inline size_t pwrite_all(int fd, const uint8_t *src, size_t n, size_t at)
         done += (size_t)w;
     }
     return done;
+}
+// (mp3s_*_fd) arm the context's sink: the result goes to fd, behind `base` bytes the caller writes itself (the WAV header's place); nothing is
+// written yet.  Chunks go to the file before the call has succeeded only if it is empty now.
+inline void sink_begin(mp3s_ctx *c, int fd, size_t base)
+{
+    struct stat st;
+    c->sink_fd = fd; c->sink_done = 0; c->sink_base = base; c->sink_early = fstat(fd, &st) == 0 && st.st_size == 0;
 }
 
 // ---------------------------------------------------------------- the frame of the list-of-files calls (file_lists.cpp)

@@ -7,6 +7,7 @@
 #include <condition_variable>
 #include <deque>
 
+#include "block_plan.h"
 #include "mp3s_internal.h"
 #include "pipe_pack.h"
 
@@ -60,9 +61,8 @@ struct Chunk {
 static inline void chunk_window(Chunk &k, const FrameRef *refs, long first, long count, bool last, const uint8_t *file, size_t len)
 {
     k.on = true; k.refs = refs; k.first = first; k.count = count; k.last = last; k.file = file; k.file_len = len;
-    k.lead = !k.decode && first > 0 ? 1 : 0;
-    k.halo = first - k.lead > 0 ? 1 : 0;
-    k.w0 = first - k.lead - k.halo; k.n_win = count + k.lead + k.halo;
+    const BlockWindow w = block_window(first, count, first + count, false, k.decode);   // (a walked stream's chunks end inside it and repeat no frame)
+    k.lead = w.lead; k.halo = w.halo; k.w0 = w.w0; k.n_win = w.n_win;
     const uint32_t lo = refs[(size_t)k.w0].file_off;
     k.image_lo = first == 0 ? 0 : (lo > kImageLead ? lo - kImageLead : 0);
     const FrameRef &lr = refs[(size_t)(first + count - 1)];

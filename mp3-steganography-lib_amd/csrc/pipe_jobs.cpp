@@ -283,8 +283,8 @@ bool prepare_block(mp3s_pipe *P, Job &j, Slot &s)
     const long n = walk_whole(file, len, j.refs, w);
     if (n <= 0 || w.dup_last) return false;
     if (!admit_stream(j, 0, w.nch, w.sampling_rate, w.bit_rate, n, false)) return false;
-    const long base = n / j.world, rem = n % j.world;
-    const long first = j.rank * base + std::min<long>(j.rank, rem), count = base + (j.rank < rem ? 1 : 0);
+    const BlockShare share = block_share(n, j.rank, j.world);
+    const long first = share.first, count = share.count;
     std::memset(&j.blk, 0, sizeof j.blk);
     j.blk.total_frames = n; j.blk.first_frame = first; j.blk.n_frames = count; j.blk.is_last = first + count == n;
     j.blk.file.kbps = j.kbps; j.blk.file.sampling_rate = w.sampling_rate; j.blk.file.channels = 2;
@@ -497,17 +497,14 @@ int issue_back(mp3s_pipe *P, Job &j, Slot &s, bool inputs_later, bool defer_down
         return k > 0 && j.stream_first[k - 1] < (uint32_t)f;
     };
     const int halo0 = ck.on ? ck.halo : 0;
-    for (long start = halo0; start < n; start += kDecodeChunk) {
-        const int halo = start == halo0 ? halo0 : (inside_stream(start) ? 1 : 0);
-        const int cnt = (int)std::min<long>(kDecodeChunk, n - start) + halo;
+    const int groups_rc = for_transform_groups(n, halo0, inside_stream, [&](const TransformGroup &g) {
         // (the last group's last dispatch signals e_dec itself where it can: a record is a packet of its own in the queue, 7-8 us of nothing
         //  between two kernels: tools/timeline.sh)
-        const bool last_group = start + kDecodeChunk >= n;
-        const int rc = decode_transform_chunk(c, (const int16_t *)v.d_is, (const mp3s_granule_si *)v.d_si, d_dechdr, start - halo, cnt, v.nch, halo,
-                                              v.out_format, (uint8_t *)v.d_keep + (size_t)(start - halo0) * v.frame_elems * v.esz, ds,
-                                              last_group && (c->opt[MP3S_OPT_PIPE_SIGNALS] & 1) ? P->e_dec[set] : nullptr);
-        if (rc) return rc;
-    }
+        return decode_transform_chunk(c, (const int16_t *)v.d_is, (const mp3s_granule_si *)v.d_si, d_dechdr, g.start - g.halo, g.cnt, v.nch, g.halo,
+                                      v.out_format, (uint8_t *)v.d_keep + (size_t)(g.start - halo0) * v.frame_elems * v.esz, ds,
+                                      g.last && (c->opt[MP3S_OPT_PIPE_SIGNALS] & 1) ? P->e_dec[set] : nullptr);
+    });
+    if (groups_rc) return groups_rc;
     if (n <= halo0 || !(c->opt[MP3S_OPT_PIPE_SIGNALS] & 1)) HIPCHK(hipEventRecord(P->e_dec[set], ds));     // (no group ran: nothing has signalled it)
     if (trace_on()) fprintf(stderr, "mp3s:   decode transforms queued %.3f ms after the job's start\n", now_ms() - t_issue0);
     P->dec_used[set] = true;

@@ -27,6 +27,7 @@ _PAST_MESSAGE = 0x3fffffff
 
 def shard_frames(n_frames, rank, world):
     """contiguous blocks, sizes differing by at most one: (first, count) of `rank`"""
+    # (the same rule in C++, where the block calls and the pipe's block jobs cut a stream: block_share of csrc/block_plan.h)
     base, rem = divmod(int(n_frames), int(world))
     return rank * base + min(rank, rem), base + (1 if rank < rem else 0)
 

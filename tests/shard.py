@@ -1,5 +1,6 @@
 """Frame sharding used by multi-GPU drivers: contiguous blocks, 1-frame halo in front of every block but the first
-(the decoder/encoder state reaches back less than one frame)."""
+(the decoder/encoder state reaches back less than one frame).  The library's own statement of the share is
+block_share of csrc/block_plan.h; tests/test_block_plan.py holds this one against it."""
 
 
 def shard_frames(n_frames, rank, world):
