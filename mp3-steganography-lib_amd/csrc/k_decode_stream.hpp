@@ -6,9 +6,11 @@
 // The reference runs imdct -> __frequency_inversion -> synth_filter_bank on one array (Frame.py:282-284).  Here that array never exists:
 // a wave walks `run` consecutive granules with lane = (channel, subband) from the first stage to the last, and what the stages hand to
 // each other stays in the wave's registers.
-//   * IMDCT as in k_dec_imdct<true>: 18 lines per lane, twiddle rows as scalar operands, the mirrored rows by sign, fused multiply-adds;
-//     the overlap tail of a granule waits for the next one in the wave's own 9 KB of LDS.  Its 18 outputs are the subband's samples of
-//     the granule's 18 time slots: S[p], one register pair per slot.
+//   * IMDCT of a long block: 18 lines per lane, the 36 outputs as the 18 values of a DCT-IV and their mirror images by sign.  The DCT-IV
+//     in two halves -- nine rotations, the sums and differences of the rotated pairs (k, 8 - k), ten stages of two four-term sums that
+//     start from their centre term --, factors as scalar operands, fused multiply-adds (derivation and error bound: mp3s_tables.cpp).
+//     Short blocks in the reference's order.  The overlap tail of a granule waits for the next one in the wave's own 9 KB of LDS.  The
+//     18 outputs are the subband's samples of the granule's 18 time slots: S[p], one register pair per slot.
 //   * Matrixing of slot p ACROSS the lanes: X[k] = sum_j S[j] cos((2j+1) k pi/64) = sum_{j<16} (S[j] -+ S[31-j]) cos(..) (k odd: the
 //     differences, k even: the sums).  A lane gets its mirror subband's sample by ds_swizzle (xor 31), forms its difference (subbands
 //     0..15: DPP row 0 / 2 of the wave) or sum (16..31: row 1 / 3), and every lane of a row sums 16 products of ITS row's 16 values with
@@ -48,6 +50,22 @@ namespace mp3s {
 
 constexpr int ST_WAVES = 4;                 // waves per workgroup; they share the staged tables and nothing else
 constexpr int ST_P43_N = 512;
+typedef double dvec4s __attribute__((ext_vector_type(4), aligned(8)));   // four factors of a table row, wherever in the row they start
+
+// A frame's header record as its two dwords -- one scalar load; read field by field the byte fields arrive as vector loads, and what
+// depends on them (the line map's address) waits for every vector load in flight.
+struct StHdr {
+    uint32_t w, stream_first;
+    __device__ __forceinline__ int sr_idx() const { return (int)(w & 0xffu); }
+    __device__ __forceinline__ int ms_stereo() const { return (int)((w >> 16) & 0xffu); }
+};
+static_assert(sizeof(mp3s_frame_hdr) == 8 && offsetof(mp3s_frame_hdr, sr_idx) == 0 && offsetof(mp3s_frame_hdr, ms_stereo) == 2 && offsetof(mp3s_frame_hdr, stream_first) == 4,
+              "StHdr reads mp3s_frame_hdr as two dwords");
+__device__ __forceinline__ StHdr st_hdr(const mp3s_frame_hdr *__restrict__ hdr, int frame)
+{
+    const uint2 d = reinterpret_cast<const uint2 *>(hdr)[frame];
+    return StHdr{d.x, d.y};
+}
 
 struct StShared {
     double pow2q[POW2Q_N];                  // (as DecShared: random per-lane reads go to LDS)
@@ -125,25 +143,72 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
     const unsigned long long ck_start = __builtin_readcyclecounter();
     unsigned long long ck_req = 0, ck_rows = 0, ck_syn = 0, ck_setup = 0;
 #endif
-    for (int i = threadIdx.x; i < POW2Q_N; i += blockDim.x) sh.pow2q[i] = c_tab.pow2q[i];
-    if (threadIdx.x < POW2H_N) sh.pow2h[threadIdx.x] = c_tab.pow2h[threadIdx.x];
-    if (threadIdx.x < 144) (&sh.win[0][0])[threadIdx.x] = (&c_tab.sine_block[0][0])[threadIdx.x];
-    for (int i = threadIdx.x; i < 2 * ST_P43_N; i += blockDim.x) {
-        const int x = i - ST_P43_N;
-        sh.p43[i] = x < 0 ? -c_tab.pow43[-x] : c_tab.pow43[x];
-    }
-    // the lanes' constants of the synthesis: 16 cosines (as the holder of X[k]: k = 2 (sb & 15) + 1 in the rows of the differences, 2 (sb & 15)
-    // in the rows of the sums) and 16 taps (as output i = sb)
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) {
-        sh.cx[i >> 5][i & 31] = c_tab.stream_cx[i & 31][i >> 5];
-        sh.wt[i >> 5][i & 31] = c_tab.stream_taps[F32 ? 0 : 1][i & 31][i >> 5];
-    }
-    __syncthreads();
     const int ga = (xcd_tile() * ST_WAVES + wave) * run;       // this wave's granules: ga .. ga + run - 1
-    if (ga >= n_granules) return;                                // (whole waves; no barrier behind this line)
-
+    // Set-up.  Every wave of the launch starts at the launch's start (one round of waves), so what stands here is on the kernel's critical
+    // path once: every load of it is in flight before the first is waited for, the run's own first inputs among them -- the frame headers
+    // the run can start under (scalar), then the tables' loads all together, then (the headers are here) the line map and the first
+    // granule's lines and side records, then the tables' LDS writes behind counted waits and the workgroup's one barrier.  A wave behind
+    // the batch asks at the last granule's addresses and leaves behind the barrier.
+    const int gq = ga < n_granules ? ga : n_granules - 1;
+    const StHdr fh_a = st_hdr(hdr, gq >> 1), fh_b = st_hdr(hdr, gq >= 2 ? (gq - 2) >> 1 : 0);    // the frames of granules ga, ga - 1 | ga - 1, ga - 2
     const int ch = lane >> 5, sb = lane & 31;
     const bool live = ch < NCH;
+    int gi0, sr_map;
+    StHdr fh;
+    uint32_t mwl[5];
+    GranIn next_in;
+    {
+        constexpr int NT = ST_WAVES * 64, NQ = (POW2Q_N + NT - 1) / NT, NP = 2 * ST_P43_N / NT, NC = 512 / NT;
+        static_assert(POW2H_N <= NT && 144 <= NT && 2 * ST_P43_N % NT == 0 && 512 % NT == 0, "one table element per thread and trip");
+        const int t = threadIdx.x;
+        double rq[NQ], rp[NP], rc[NC], rw[NC];
+        // (every index clamped into its table: no branch stands around a load; the writes are predicated)
+#pragma unroll
+        for (int j = 0; j < NQ; j++) rq[j] = c_tab.pow2q[t + j * NT < POW2Q_N ? t + j * NT : POW2Q_N - 1];
+        const double rh = c_tab.pow2h[t < POW2H_N ? t : POW2H_N - 1];
+        const double rs = (&c_tab.sine_block[0][0])[t < 144 ? t : 143];
+#pragma unroll
+        for (int j = 0; j < NP; j++) {
+            const int x = t + j * NT - ST_P43_N;
+            rp[j] = c_tab.pow43[x < 0 ? -x : x];
+        }
+        // the lanes' constants of the synthesis: 16 cosines (as the holder of X[k]: k = 2 (sb & 15) + 1 in the rows of the differences, 2 (sb & 15)
+        // in the rows of the sums) and 16 taps (as output i = sb)
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            const int i = t + j * NT;
+            rc[j] = c_tab.stream_cx[i & 31][i >> 5];
+            rw[j] = c_tab.stream_taps[F32 ? 0 : 1][i & 31][i >> 5];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the stream the run starts in begins at granule s_a of the launch: nothing in front of it primes the run
+        const int s_a = fh_a.stream_first > (uint32_t)sf_base ? (int)(fh_a.stream_first - (uint32_t)sf_base) * 2 : 0;
+        // priming: the granule in front of the run (history of the synthesis) and the tail of the one before, as far as they belong to the stream
+        gi0 = gq - 2 >= s_a ? -2 : (gq - 1 >= s_a ? -1 : 0);
+        fh = ((gq + gi0) >> 1) == (gq >> 1) ? fh_a : fh_b;
+        // the line map of long blocks (scalefactor band of each of the lane's 18 lines) depends on the sample rate alone: kept across granules
+        sr_map = fh.sr_idx() < 3 ? fh.sr_idx() : 0;
+#pragma unroll
+        for (int k = 0; k < 5; k++) mwl[k] = reinterpret_cast<const uint32_t *>(c_tab.rq_map[sr_map][0][sb])[k];
+        next_in = dec_fetch(is, si, gq + gi0, NCH, lane);
+        // (the order of the requests is the point of this block: the tables' loads above, the run's own below, then the writes)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < NQ; j++) if (t + j * NT < POW2Q_N) sh.pow2q[t + j * NT] = rq[j];
+        if (t < POW2H_N) sh.pow2h[t] = rh;
+        if (t < 144) (&sh.win[0][0])[t] = rs;
+#pragma unroll
+        for (int j = 0; j < NP; j++) sh.p43[t + j * NT] = t + j * NT < ST_P43_N ? -rp[j] : rp[j];
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            const int i = t + j * NT;
+            sh.cx[i >> 5][i & 31] = rc[j];
+            sh.wt[i >> 5][i & 31] = rw[j];
+        }
+    }
+    __syncthreads();
+    if (ga >= n_granules) return;                                // (whole waves; no barrier behind this line)
+
     const uint32_t sgn_odd = (sb & 1) ? 0x80000000u : 0u;       // frequency inversion (Frame.py:629-631): odd slots of odd subbands
     auto flip = [&](double x) { return __hiloint2double(__double2hiint(x) ^ (int)sgn_odd, __double2loint(x)); };
     // ---- where the lane's A and B come from (as output i = sb)
@@ -166,20 +231,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
 #pragma unroll
     for (int i = 0; i < 18; i++) acc[i] = 0.0;
     double gm1 = 0.0, gm2 = 0.0;                                // G of the two granules in front (this lane's channel)
-    // the stream the run starts in begins at granule s_a of the launch: nothing in front of it primes the run
-    const int s_a = [&] { const uint32_t sf = hdr[ga >> 1].stream_first; return sf > (uint32_t)sf_base ? (int)(sf - (uint32_t)sf_base) * 2 : 0; }();
     bool fresh = true;                                          // the tail in LDS and the running sums are to be cleared before the next granule
-    GranIn next_in = {};
-    bool have_next = false;
-
-    // priming: the granule in front of the run (history of the synthesis) and the tail of the one before, as far as they belong to the stream
-    const int gi0 = ga - 2 >= s_a ? -2 : (ga - 1 >= s_a ? -1 : 0);
-    mp3s_frame_hdr fh = hdr[(ga + gi0) >> 1];
-    // the line map of long blocks (scalefactor band of each of the lane's 18 lines) depends on the sample rate alone: kept across granules
-    int sr_map = fh.sr_idx < 3 ? fh.sr_idx : 0;
-    uint32_t mwl[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) mwl[k] = reinterpret_cast<const uint32_t *>(c_tab.rq_map[sr_map][0][sb])[k];
 #if MP3S_ST_CLOCKS
     ck_setup = __builtin_readcyclecounter() - ck_start;
 #endif
@@ -191,10 +243,10 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
         const unsigned long long ck_a = __builtin_readcyclecounter();
 #endif
         const int first_gran = fh.stream_first > (uint32_t)sf_base ? (int)(fh.stream_first - (uint32_t)sf_base) * 2 : 0;
-        const int sr = fh.sr_idx < 3 ? fh.sr_idx : 0;
-        const bool ms = fh.ms_stereo != 0;
+        const int sr = fh.sr_idx() < 3 ? fh.sr_idx() : 0;
+        const bool ms = fh.ms_stereo() != 0;
         // (the next granule's frame header: a scalar load whose latency passes under this granule)
-        fh = hdr[(g + 1 < n_granules ? g + 1 : g) >> 1];
+        fh = st_hdr(hdr, (g + 1 < n_granules ? g + 1 : g) >> 1);
         if (g == first_gran) fresh = true;                      // Frame.py:234-235: prev_samples and the fifo start as zeros
         if (fresh) {
 #pragma unroll
@@ -213,7 +265,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
         // ---- requantise, MS stereo (dec_requant_ms), then reorder | alias reduction without an exchange buffer
         double v[18];
         int bt, cse;
-        const GranIn in = have_next ? next_in : dec_fetch(is, si, g, NCH, lane);
+        const GranIn in = next_in;                             // (asked for by the set-up or under the granule in front)
         // The common granule -- long blocks in every channel, no value beyond the small |is|^(4/3) table -- without a trip to memory: the
         // side records' fields from the registers they arrived in (lane d of the first 36 holds dword d: v_readlane for the two
         // head dwords of a channel, one ds_bpermute for a lane's scalefactor byte), the line map kept from the granule before,
@@ -368,13 +420,17 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
             //      DCT-IV of the 18 lines: y[n] = sum_k v[k] cos((2n+1)(2k+1) pi/72), rows 0..8 = y[9..17], rows 18..26 = -y[8..0].  In two
             //      halves (DevTables::imdct_rot / imdct_pq, derivation and error bound in mp3s_tables.cpp): nine rotations of the pairs
             //      (v[k], v[17-k]) into (p, q), then ten stages m of two nine-term sums P[m], Q[m] that give y[2m] = P + Q and
-            //      y[2m-1] = P - Q -- 236 multiply-adds where the mirrored rows took 324.  Stages 9..5 give the rows that read the old tail,
-            //      stages 4..0 the rows that write the new one.  A stage's 18 factors (scalar cache), its rows' window factors and tail
-            //      values (LDS) are asked for one stage ahead, the wait for them at the TOP of a stage (k_dec_imdct).
+            //      y[2m-1] = P - Q.  The nine terms of a sum are four pairs (k, 8 - k) with factors equal up to the sign (-1)^m and a
+            //      centre term that is 0 or +-1: with the sums and differences of the pairs formed once behind the rotations (16
+            //      additions), a stage is eight multiply-adds -- 36 + 16 + 72 operations where the nine-term sums took 236 and the
+            //      mirrored rows 324.  Stages 9..5 give the rows that read the old tail, stages 4..0 the rows that write the new one.  A
+            //      stage's eight factors (scalar cache), its rows' window factors and tail values (LDS) are asked for one stage ahead,
+            //      the wait for them at the TOP of a stage (k_dec_imdct).
             const double *wl = sh.win[bt];
-            double p[9], q[9];
+            double ap[4], dp[4], aq[4], dq[4], p4, q4;
             {
                 const Row18s r = load_row18s(tab.imdct_rot, 0);
+                double p[9], q[9];
 #pragma unroll
                 for (int k = 0; k < 9; k++) {
                     const double c = 2 * k < 8 ? r.a[2 * k] : (2 * k < 16 ? r.b[2 * k - 8] : r.c[2 * k - 16]);
@@ -382,13 +438,21 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
                     p[k] = __builtin_fma(v[17 - k], sn, v[k] * c);
                     q[k] = __builtin_fma(v[17 - k], c, -(v[k] * sn));
                 }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    ap[k] = p[k] + p[8 - k]; dp[k] = p[k] - p[8 - k];
+                    aq[k] = q[k] + q[8 - k]; dq[k] = q[k] - q[8 - k];
+                }
+                p4 = p[4]; q4 = q[4];
             }
-            struct StageIn { Row18s c; double w[4], t[4]; };
+            struct StageIn { dvec4s c, s; double w[4], t[4]; };
             // rows of stage m: the one of y[2m] first (none for m = 9), then the one of y[2m-1] (none for m = 0)
             auto stage_in = [&](auto mc) {
                 constexpr int m = decltype(mc)::value;
                 StageIn in;
-                in.c = load_row18s(tab.imdct_pq, m);
+                // (the first four cosines and the first four sines of the stage's row of 18: the other factors are these up to sign, 0 or +-1)
+                in.c = *reinterpret_cast<const dvec4s *>(tab.imdct_pq[m]);
+                in.s = *reinterpret_cast<const dvec4s *>(tab.imdct_pq[m] + 9);
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const int n = h == 0 ? 2 * m : 2 * m - 1;
@@ -407,13 +471,16 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
             };
             auto stage = [&](auto mc, const StageIn &in) {
                 constexpr int m = decltype(mc)::value;
-                double P = 0.0, Q = 0.0;
+                // even m: the cosines of k and 8 - k are equal, the sines opposite, the centre terms cos(m pi/2) p[4] = +-p[4] and 0;
+                // odd m: the cosines opposite, the sines equal, the centre terms 0 and sin(m pi/2) q[4] = +-q[4].  A sum starts from its
+                // centre term: four fused multiply-adds each.
+                constexpr bool even = (m & 1) == 0;
+                double P = even ? ((m >> 1) & 1 ? -p4 : p4) : 0.0;
+                double Q = even ? 0.0 : ((m >> 1) & 1 ? -q4 : q4);
 #pragma unroll
-                for (int k = 0; k < 9; k++) {
-                    const double cp = k < 8 ? in.c.a[k] : in.c.b[0];
-                    const double cq = k < 7 ? in.c.b[1 + k] : in.c.c[k - 7];
-                    if (m != 9) P = __builtin_fma(p[k], cp, P);          // (P[9] = 0: its factors are zeros)
-                    if (m != 0) Q = __builtin_fma(q[k], cq, Q);          // (Q[0] = 0)
+                for (int k = 0; k < 4; k++) {
+                    if (m != 9) P = __builtin_fma(even ? ap[k] : dp[k], in.c[k], P);     // (P[9] = 0: its factors are zeros)
+                    if (m != 0) Q = __builtin_fma(even ? dq[k] : aq[k], in.s[k], Q);     // (Q[0] = 0)
                 }
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
@@ -499,8 +566,7 @@ __global__ __launch_bounds__(ST_WAVES * 64, 2) void k_dec_stream(
             for (int i = 0; i < 6; i++) tl[i * 64] = tn[i];
         }
         // the next granule's lines and side records: asked for here, behind the rows (their registers are wanted there), under the synthesis
-        have_next = gi + 1 < run && g + 1 < n_granules;
-        if (have_next) next_in = dec_fetch(is, si, g + 1, NCH, lane);
+        if (gi + 1 < run && g + 1 < n_granules) next_in = dec_fetch(is, si, g + 1, NCH, lane);
 #if MP3S_ST_CLOCKS
         const unsigned long long ck_c = __builtin_readcyclecounter();
         ck_rows += ck_c - ck_b;

@@ -191,12 +191,22 @@ void build()
         //     p[k] = x cos a + x' sin a,   q[k] = -x sin a + x' cos a                                   (9 rotations)
         //     P[m] = sum_k p[k] cos(m (2k+1) pi/18),   Q[m] = sum_k q[k] sin(m (2k+1) pi/18),  m = 0..9  (P[9] = Q[0] = 0)
         //     y[2m] = P[m] + Q[m],   y[2m-1] = P[m] - Q[m]
-        // (the angle-addition formulas for (4m +- 1) a; checked against the direct sums in tests/test_tables.py): 236 instead of 324
-        // multiply-adds per subband.  Its distance from the TRUE sums, factors rounded once (<= u each), a product and a fused
-        // multiply-add per rotation, nine fused multiply-adds per sum, one addition:
+        // (the angle-addition formulas for (4m +- 1) a; checked against the direct sums in tests/test_tables.py).  The nine terms of a
+        // sum are four pairs and a centre: with t = m (2k+1) pi/18, cos(m pi - t) = (-1)^m cos t and sin(m pi - t) = -(-1)^m sin t are
+        // the factors of term 8 - k, and the centre's are cos(m pi/2), sin(m pi/2): 0 or +-1.  So, over k < 4,
+        //     m even:  P[m] = (-1)^(m/2) p[4] + sum (p[k] + p[8-k]) cos t,       Q[m] = sum (q[k] - q[8-k]) sin t
+        //     m odd:   P[m] = sum (p[k] - p[8-k]) cos t,                         Q[m] = (-1)^((m-1)/2) q[4] + sum (q[k] + q[8-k]) sin t
+        // which is what the kernel computes (tests/test_imdct_split_sums.py): the 16 sums and differences once, each sum four fused
+        // multiply-adds onto its centre term (or onto zero) -- 124 operations per subband where the nine-term sums took 236 and the
+        // mirrored rows 324.  Its distance from the TRUE sums, factors rounded once (<= u each), a product and a fused multiply-add per
+        // rotation, one rounded addition in front of each product of a sum, four fused multiply-adds per sum (the centre term enters
+        // exactly; its true factor is the integer), one addition of P and Q:
         //     |dp| <= 3.01 u (|x| + |x'|),  sum_k (|p| + |q|) <= sqrt2 B (1 + 4u),
-        //     |dP| <= (g9 + u) sum |p| + sum |dp|,  |dy| <= |dP| + |dQ| + u (sum |p| + sum |q|)  <=  ((g9 + 2u) sqrt2 + 6.02 u) B  <  22 u B
-        // and the reference's X from the true sums: g18 B for its own additions + dC B, dC = max |C[i][k] - cos((2i+19)(2k+1) pi/72)| of
+        //     |d(p[k] +- p[8-k])| <= u (|p[k]| + |p[8-k]|) + |dp[k]| + |dp[8-k]|,
+        //     |dP| <= (g4 + u + u) sum |p| + sum |dp|      (g4: the four additions of the sum; u: a factor; u: the addition in front),
+        //     |dy| <= |dP| + |dQ| + u (sum |p| + sum |q|)  <=  ((g4 + 3u) sqrt2 + 6.02 u) B  <  16 u B
+        // -- below the 22 u B of the nine-term sums ((g9 + 2u) sqrt2 + 6.02 u) this constant was set for, which therefore stays.
+        // The reference's X from the true sums: g18 B for its own additions + dC B, dC = max |C[i][k] - cos((2i+19)(2k+1) pi/72)| of
         // its table (arguments rounded before the cosine: measured in long double).  So |Y - X| <= (g18 + dC + 22u) B; window factor and
         // overlap-add as above.  kappa covers both routes (k_dec_imdct<true>, k_dec_fixup's callers keep the mirrored sums).
         long double dC = 0;
