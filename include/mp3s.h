@@ -1226,6 +1226,81 @@ int mp3s_pcm_batch_encode_at(mp3s_ctx *ctx, const void *d_in, int n_items, int i
                              int in_rate, int mode, int bitrate_kbps, const uint8_t *const *hide_bits, const int32_t *n_hide,
                              mp3s_buf **owner, mp3s_file *out, int32_t *status);
 
+/* ---------------------------------------------------------------- QMDCT on the device, section vi-g: spectra as tensors, Markov features
+ * (behind (vi-f); the label stands without parentheses and behind the title: the next heading of the dashed form is (vii))
+ * replaces: nothing in the reference -- its decoder keeps the quantised MDCT coefficients (the `is` values of the Huffman decode) to
+ *           itself.  They are what a payload lives in, and what MP3 steganalysis of ANY encoder works from; (vi-e) speaks for this
+ *           encoder family only.
+ * Both calls below stand on the front half of the decode (upload, Huffman decode, the host's repair, no transform), as (vi-e) does.
+ * For one stream of n_frames frames and nch channels, d_is is the decoder's own layout, int16 [frame][2 gr][2 ch][576]:
+ *   G = 2 * n_frames granule rows;  q[c][g][k] = is[g >> 1][g & 1][c][k];  a = |q| in int32 (-32768 gives 32768).
+ * The frame a decoder repeats behind a bad header (dup_last_frame) has no spectrum of its own and is not a row.  A mono stream has rows
+ * for c = 0 only; whatever lies at ch 1 of d_is is never read.  Rows are taken as they lie: short and mixed blocks keep their own line
+ * order (three interleaved windows), nothing is reordered -- mp3s_table_audit.window_units says how many units of a file are such.
+ *
+ * Features.  T = MP3S_QMDCT_T, B = 2 T + 1 = 9, K = n_lines (1 .. 576): only the lines k < K count.  Per stream AND channel, all int64
+ * and exact:
+ *   hist[v], v = 0 .. 15:  the number of (g, k), g < G, k < K, with min(a, 15) == v.
+ *   dh[g][k] = clamp(a[g][k] - a[g][k+1], -T, T) for k + 1 < K;
+ *   intra[i][j]:  the number of (g, k), g < G, k + 2 < K, with dh[g][k] == i - T and dh[g][k+1] == j - T.
+ *   dv[g][k] = clamp(a[g][k] - a[g+1][k], -T, T) for g + 1 < G;
+ *   inter[i][j]:  the number of (g, k), g + 2 < G, k < K, with dv[g][k] == i - T and dv[g+1][k] == j - T.
+ *   max_abs:  the maximum of a over the counted lines, 0 without rows.   bandwidth:  1 + the largest k < K with a != 0 in any row, 0 if none.
+ * So sum(hist) = G K, sum(intra) = G max(K - 2, 0), sum(inter) = max(G - 2, 0) K.  Probabilities are a division the caller does.
+ * The work of a stream is cut into slices of MP3S_QMDCT_SLICE granule rows of one channel, one workgroup each: a slice [s0, s1) owns
+ * the hist and intra terms of its rows and the inter terms whose FIRST row lies in it (it reads rows up to s1 + 1 where they exist).
+ * Every term has one owner and the sums are integers: the result does not depend on the order the slices arrive in. */
+#define MP3S_QMDCT_T 4
+#define MP3S_QMDCT_SLICE 64
+typedef struct { int64_t hist[16], intra[9][9], inter[9][9], max_abs, bandwidth; } mp3s_qmdct_channel; /* 180 * 8 = 1440 bytes */
+typedef struct { mp3s_qmdct_channel ch[2]; int32_t n_frames, channels, sampling_rate, kbps, n_lines, reserved; } mp3s_qmdct_features; /* 2904 bytes */
+/* k_qmdct_features alone (k_qmdct.hpp), asynchronous on the context's stream.  d_segs [n_segs] are the streams (mp3s_table_audit_seg:
+ * first_frame, n_frames) of the batch d_is of n_frames frames; h_segs is the same table on the host, read before the call returns: it
+ * sizes the grid -- one workgroup per (segment, channel, slice) --, which travels on the stream from a buffer the context keeps, by the
+ * rule of mp3s_pcm_diff_dev.  d_out [n_segs] is written completely (cleared on the stream in front of the kernel; the caller clears
+ * nothing): n_frames, channels = nch and n_lines filled in, sampling_rate and kbps 0, ch[1] of a mono batch zero.  A segment of 0
+ * frames gets zeros.  Null pointers, n_frames <= 0, n_segs <= 0, nch outside {1, 2}, n_lines outside [1, 576], a d_is that is not
+ * 4-byte or a d_out that is not 8-byte aligned, an h_segs entry that reaches outside the batch: MP3S_E_ARG (checked without a device). */
+int mp3s_qmdct_features_dev(mp3s_ctx *ctx, const int16_t *d_is, int n_frames, int nch, const mp3s_table_audit_seg *d_segs,
+                            const mp3s_table_audit_seg *h_segs, int n_segs, int n_lines, mp3s_qmdct_features *d_out);
+/* The features of a list of MP3 files on the frame of the list-of-files calls: scanned on the host threads, grouped by channel count,
+ * per group ONE batch through the front half of the decode and one k_qmdct_features launch; 2904 bytes per file come down.
+ * sampling_rate and kbps are the last frame's, as in every list call.  A file without a frame gets zeros with its header fields.
+ * status[i] / mp3s_last_error() by the rule of every list call (MP3S_E_ARG for a null file).  The records point at nothing: no owner. */
+int mp3s_qmdct_features_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, int n_lines,
+                              mp3s_qmdct_features *out, int32_t *status);
+/* The spectra themselves in the caller's device memory: int16 [B][C][Gt][576], row-major, C = 1 or 2, Gt granule rows a slot: element
+ * (b, c, g, k) at (((b * C) + c) * Gt + g) * 576 + k. */
+typedef struct {
+    int64_t src_frame;      /* first frame of the stream in d_is */
+    int64_t n_frames;       /* frames the stream has there (>= 0) */
+    int64_t first_granule;  /* where the window starts inside the stream (>= 0; may lie at or behind 2 n_frames) */
+    int32_t slot;           /* b: the item's rows go to d_out[b][.][0..Gt) */
+    int32_t reserved;
+} mp3s_qmdct_batch_item; /* 32 bytes */
+typedef struct { int32_t n_frames, nch, sampling_rate, bit_rate; int64_t n_granules, first_granule, valid_granules; } mp3s_qmdct_batch_info; /* 40 bytes */
+/* k_qmdct_batch alone (k_qmdct.hpp), asynchronous on the context's stream.  With valid = clamp(2 n_frames - first_granule, 0, Gt), row
+ * (slot, c, g) for g < valid and c < nch is q[c][first_granule + g] of the item's stream; every other row of the slot is written as
+ * zero (a mono item in a two-channel batch gets a zero plane 1).  nch == 2 with out_channels == 1: MP3S_E_ARG -- there is no
+ * meaningful downmix of quantised values.  Every element of a slot has one writer, nothing has to be cleared first and nothing outside
+ * the slot is touched; the slots of different items must differ.  d_is and d_out must be 16-byte aligned, which makes every row
+ * aligned: 16-byte loads and stores only.  h_items is the same table on the host, read before the call returns (the launch geometry
+ * travels as mp3s_pcm_batch_dev's does).  Null pointers, n_items <= 0, nch or out_channels outside {1, 2}, Gt <= 0 or above 2^24, a
+ * misaligned pointer, a negative field of an item: MP3S_E_ARG (checked without a device). */
+int mp3s_qmdct_batch_dev(mp3s_ctx *ctx, const int16_t *d_is, int nch, const mp3s_qmdct_batch_item *d_items,
+                         const mp3s_qmdct_batch_item *h_items, int n_items, int out_channels, int64_t Gt, int16_t *d_out);
+/* A list of MP3 files into the caller's batch d_out [n_files][out_channels][Gt][576] (device memory, out_bytes of it), by the rules of
+ * mp3s_pcm_batch_decode_files with rows read as granules: per channel count ONE front half of the decode and one k_qmdct_batch launch
+ * write file i's rows [first_granules[i], first_granules[i] + Gt) into slot i (first_granules NULL: 0).  info[i]: the header fields,
+ * n_granules = 2 n_frames, first_granule as given, valid_granules = clamp(n_granules - first_granule, 0, Gt).  status[i]: with status a
+ * file that fails alone does not spoil the others (a failing batch is run again file by file), without it the first failing file
+ * fails the call; a stereo file with out_channels == 1 fails alone with MP3S_E_ARG.  A failed file has a zeroed info[i], a failed or
+ * frameless file valid_granules 0 and a zeroed slot.  out_bytes < n_files * out_channels * Gt * 1152, a negative first granule, a
+ * d_out that is not 16-byte aligned: MP3S_E_ARG before anything is touched.  d_out == NULL is the sizing call: only the front end
+ * runs, info is filled (valid_granules 0); Gt and out_bytes are ignored.  The call returns behind a synchronise of the context's stream. */
+int mp3s_qmdct_batch_decode_files(mp3s_ctx *ctx, const uint8_t *const *mp3s, const size_t *lens, int n_files, const int64_t *first_granules /* NULL: 0 */,
+                                  int64_t Gt, int out_channels, int16_t *d_out, size_t out_bytes, mp3s_qmdct_batch_info *info, int32_t *status);
+
 /* ---------------------------------------------------------------- (vii) asynchronous host-fed pipeline
  * replaces: a loop of Steganography.hide_message / clear_file over many files or batches of files -- reference
  *           steganography.py:133-182, whose two serial frame loops (decoder/MP3_Parser.py:68-80, encoder/MP3_Encoder.py:

@@ -221,6 +221,54 @@ int launch_pcm_batch(hipStream_t stream, const int16_t *d_pcm, int nch, const mp
 int launch_pcm_unbatch(hipStream_t stream, const void *d_in, int in_channels, int in_format, int64_t T, const mp3s_pcm_unbatch_item *d_items,
                        const PcmBatchTile *d_tiles, int n_tiles, int16_t *d_pcm);
 
+// QMDCT on the device (k_qmdct.hpp; the rules: include/mp3s.h, vi-g).
+//   k_qmdct_features: one workgroup per (entry of d_tiles, channel): slice `slice` (kQmdctSlice granule rows) of stream `seg` of d_segs.
+//                     A stream of 0 frames has one entry too: its slice 0 writes the record's tail.  The launcher clears d_out [n_segs]
+//                     on the stream in front of the kernel, which adds into it.
+//   k_qmdct_batch:    a lane owns one 16-byte piece of a slot's out_channels * Gt rows of 72 pieces; item and tile from d_tiles
+//                     (PcmBatchTile: lanes [first * kPcmBatchThreads, + kPcmBatchThreads) of item `item`).
+constexpr int kQmdctSlice = MP3S_QMDCT_SLICE;
+constexpr int64_t kQmdctMaxRows = (int64_t)1 << 24;   // Gt of a batch
+struct QmdctTile { uint32_t seg, slice; };   // 8 bytes
+// appends the entries of segs[0 .. n_segs) (anything with push_back); false: more than a grid takes
+template <class Tiles>
+bool qmdct_feature_tiles(const mp3s_table_audit_seg *segs, int n_segs, Tiles &tiles)
+{
+    uint64_t n = tiles.size();
+    for (int s = 0; s < n_segs; s++) n += segs[s].n_frames <= 0 ? 1 : ((uint64_t)2 * (uint64_t)segs[s].n_frames + kQmdctSlice - 1) / kQmdctSlice;
+    if (n > 0x7fffffffu) return false;
+    for (int s = 0; s < n_segs; s++) {
+        const uint64_t per = segs[s].n_frames <= 0 ? 1 : ((uint64_t)2 * (uint64_t)segs[s].n_frames + kQmdctSlice - 1) / kQmdctSlice;
+        for (uint64_t k = 0; k < per; k++) tiles.push_back(QmdctTile{(uint32_t)s, (uint32_t)k});
+    }
+    return true;
+}
+// ... of n_items items of a batch of Gt rows a plane
+template <class Tiles>
+bool qmdct_batch_tiles(int n_items, int out_channels, int64_t Gt, Tiles &tiles)
+{
+    if (n_items <= 0 || out_channels < 1 || out_channels > 2 || Gt <= 0 || Gt > kQmdctMaxRows) return false;
+    const uint64_t per = ((uint64_t)out_channels * (uint64_t)Gt * 72 + kPcmBatchThreads - 1) / kPcmBatchThreads;
+    if ((uint64_t)tiles.size() + per * (uint64_t)n_items > 0x7fffffffu) return false;
+    for (int i = 0; i < n_items; i++)
+        for (uint64_t f = 0; f < per; f++) tiles.push_back(PcmBatchTile{(uint32_t)i, (uint32_t)f});
+    return true;
+}
+inline bool qmdct_batch_items_ok(const mp3s_qmdct_batch_item *items, int n_items)
+{
+    for (int i = 0; i < n_items; i++)
+        if (items[i].src_frame < 0 || items[i].n_frames < 0 || items[i].first_granule < 0 || items[i].slot < 0 || items[i].src_frame > 0x7fffffff ||
+            items[i].n_frames > 0x7fffffff || items[i].first_granule > ((int64_t)1 << 40))
+            return false;
+    return true;
+}
+// d_is: 4-byte aligned; d_out: [n_segs], 8-byte aligned
+int launch_qmdct_features(hipStream_t stream, const int16_t *d_is, int nch, const mp3s_table_audit_seg *d_segs, int n_segs, const QmdctTile *d_tiles,
+                          int n_tiles, int n_lines, mp3s_qmdct_features *d_out);
+// d_is and d_out: 16-byte aligned; d_out [slots][out_channels][Gt][576] int16
+int launch_qmdct_batch(hipStream_t stream, const int16_t *d_is, int nch, const mp3s_qmdct_batch_item *d_items, const PcmBatchTile *d_tiles, int n_tiles,
+                       int out_channels, int64_t Gt, int16_t *d_out);
+
 // WAV bytes -> int16 PCM frames of an encode batch (k_wav.hpp): per stream the byte offset of its first sample in the image (any
 // alignment), its first frame in the batch and its frames.  d_image needs kWavSlack readable bytes behind the last sample taken.
 struct WavRun { uint64_t src; uint32_t first_frame, n_frames; };   // 16 bytes

@@ -33,6 +33,7 @@ __constant__ __attribute__((aligned(64))) int32_t c_fl_sign[ANALYSIS_SIGN_STREAM
 #include "k_pcmdiff.hpp"
 #include "k_pcmalign.hpp"
 #include "k_pcmbatch.hpp"
+#include "k_qmdct.hpp"
 #include "k_pack.hpp"
 #include "k_chain.hpp"
 #include "k_wav.hpp"
@@ -476,6 +477,33 @@ int launch_pcm_batch(hipStream_t stream, const int16_t *d_pcm, int nch, const mp
     default: PCM_BATCH_LAUNCH(2, 2, true); break;
     }
 #undef PCM_BATCH_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// k_qmdct_features: the records cleared on the stream, then one workgroup per (tile of d_tiles, channel), which adds into them
+int launch_qmdct_features(hipStream_t stream, const int16_t *d_is, int nch, const mp3s_table_audit_seg *d_segs, int n_segs, const QmdctTile *d_tiles,
+                          int n_tiles, int n_lines, mp3s_qmdct_features *d_out)
+{
+    if (n_segs <= 0) return 0;
+    if ((nch != 1 && nch != 2) || n_lines < 1 || n_lines > 576 || n_tiles < n_segs || ((uintptr_t)d_is & 3) || ((uintptr_t)d_out & 7)) return (int)hipErrorInvalidValue;
+    if (const hipError_t e = hipMemsetAsync(d_out, 0, (size_t)n_segs * sizeof(mp3s_qmdct_features), stream)) return (int)e;
+    hipLaunchKernelGGL(k_qmdct_features, dim3((unsigned)n_tiles, (unsigned)nch), dim3(QM_WAVES * 64), 0, stream, d_is, d_segs, d_tiles, nch, n_lines, d_out);
+    return (int)hipGetLastError();
+}
+
+// k_qmdct_batch: one workgroup per tile of d_tiles; the channel counts are the launch's (template arguments)
+int launch_qmdct_batch(hipStream_t stream, const int16_t *d_is, int nch, const mp3s_qmdct_batch_item *d_items, const PcmBatchTile *d_tiles, int n_tiles,
+                       int out_channels, int64_t Gt, int16_t *d_out)
+{
+    if (n_tiles <= 0) return 0;
+    if ((nch != 1 && nch != 2) || (out_channels != 1 && out_channels != 2) || nch > out_channels || Gt <= 0 || Gt > kQmdctMaxRows ||
+        ((uintptr_t)d_is & 15) || ((uintptr_t)d_out & 15))
+        return (int)hipErrorInvalidValue;
+#define QMDCT_BATCH_LAUNCH(N, C) hipLaunchKernelGGL((k_qmdct_batch<N, C>), dim3((unsigned)n_tiles), dim3(kPcmBatchThreads), 0, stream, d_is, d_items, d_tiles, Gt, d_out)
+    if (out_channels == 1) QMDCT_BATCH_LAUNCH(1, 1);
+    else if (nch == 1) QMDCT_BATCH_LAUNCH(1, 2);
+    else QMDCT_BATCH_LAUNCH(2, 2);
+#undef QMDCT_BATCH_LAUNCH
     return (int)hipGetLastError();
 }
 

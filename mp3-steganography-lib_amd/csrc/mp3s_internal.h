@@ -55,13 +55,13 @@ enum PoolSlot : int {
     kPoolFrameHdr, kPoolPcmChunk, kPoolHufStatus, kPoolMainData, kPoolSideInfo,   // decode_front: headers, a chunk of PCM on its way down, Huffman status, main data, side records
     kPoolPcm0,              // int16 PCM that stays on the device: reencode_decode, the pair calls, wav_to_device, the PCM batch calls (mp3s_pcm_batch.cpp), set 0 of a pipe; the table audit, which decodes no PCM, keeps its unit records here
     kPoolPcmUp,             // the PCM an encode brings from the host (encode_batch without pcm_dev)
-    kPoolInputs,            // the host-made input block of the call: the encoder's (EncLayout), the pair calls', the audit's stream table, the workgroup tables of mp3s_pcm_diff_dev / mp3s_pcm_align_dev, [items | workgroup table] of the PCM batch launches
+    kPoolInputs,            // the host-made input block of the call: the encoder's (EncLayout), the pair calls', the audit's stream table, the workgroup tables of mp3s_pcm_diff_dev / mp3s_pcm_align_dev, [items | workgroup table] of the PCM batch launches, [streams or items | workgroup table] of the QMDCT launches (mp3s_qmdct_files.cpp)
     kPoolMdct,              // encode_batch, capacity_batch: MDCT lines [n_all][2][2][576]
     kPoolRedo,              // enc_resolve: entries of the exact re-runs
     kPoolIx, kPoolGrOut, kPoolEnergy,   // encode_batch, capacity_batch: quantised lines, GrInfo records, band energies
     kPoolChainAgg,          // chain_agg_bytes(n) of the chain check: encode_batch, capacity_batch, every job of a pipe
     kPoolMp3, kPoolScfsi,   // encode_batch: the packed bytes, the scalefactor selection (capacity_batch packs nothing and takes neither)
-    kPoolSmall,             // the small results one copy brings down: of an encode (small_bytes; capacity_batch: + capacity records and profile), of the pair calls, of the audit
+    kPoolSmall,             // the small results one copy brings down: of an encode (small_bytes; capacity_batch: + capacity records and profile), of the pair calls, of the audit, the QMDCT feature records
     kPoolVarEntries, kPoolVarIx, kPoolVarOut, kPoolVarEnergy, kPoolVarPairs,   // message variants: enc_resolve's launches take all five, the entries inside the first rate-loop launch
                             // (enc_variant_buffers) Ix, Out and Energy -- their selection is through before a resolve begins
     kPoolIs1, kPoolSi1, kPoolPcm1,      // set 1 of a pipe
@@ -131,7 +131,7 @@ struct mp3s_ctx {
     hipEvent_t ev_pcm_tiles = nullptr;
     // ... and the block [workgroup table | given lags] of the last mp3s_pcm_align_dev, by the same rule and behind the same event
     std::vector<uint8_t> h_pcm_align;
-    // ... and the block [items | workgroup table] of the last PCM batch launch (mp3s_pcm_batch.cpp), by the same rule and behind the same event
+    // ... and the block [items | workgroup table] of the last PCM batch launch (mp3s_pcm_batch.cpp) or QMDCT launch (mp3s_qmdct_files.cpp), by the same rule and behind the same event
     std::vector<uint8_t> h_pcm_batch;
     static int ensure(void *&buf, size_t &have, size_t bytes)
     {

@@ -267,6 +267,37 @@ BATCH_FORMATS = {"i16": BATCH_I16, "f32": BATCH_F32, BATCH_I16: BATCH_I16, BATCH
 BATCH_DTYPES = {BATCH_I16: np.dtype(np.int16), BATCH_F32: np.dtype(np.float32)}
 
 
+class QmdctChannel(C.Structure):
+    """mp3s_qmdct_channel: the features of one channel of a stream (include/mp3s.h, vi-g)"""
+    _fields_ = [("hist", C.c_int64 * 16), ("intra", (C.c_int64 * 9) * 9), ("inter", (C.c_int64 * 9) * 9), ("max_abs", C.c_int64), ("bandwidth", C.c_int64)]
+
+
+class QmdctFeatures(C.Structure):
+    """mp3s_qmdct_features: what mp3s_qmdct_features_files answers per file and k_qmdct_features writes per stream"""
+    _fields_ = [("ch", QmdctChannel * 2), ("n_frames", C.c_int32), ("channels", C.c_int32), ("sampling_rate", C.c_int32), ("kbps", C.c_int32),
+                ("n_lines", C.c_int32), ("reserved", C.c_int32)]
+
+
+class QmdctBatchItem(C.Structure):
+    _fields_ = [("src_frame", C.c_int64), ("n_frames", C.c_int64), ("first_granule", C.c_int64), ("slot", C.c_int32), ("reserved", C.c_int32)]
+
+
+class QmdctBatchInfo(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
+                ("n_granules", C.c_int64), ("first_granule", C.c_int64), ("valid_granules", C.c_int64)]
+
+
+QMDCT_T, QMDCT_SLICE = 4, 64          # MP3S_QMDCT_T, MP3S_QMDCT_SLICE
+QMDCT_CHANNEL_DTYPE = np.dtype([("hist", "<i8", (16,)), ("intra", "<i8", (9, 9)), ("inter", "<i8", (9, 9)), ("max_abs", "<i8"), ("bandwidth", "<i8")])
+QMDCT_FEATURES_DTYPE = np.dtype([("ch", QMDCT_CHANNEL_DTYPE, (2,)), ("n_frames", "<i4"), ("channels", "<i4"), ("sampling_rate", "<i4"), ("kbps", "<i4"),
+                                 ("n_lines", "<i4"), ("reserved", "<i4")])
+QMDCT_BATCH_ITEM_DTYPE = np.dtype([("src_frame", "<i8"), ("n_frames", "<i8"), ("first_granule", "<i8"), ("slot", "<i4"), ("reserved", "<i4")])
+QMDCT_BATCH_INFO_DTYPE = np.dtype([("n_frames", "<i4"), ("nch", "<i4"), ("sampling_rate", "<i4"), ("bit_rate", "<i4"),
+                                   ("n_granules", "<i8"), ("first_granule", "<i8"), ("valid_granules", "<i8")])
+assert QMDCT_CHANNEL_DTYPE.itemsize == 1440 and QMDCT_FEATURES_DTYPE.itemsize == 2904
+assert QMDCT_BATCH_ITEM_DTYPE.itemsize == 32 and QMDCT_BATCH_INFO_DTYPE.itemsize == 40
+
+
 class IndexInfo(C.Structure):
     _fields_ = [("n_frames", C.c_int64), ("nch", C.c_int32), ("sampling_rate", C.c_int32), ("bit_rate", C.c_int32),
                 ("dup_last_frame", C.c_int32), ("gpu_ok", C.c_int32), ("reserved", C.c_int32)]
@@ -320,6 +351,8 @@ RECORDS = {
     "pcm_batch_item": (PcmBatchItem, PCM_BATCH_ITEM_DTYPE), "pcm_unbatch_item": (PcmUnbatchItem, PCM_UNBATCH_ITEM_DTYPE),
     "pcm_batch_info": (PcmBatchInfo, PCM_BATCH_INFO_DTYPE), "pcm_resample_ratio": (PcmResampleRatio,),
     "pcm_resample_item": (PcmResampleItem, PCM_RESAMPLE_ITEM_DTYPE), "pcm_batch_info_at": (PcmBatchInfoAt, PCM_BATCH_INFO_AT_DTYPE),
+    "qmdct_channel": (QmdctChannel, QMDCT_CHANNEL_DTYPE), "qmdct_features": (QmdctFeatures, QMDCT_FEATURES_DTYPE),
+    "qmdct_batch_item": (QmdctBatchItem, QMDCT_BATCH_ITEM_DTYPE), "qmdct_batch_info": (QmdctBatchInfo, QMDCT_BATCH_INFO_DTYPE),
     "pipe_stats": (PipeStats,)}
 
 VOID = object()              # a restype of PROTOTYPES: the function returns nothing
@@ -435,6 +468,10 @@ def _prototypes():
         "mp3s_pcm_batch_resample_dev": (None, [vp, vp, i32, vp, i32, i32, i32, i64, vp]),
         "mp3s_pcm_batch_decode_files_at": (None, [vp, vp, vp, i32, i32, vp, i64, i32, i32, vp, sz, vp, vp]),
         "mp3s_pcm_batch_encode_at": (None, [vp, vp, i32, i32, i32, i64, vp, i32, i32, i32, vp, vp, pvp, vp, vp]),
+        "mp3s_qmdct_features_dev": (None, [vp, vp, i32, i32, vp, vp, i32, i32, vp]),
+        "mp3s_qmdct_features_files": (None, [vp, vp, vp, i32, i32, vp, vp]),
+        "mp3s_qmdct_batch_dev": (None, [vp, vp, i32, vp, vp, i32, i32, i64, vp]),
+        "mp3s_qmdct_batch_decode_files": (None, [vp, vp, vp, i32, vp, i64, i32, vp, sz, vp, vp]),
         "mp3s_pipe_create": (None, [vp, i32, sz, i32, pvp]),
         "mp3s_pipe_destroy": (VOID, [vp]),
         "mp3s_pipe_submit": (None, [vp, vp, vp, i32, vp, vp, pi64]),

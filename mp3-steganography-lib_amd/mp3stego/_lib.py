@@ -971,6 +971,86 @@ class Context:
         own = _Owner(owner)
         return _per_file(out, status, lambda f: _file_dict(f, own), n=n)
 
+    # ---- QMDCT on the device (include/mp3s.h section vi-g)
+    @staticmethod
+    def _qmdct_features(x):
+        """the dict of an mp3s_qmdct_features (a ctypes record or a numpy one): the arrays are copies, channels 0 .. channels - 1"""
+        r = np.frombuffer(bytes(x), dtype=QMDCT_FEATURES_DTYPE)[0] if isinstance(x, C.Structure) else x
+        nch = int(r["channels"])
+        ch = r["ch"][:nch]
+        return {"hist": ch["hist"].copy(), "intra": ch["intra"].copy(), "inter": ch["inter"].copy(), "max_abs": ch["max_abs"].copy(),
+                "bandwidth": ch["bandwidth"].copy(), "n_frames": int(r["n_frames"]), "n_granules": 2 * int(r["n_frames"]), "channels": nch,
+                "sampling_rate": int(r["sampling_rate"]), "kbps": int(r["kbps"]), "n_lines": int(r["n_lines"])}
+
+    def qmdct_features(self, mp3s, lines=576):
+        """Markov and histogram features of the quantised MDCT coefficients of a list of MP3 files (mp3s_qmdct_features_files), the
+        input of general MP3 steganalysis, computed on the device from the Huffman-decoded spectrum; no transform runs.  With
+        a = |q| over the granule rows of a channel and the lines k < lines: "hist" int64 [channels, 16] counts min(a, 15), "intra" /
+        "inter" [channels, 9, 9] count the pairs of consecutive differences of a along a row / down the rows, clipped to +-QMDCT_T
+        (include/mp3s.h, vi-g, has the exact definitions), "max_abs" and "bandwidth" [channels]; beside them n_frames, n_granules,
+        channels, sampling_rate, kbps, n_lines.  Counts, not probabilities.  mp3s: byte strings (None: a null file, which gets its
+        code).  Returns one entry per file: that dict, or the Mp3sError of the file."""
+        if len(mp3s) == 0:
+            return []
+        n, _keep, files, lens = _file_list(mp3s, none_is_null=True)
+        out, status = (QmdctFeatures * n)(), (C.c_int32 * n)()
+        check(lib().mp3s_qmdct_features_files(self.handle, files, lens, n, int(lines), out, status))
+        return _per_file(out, status, self._qmdct_features)
+
+    def qmdct_features_dev(self, is_, segs, nch, lines=576):
+        """test aid: k_qmdct_features alone (mp3s_qmdct_features_dev) on int16 [n_frames][2][2][576] samples and TABLE_AUDIT_SEG_DTYPE
+        streams -> QMDCT_FEATURES_DTYPE [len(segs)]; the records are filled with 0xFF bytes before the call"""
+        is_ = np.ascontiguousarray(is_, dtype=np.int16)
+        segs = np.ascontiguousarray(segs, dtype=TABLE_AUDIT_SEG_DTYPE)
+        n_frames = is_.size // 2304
+        if is_.size != n_frames * 2304:
+            raise ValueError("is_ must hold 2304 samples per frame")
+        with self.device_scope() as dev:
+            d_is, d_segs = dev.to_device(is_ if is_.size else np.zeros(8, dtype=np.int16)), dev.to_device(segs)
+            d_out = dev.alloc(max(len(segs), 1) * QMDCT_FEATURES_DTYPE.itemsize)
+            check(lib().mp3s_dev_memset(self.handle, d_out, 0xFF, max(len(segs), 1) * QMDCT_FEATURES_DTYPE.itemsize))
+            check(lib().mp3s_qmdct_features_dev(self.handle, d_is, n_frames, int(nch), d_segs, segs.ctypes.data, len(segs), int(lines), d_out))
+            return self.download(d_out, QMDCT_FEATURES_DTYPE, (len(segs),))
+
+    def qmdct_batch_dev(self, is_, items, nch, channels, granules, guard_rows=2):
+        """test aid: k_qmdct_batch alone (mp3s_qmdct_batch_dev) on int16 [n_frames][2][2][576] samples and QMDCT_BATCH_ITEM_DTYPE
+        items -> (batch int16 [slots][channels][granules][576], slots = 1 + the largest slot; guard rows in front of and behind it as
+        they came back).  Batch and guards are filled with 0x5A bytes before the call."""
+        is_ = np.ascontiguousarray(is_, dtype=np.int16)
+        items = np.ascontiguousarray(items, dtype=QMDCT_BATCH_ITEM_DTYPE)
+        slots = int(items["slot"].max()) + 1 if len(items) else 1
+        body, guard = slots * int(channels) * int(granules) * 1152, int(guard_rows) * 1152
+        with self.device_scope() as dev:
+            d_is, d_items = dev.to_device(is_ if is_.size else np.zeros(8, dtype=np.int16)), dev.to_device(items)
+            d_all = dev.alloc(body + 2 * guard)
+            check(lib().mp3s_dev_memset(self.handle, d_all, 0x5A, body + 2 * guard))
+            check(lib().mp3s_qmdct_batch_dev(self.handle, d_is, int(nch), d_items, items.ctypes.data, len(items), int(channels), int(granules),
+                                             _addr(d_all.value + guard)))
+            got = self.download(d_all, np.int16, ((body + 2 * guard) // 2,))
+        g = guard // 2
+        return got[g:g + body // 2].reshape(slots, int(channels), int(granules), 576), (got[:g], got[g + body // 2:])
+
+    def qmdct_batch(self, mp3s, d_out, out_bytes, granules, first_granules=None, channels=2, per_file=False):
+        """The quantised MDCT coefficients of a list of MP3 files in the caller's device memory as ONE batch int16 [len(mp3s)][channels]
+        [granules][576] at the device address d_out (mp3s_qmdct_batch_decode_files; 16-byte aligned): file i's granule rows from
+        first_granules[i] (0) on into slot i, zeros behind its last row and in plane 1 of a mono file; nothing comes down.  Returns one
+        dict per file: n_frames, channels, sampling_rate, bit_rate, n_granules, first_granule, valid_granules.  per_file=True: a file
+        that fails (None, damage, a stereo file with channels=1) yields its Mp3sError and a zeroed slot, the others are unaffected;
+        otherwise the first such file fails the call.  d_out=None: the sizing call -- only the front end runs."""
+        n = len(mp3s)
+        if n == 0:
+            return []
+        _, _keep, ptrs, lens = _file_list(mp3s, none_is_null=True)
+        first = None
+        if first_granules is not None:
+            if len(first_granules) != n:
+                raise ValueError("one first granule per file")
+            first = (C.c_int64 * n)(*[int(x) for x in first_granules])
+        info, status = (QmdctBatchInfo * n)(), (C.c_int32 * n)()
+        check(lib().mp3s_qmdct_batch_decode_files(self.handle, ptrs, lens, n, first, int(granules), int(channels), _addr(d_out), int(out_bytes),
+                                                  info, status if per_file else None))
+        return _per_file(info, status, _batch_info_dict)
+
     def debug_wav_gather(self, wavs):
         """test aid: the PCM buffer k_wav_gather makes of these WAV files, int16 [frames of all files][1152][2]"""
         n, files, lens, _, _, _, _keep = _encode_args(wavs, 128, None, None)

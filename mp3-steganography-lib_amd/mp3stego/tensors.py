@@ -4,7 +4,8 @@ decode() leaves a list of MP3 files in a device tensor [B, C, T] -- channels fir
 encode() makes MP3 files (with hidden messages, if asked) of such a tensor.  The samples do not cross PCIe in either direction: the
 library's kernels read and write the tensor's memory.  decode(samplerate=...) leaves every slot at ONE sampling rate whatever the files'
 rates are (16 kHz for a model, say), and encode(resample=...) takes a tensor at any rate: both resample on the device, with the exact
-integer polyphase filter of the "wav_resample" option.
+integer polyphase filter of the "wav_resample" option.  qmdct() (section vi-g) leaves the quantised MDCT coefficients of the list -- what
+a hidden payload lives in -- in an int16 device tensor [B, C, granules, 576]: the front half of the decode, no transform.
 
 This is the only module of the package that imports torch, and it does so when a function is first called: the C library and
 mp3stego._lib stay torch-free.  The library works on its context's own stream; both functions synchronise torch's current stream of
@@ -84,6 +85,46 @@ def decode(mp3s, rows=None, first_rows=None, channels=2, dtype=None, ctx=None, o
                              _formats(torch)[dtype], per_file, samplerate)
     lengths = torch.tensor([0 if isinstance(i, Exception) else i["valid_rows"] for i in infos], dtype=torch.int64)
     return out, lengths, infos
+
+
+def qmdct(mp3s, granules=None, first_granules=None, channels=2, ctx=None, out=None, per_file=False):
+    """The quantised MDCT coefficients of the MP3 files `mp3s` (byte strings; None: a missing file) as one device tensor: the int16 `is`
+    values of the Huffman decode, the representation a hidden payload lives in and the input of learned steganalysis (include/mp3s.h,
+    section vi-g).  No transform runs and nothing comes down.
+
+    Returns (batch, infos): batch int16 [len(mp3s), channels, granules, 576] on the context's device, file i's granule rows (two a
+    frame, lines as they lie in the stream: short blocks are not reordered) from first_granules[i] (0) on in batch[i], zeros behind
+    them and in plane 1 of a mono file; infos: the dicts of Context.qmdct_batch, "valid_granules" the rows of a slot that are spectra
+    (per_file=True: the Mp3sError of a file that fails, whose slot is zero; otherwise such a file fails the call).  A stereo file has
+    no one-channel spectrum: with channels=1 it fails.  granules=None sizes the tensor as the largest n_granules - first_granule of
+    the list, which costs one more run of the host front end over the files; say granules when you know it.
+    out= reuses a tensor of the caller's ([len(mp3s), C, granules, 576] int16, contiguous); the work torch's current stream has
+    pending on it is waited for first."""
+    torch = _torch()
+    ctx = ctx or _lib.default_context()
+    n = len(mp3s)
+    if n == 0:
+        raise ValueError("an empty list")
+    device = torch.device("cuda", ctx.device)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dim() != 4 or out.dtype != torch.int16 or out.shape[3] != 576 or out.shape[1] not in (1, 2):
+            raise ValueError("out: an int16 tensor [B, C, granules, 576] with 1 or 2 channels is expected")
+        if not out.is_contiguous():
+            raise ValueError("out: the tensor is not contiguous")
+        if out.device.type != "cuda" or out.device.index != ctx.device:
+            raise ValueError(f"out: the tensor is on {out.device}, the context works on cuda:{ctx.device}")
+        if out.shape[0] != n:
+            raise ValueError(f"out: {out.shape[0]} slots for {n} files")
+        channels, granules = int(out.shape[1]), int(out.shape[2])
+    else:
+        if granules is None:
+            firsts = first_granules if first_granules is not None else [0] * n
+            sized = ctx.qmdct_batch(mp3s, None, 0, 0, channels=int(channels), per_file=per_file)
+            granules = max([1] + [s["n_granules"] - int(f) for s, f in zip(sized, firsts) if not isinstance(s, Exception)])
+        out = torch.empty((n, int(channels), int(granules), 576), dtype=torch.int16, device=device)
+    torch.cuda.current_stream(device).synchronize()       # (the memory may be a block torch's stream has not finished with)
+    infos = ctx.qmdct_batch(mp3s, out.data_ptr(), out.numel() * 2, int(granules), first_granules, int(channels), per_file)
+    return out, infos
 
 
 def encode(batch, lengths, samplerate, bitrate=320, messages=None, hide_bits=None, ctx=None, per_file=False, resample=0):
